@@ -32,6 +32,13 @@ N > 1 : configs[2]: the same trio, kevlar's k-mer banding with band b on GPU b (
 Also on the line: `roofline` (algorithmic bytes / live HIP-event time of the dominant stage), `cpu_baseline`
 (the C oracle on the host cores: one core and all cores), `end_to_end` (FASTQ files on disk -> annotated reads
 through the CLI drivers, host parse and PCIe included).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line; every leg
+beside the headline figure runs with --full only: the live rocprofv3 traffic passes behind roofline.traffic (a plain run
+takes it from a committed profile of the same kernel sources, if there is one), the banded replays behind `banded_checksums` /
+`replay_checksum`, `cpu_baseline`, `end_to_end` and cfg4-band's `downstream` stages.
+--dump-outputs DIR writes what the last timed step handed its caller -- the hits (read, offset, abundances) and the k-mers
+counted -- as float .npy files, so that two builds can be compared output for output on the same seeded family.
 """
 import argparse
 import ctypes
@@ -113,16 +120,24 @@ def parse_args():
     p.add_argument('--no-downstream', action='store_true', help='cfg4-band: count and scan only (no annotated reads, filter, partition)')
     p.add_argument('--traffic', default='live', choices=['live', 'file', 'none'],
                    help='roofline.traffic (HBM bytes of the dominant stage): live = measured by two rocprofv3 --pmc child passes of this '
-                        'command before the timed run (cfg2, one GPU; ~1.5 min); file = the committed profiles/r*_final file if it '
-                        'measured these kernel sources; none')
+                        'command before the timed run (cfg2, one GPU, --full only: a plain run reads the file instead; ~1.5 min); '
+                        'file = the committed profiles/r*_final file if it measured these kernel sources; none')
     p.add_argument('--launch-check', action='store_true', help='only start the ranks and let them meet (no GPU work)')
     p.add_argument('--backend', default='nccl', help='nccl (= RCCL) is what the driver runs; gloo lets two ranks share one GPU in tests')
+    p.add_argument('--full', action='store_true',
+                   help='every leg beside the headline figure as well: live roofline traffic, banded replays, CPU baseline, end-to-end leg, '
+                        'cfg4-band downstream stages (the --no-* switches still leave single legs out)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the hits of the last timed step and its k-mer count to DIR/<name>.npy (float32 / float64, at most 64 MB '
+                        'in all: a fixed, seeded sample of the hits beyond that)')
     args = p.parse_args()
     heavy = args.workload in ('cfg4-band', 'cfg4-proxy')
     if args.steps is None:
         args.steps = 2 if heavy else 20
     if args.warmup is None:
         args.warmup = 1 if heavy else 5
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
     return args
 
 
@@ -244,6 +259,34 @@ def hits_checksum(r, o, a):
     return '{}:{}'.format(len(r), h.hexdigest()[:16])
 
 
+DUMP_BYTES = 64_000_000      # --dump-outputs: all files together, headers included
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, r, o, a, kmers):
+    """--dump-outputs: what the last timed step handed its caller -- the hits as hk.novel_scan returns them, sorted by (read,
+    offset), and the number of k-mers counted -- as DIR/<name>.npy: hit_read, hit_offset, hit_abundance[n, S], kmers_counted.
+    float32 where every value is exact in it (below 2**24), float64 otherwise.  Hits that do not fit the byte budget are
+    sampled: the same seeded choice of rows for the same number of hits, in their order, and hit_rows names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'hit_read': np.asarray(r), 'hit_offset': np.asarray(o), 'hit_abundance': np.asarray(a)}
+    arrays = {name: v.astype(np.float32 if v.size == 0 or int(v.max()) < (1 << 24) else np.float64) for name, v in arrays.items()}
+    n = len(r)
+    row_bytes = sum(v.itemsize * (v.size // n if n else 1) for v in arrays.values())
+    room = DUMP_BYTES - 4096                              # (the .npy headers and kmers_counted)
+    if n * row_bytes > room:
+        rows = room // (row_bytes + 8)                    # (+ the sampled rows' indices)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=rows, replace=False))
+        arrays = {name: v[pick] for name, v in arrays.items()}
+        arrays['hit_rows'] = pick.astype(np.float64)
+    elif os.path.exists(os.path.join(path, 'hit_rows.npy')):
+        os.remove(os.path.join(path, 'hit_rows.npy'))      # (left by an earlier, sampled dump into the same directory)
+    arrays['kmers_counted'] = np.array([kmers], dtype=np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(v))
+
+
 def main():
     args = parse_args()
     wl = dict(WORKLOADS[args.workload])
@@ -263,7 +306,7 @@ def main():
         return launch_check(args, rank, world)
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')       # (ranks started by somebody else's torch.distributed.run: see self_launch)
     global LIVE_PMC
-    if world == 1 and args.gpus == 1 and args.traffic == 'live' and args.workload == 'cfg2':
+    if args.full and world == 1 and args.gpus == 1 and args.traffic == 'live' and args.workload == 'cfg2':
         LIVE_PMC = live_traffic(args)
     import numpy as np
     import torch
@@ -597,6 +640,8 @@ def main():
     assert nhits > 0, 'the synthetic family must yield interesting k-mers'
     assert (a[:, 0] >= args.case_min).all() and (a[:, 1:] <= args.ctrl_max).all()
     selfcheck = {'hits_checksum': hits_checksum(r, o, a)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, o, a, kmers)
     if os.environ.get('BENCH_DUMP_HITS') and rank == 0:
         np.savez_compressed(os.path.join(os.environ['BENCH_DUMP_HITS'], 'step_world{}.npz'.format(world)), r=np.asarray(r), o=np.asarray(o), a=np.asarray(a))
     if band_mask is not None:
@@ -654,7 +699,7 @@ def main():
                                 r=rr[order], o=oo[order], a=aa[order])
         return hits_checksum(rr[order], oo[order], aa[order])
 
-    if not args.no_replay and args.workload in ('cfg2', 'cfg1', 'cfg5'):
+    if args.full and not args.no_replay and args.workload in ('cfg2', 'cfg1', 'cfg5'):
         saved_wall = dict(wall)
         if world == 1:
             selfcheck['banded_checksums'] = {str(nb): replay_bands(nb) for nb in (2, 4, 8)}
@@ -747,7 +792,7 @@ def main():
 
     cpu = e2e = None
     downstream = None
-    if on_device and not args.no_downstream:
+    if args.full and on_device and not args.no_downstream:
         # the step's working buffers (staging for three batches side by side) go back first: `filter` and `partition` are processes of
         # their own in the workflow and allocate their own sketches; the step's peak is noted before
         note_hbm()
@@ -757,7 +802,7 @@ def main():
         props = torch.cuda.get_device_properties(dev_index)
         downstream['hbm_peak_gb'] = round((props.total_memory - hbm_low[0]) / 1e9, 1)
         downstream['hbm_resident_reads_gb'] = round(sum(b.device_bytes() for n in names for b in batches[n]) / 1e9, 1)
-    if rank == 0 and world == 1 and not on_device:
+    if args.full and rank == 0 and world == 1 and not on_device:
         if not args.no_cpu_baseline:
             cpu = cpu_baseline(args, wl, packed, names, synth)
         if not args.no_e2e:

@@ -2,7 +2,7 @@
 # the default bench line of every workload (CPU baseline and end-to-end legs included)
 for w in cfg1 cfg5 cfg4-proxy; do
   s=$(date +%s)
-  timeout 900 python bench.py --workload $w 2>/tmp/err_$w.txt > /tmp/out_$w.json
+  timeout 900 python bench.py --workload $w --full 2>/tmp/err_$w.txt > /tmp/out_$w.json
   echo "$w rc=$? $(( $(date +%s) - s )) s"
   python3 - "$w" <<'PY'
 import sys, json

@@ -41,7 +41,7 @@ def test_self_launch_relays_a_failing_rank():
 
 @pytest.mark.gpu
 def test_self_launch_runs_config_1_on_two_ranks_sharing_the_gpu():
-    res = run_bench('--gpus', '2', '--backend', 'gloo', '--workload', 'cfg1', '--steps', '1', '--warmup', '1',
+    res = run_bench('--gpus', '2', '--backend', 'gloo', '--workload', 'cfg1', '--steps', '1', '--warmup', '1', '--full',
                     '--no-cpu-baseline', '--no-e2e', '--merge', 'mask')
     assert res.returncode == 0, res.stderr[-3000:]
     out = last_json(res.stdout)
@@ -56,7 +56,7 @@ def test_self_launch_runs_config_1_on_two_ranks_sharing_the_gpu():
 def test_exchange_layout_with_its_samples_interleaved_equals_the_banded_replay(ranks, items):
     """bench.py --multi exchange: a sample's records travel while the next sample's shard is cut, its pairs while the next sample's
     records are combined (ShardedTrio.cut_minimizer / combine_minimizer); the merged hits must equal rank 0's replay of the bands"""
-    res = run_bench('--gpus', str(ranks), '--backend', 'gloo', '--workload', 'cfg1', '--steps', '2', '--warmup', '1',
+    res = run_bench('--gpus', str(ranks), '--backend', 'gloo', '--workload', 'cfg1', '--steps', '2', '--warmup', '1', '--full',
                     '--no-cpu-baseline', '--no-e2e', '--multi', 'exchange', '--exchange-items', items)
     assert res.returncode == 0, res.stderr[-3000:]
     out = last_json(res.stdout)
