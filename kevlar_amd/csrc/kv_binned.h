@@ -13,21 +13,19 @@
 // A coarse item (stage A -> stage B) is one u32.  Unweighted (one item per k-mer):
 //   bits  0..15  offset of the bin inside its 65536-bin slice        bits 16..24  slice inside the coarse bucket (< F <= 512)
 // Weighted (one item per distinct k-mer of a batch; saturating adds commute, so a k-mer seen c times is one item of
-// weight c instead of c items): the same layout plus bits 25..31 = weight - 1.  (A 32768-bin variant exists behind
-// KV_BIN_SLICE15=1 -- offset 15 bits, slice 10 bits -- it measured no faster, see kv_bin_plan.)
+// weight c instead of c items): the same layout plus bits 25..31 = weight - 1.
 // A fine item (stage B -> stage C) is the u16 offset, or for weighted items offset | weight << 16.
 #define BIN_W_SHIFT 25
 #define BIN_W_MAX 128u
-#define BIN_SLICE_BITS 16      // unweighted path
-#define BIN_SLICE_BITS_W 15    // weighted path
+#define BIN_SLICE_BITS 16
 
 struct BinGeom {
     int T, F, C;                     // tables, slices per coarse bucket, coarse buckets in use (<= BIN_C)
-    int sbits;                       // log2 of the bins per slice (BIN_SLICE_BITS or BIN_SLICE_BITS_W)
-    uint32_t ringA, ringB;           // LDS ring entries per stream in stages A / B (powers of two)
+    int sbits;                       // log2 of the bins per slice (BIN_SLICE_BITS)
+    uint32_t ringB;                  // LDS ring entries per stream in stage B (a power of two)
     uint32_t recipF;                 // floor(2^32 / F) + 1: slice / F by multiply-high
     uint32_t nslices[BIN_MAX_T];
-    uint32_t tile_lds;               // bytes of dynamic LDS in front of the stage-A rings
+    uint32_t tile_lds;               // bytes of dynamic LDS stage A stages a tile of reads in
     uint32_t nwgA, nwgB;             // writers per coarse bucket (stage-A workgroups) / per slice (stage-B workgroups of the bucket)
     uint32_t quotaA;                 // work units (tiles / list chunks) one stage-A workgroup may take: bounds its segments' fill
     uint64_t cap1, cap2, spill_cap;  // items per PRIVATE segment: every writer owns its own region of every stream,

@@ -10,8 +10,7 @@
 //                   (bin range = F slices of 65536 bins).  Every workgroup owns a private segment
 //                   of every bucket; its write cursor lives in LDS and the item is stored straight
 //                   to HBM (L2 merges the partial lines): no global atomic, no barrier.
-//                   (k_bin_hash is the earlier variant that stages items in LDS rings and flushes
-//                   coalesced bursts; k_bin_list takes hashes from a list instead of reads.)
+//                   (k_bin_list takes hashes from a list instead of reads.)
 //   B  k_bin_split  each coarse bucket is split into its F slices; items shrink to the 16-bit
 //                   offset inside the slice.  The fan-out is too wide for direct stores here, so
 //                   items collect in per-workgroup LDS rings and leave as coalesced bursts.
@@ -43,7 +42,6 @@ namespace {
 #define BIN_B_ITEMS 8       // items per thread per round in stage B
 #define BIN_B_BUDGET 16384  // LDS ring entries per stage-B workgroup
 #define BIN_C_THREADS 1024
-#define BIN_CW_THREADS 512   // weighted stage C: 32-KB slices, four workgroups per CU
 #define BIN_MAX_SEG 512      // stage-B writers per slice (nwgB)
 
 // ---- LDS write-combining rings ------------------------------------------------------------
@@ -169,124 +167,10 @@ __device__ __forceinline__ void rings_store_counts(uint32_t ns, uint32_t written
     if (lane < per_wave && s < ns) counts[(uint64_t)s * stride + writer] = written < cap ? written : cap;
 }
 
-// one k-mer -> T ring appends.  All T ring positions are requested back to back (independent LDS
-// atomics in flight together) before any of them is consumed.
-__device__ __forceinline__ uint32_t bin_push(const Rings<uint32_t> &rs, const BinGeom &g, const SketchDev *__restrict__ sk, uint64_t h)
-{
-    uint32_t sidx[BIN_MAX_T], item[BIN_MAX_T], pos[BIN_MAX_T];
-    uint64_t bins[BIN_MAX_T];
-#pragma unroll
-    for (int t = 0; t < BIN_MAX_T; ++t) {
-        if (t >= g.T) break;
-        const uint64_t bin = fastmod(h, sk->size[t], sk->magic[t]);
-        const uint32_t slice = (uint32_t)(bin >> 16);
-        const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-        bins[t] = bin;
-        item[t] = ((slice - c * (uint32_t)g.F) << 16) | (uint32_t)(bin & 0xffffu);
-        sidx[t] = (uint32_t)t * (uint32_t)g.C + c;
-    }
-#pragma unroll
-    for (int t = 0; t < BIN_MAX_T; ++t)
-        if (t < g.T) pos[t] = atomicAdd(&rs.cnt[sidx[t]], 1u);
-#pragma unroll
-    for (int t = 0; t < BIN_MAX_T; ++t) {
-        if (t >= g.T) break;
-        const uint32_t s_ = sidx[t];
-        if (pos[t] - rs.base[s_] < rs.R) rs.ring[s_ * rs.R + ((pos[t] + rs.skew * s_) & (rs.R - 1))] = item[t];
-        else spill_item(g, t, bins[t]);
-    }
-    return 0u;
-}
-
 // ---- stage A -----------------------------------------------------------------------------
-template <int THREADS, int NW>
-__global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash(   // 3 x 8 waves (or 1 x 16) per CU must fit the register file
-    ReadsDev rd, uint32_t n_tiles, const SketchDev *__restrict__ sk,
-                                                      const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
-{
-    __shared__ TileShared sh;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (threadIdx.x == 0) sh.ascii = (uint32_t *)smem;     // [0, tile_lds): staged ASCII; rings follow
-    const uint32_t ns = (uint32_t)(g.T * g.C);
-    Rings<uint32_t> rs;
-    rs.R = g.ringA;
-    rs.skew = 1;
-    rs.ring = (uint32_t *)(smem + g.tile_lds);
-    rs.cnt = rs.ring + (size_t)ns * rs.R;
-    rs.base = rs.cnt + ns;
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS) { rs.cnt[s] = 0; rs.base[s] = 0; }
-    __syncthreads();
-    uint32_t written = 0;
-    uint64_t seg_base = 0;        // element index of this lane's private segment (lane <-> stream as in rings_flush)
-    {
-        const uint32_t nwaves = THREADS >> 6, per_wave = (ns + nwaves - 1) / nwaves;
-        const uint32_t mine = (threadIdx.x >> 6) * per_wave + (threadIdx.x & 63);
-        if ((threadIdx.x & 63) < per_wave && mine < ns) seg_base = ((uint64_t)mine * g.nwgA + blockIdx.x) * g.cap1;
-    }
-    auto store = [&](uint64_t idx, uint32_t item) { g.gbuf1[idx] = item; };
-    auto overflow = [&](uint32_t s, uint32_t item) {   // private segment full: keep the increment, apply it later with an atomic
-        const uint32_t t = s / (uint32_t)g.C, c = s % (uint32_t)g.C;
-        spill_item(g, (int)t, (((uint64_t)c * g.F + (item >> 16)) << 16) | (item & 0xffffu));
-    };
-    uint64_t n_added = 0;
-    // tiles are handed out dynamically (one global atomic per tile): a workgroup that becomes resident
-    // late, or shares its CU with fewer siblings, simply takes fewer -- a static deal is hostage to the
-    // slowest workgroup, which showed as 46 vs 64 ms for the same launch on different boxes.  A quota of
-    // 1.5x the average share keeps early workgroups from swallowing everything when the grid is not fully
-    // resident (GPU shared with another stream or process): that overflowed their segments into the spill list
-    __shared__ uint32_t next_tile;
-    for (uint32_t taken = 0; taken < g.quotaA; ++taken) {
-        __syncthreads();
-        if (threadIdx.x == 0) next_tile = (uint32_t)atomicAdd(&g.ctr[4], 1ull);
-        __syncthreads();
-        const uint32_t tile = next_tile;
-        if (tile >= n_tiles) break;
-        uint32_t read0;
-        const uint32_t nr = stage_tile(sh, rd, tile, f.hp.k, 0, 0, read0);
-        const uint32_t total = sh.kpre[nr];
-        // every thread owns a run of consecutive k-mers (rolling register windows when NW > 0); one
-        // k-mer per thread per round, then the workgroup flushes its rings
-        const uint32_t run = (total + THREADS - 1) / THREADS;
-        const uint32_t q0 = threadIdx.x * run, q1 = min(total, q0 + run);
-        KmerRoll<(NW > 0 ? NW : 8)> w;
-        if (NW > 0 && q0 < q1) {
-            locate_kmer(sh, nr, q0, w.r, w.i);
-            roll_load(w, sh, f.hp.k);
-        }
-        for (uint32_t step = 0; step < run; ++step) {
-            const uint32_t q = NW > 0 ? q0 + step : step * THREADS + threadIdx.x;
-            const bool live = NW > 0 ? q < q1 : q < total;
-            if (live) {
-                uint64_t h;
-                if (NW > 0) {
-                    h = roll_hash(w, f.hp);
-                    if (q + 1 < q1) roll_step(w, sh, nr, f.hp.k);
-                } else {
-                    uint32_t r, i;
-                    locate_kmer(sh, nr, q, r, i);
-                    const uint32_t fwd = sh.foff[r] + i;
-                    const uint32_t rc = sh.roff[r] + (sh.len[r] - (uint32_t)f.hp.k - i);
-                    h = kmer_hash_lds(sh.ascii, fwd, rc, f.hp);
-                }
-                if (consume_filter_pass(f, mask, h)) {
-                    n_added += 1;
-                    n_added += bin_push(rs, g, sk, h);
-                }
-            }
-            __syncthreads();
-            rings_flush(rs, ns, false, written, seg_base, (uint32_t)g.cap1, store, overflow);
-            __syncthreads();
-        }
-    }
-    rings_flush(rs, ns, true, written, seg_base, (uint32_t)g.cap1, store, overflow);
-    rings_store_counts(ns, written, (uint32_t)g.cap1, g.gcnt1, g.nwgA, blockIdx.x);
-    n_added = wave_sum_u64(n_added);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
-}
-
-// Stage A without LDS rings: every workgroup still owns a private segment of every coarse bucket, but
-// the segment's write cursor lives in LDS and each item is stored straight to HBM -- no barrier, no
-// flush phase between hashing a k-mer and storing its T items.  The write frontier (workgroups x
+// Every workgroup owns a private segment of every coarse bucket; the segment's write cursor lives in
+// LDS and each item is stored straight to HBM -- no barrier, no flush phase between hashing a k-mer
+// and storing its T items.  The write frontier (workgroups x
 // buckets x one 128-B line) sits in L2, which merges the partial lines before they reach HBM.
 template <int THREADS, int NW>
 __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_direct(
@@ -517,7 +401,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_list(
 
 // ---- stage B -----------------------------------------------------------------------------
 // W = weighted items (kv_binned.h): a coarse item carries its increment in bits 25..31 and leaves as offset | increment << 16
-template <bool W, int SBITS>
+template <bool W>
 __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
 {
     typedef typename std::conditional<W, uint32_t, uint16_t>::type Out;
@@ -541,7 +425,7 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
         if ((threadIdx.x & 63) < per_wave && mine < F) seg_base = (((uint64_t)s * F + mine) * g.nwgB + blockIdx.x) * g.cap2;
     }
     Out *gbuf2 = (Out *)g.gbuf2;
-    constexpr uint32_t SB = SBITS, OFFMASK = (1u << SB) - 1u;
+    constexpr uint32_t SB = BIN_SLICE_BITS, OFFMASK = (1u << SB) - 1u;
     auto slice_of = [](uint32_t item) { return W ? (item >> SB) & ((1u << (BIN_W_SHIFT - SB)) - 1u) : item >> SB; };
     auto fine_of = [](uint32_t item) { return W ? (Out)((item & OFFMASK) | (((item >> BIN_W_SHIFT) + 1u) << 16)) : (Out)(item & OFFMASK); };
     auto spill_coarse = [&](uint32_t item) {
@@ -609,118 +493,6 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
     }
     rings_flush(rs, F, true, written, seg_base, (uint32_t)g.cap2, store, overflow, 64u / (uint32_t)sizeof(Out));
     rings_store_counts(F, written, (uint32_t)g.cap2, g.gcnt2 + (uint64_t)s * F * g.nwgB, g.nwgB, blockIdx.x);
-}
-
-// Stage B for weighted items, sorted in LDS (round 5).  The ring kernel above appends 2048 items per round to ~380 LDS rings and
-// then lets a lane per ring look whether its ring has a burst to flush, between two barriers: ~70 lane-instructions per item, and -- like
-// every kernel of the count stage -- bound by instruction issue, not by the 3.4 GB it moves.  Here a workgroup takes 8192 coarse items at
-// a time, ranks them by slice with LDS atomics, lays them out slice by slice in LDS (as coarse items: they carry their slice) and copies
-// that image out with consecutive lanes on consecutive items, converting to fine items on the way: a slice's items of one chunk leave
-// as one contiguous run of ~20.  The scheme of k_skm_split_sorted, for 4-byte items.  MEASURED SLOWER than the rings (1.33 against 1.08 ms
-// per sample: five barriers per 8192 items with two workgroups' worth of registers per thread) and therefore not the default.
-#define BIN_BS_CHUNK 8192u
-#define BIN_BS_MAXSEG 64u          // coarse segments one stage-B workgroup drains (nwgB >= nwgA / 32: at most 32)
-template <int SBITS>
-__global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split_sorted(BinGeom g)
-{
-    __shared__ uint32_t cur[BIN_MAX_F], hist[BIN_MAX_F], off[BIN_MAX_F];
-    __shared__ uint32_t spre[BIN_BS_MAXSEG + 1], scnt[BIN_BS_MAXSEG];
-    __shared__ uint32_t wsum[BIN_B_THREADS / 64];
-    __shared__ uint32_t chunk_items;
-    extern __shared__ __attribute__((aligned(16))) uint32_t bimg[];      // [BIN_BS_CHUNK] coarse items in sorted order
-    const uint32_t s = blockIdx.y;
-    const uint32_t t = s / (uint32_t)g.C, c = s % (uint32_t)g.C, F = (uint32_t)g.F;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr uint32_t SB = SBITS, OFFMASK = (1u << SB) - 1u;
-    auto slice_of = [](uint32_t item) { return (item >> SB) & ((1u << (BIN_W_SHIFT - SB)) - 1u); };
-    auto fine_of = [](uint32_t item) { return (item & OFFMASK) | (((item >> BIN_W_SHIFT) + 1u) << 16); };
-    for (uint32_t f = threadIdx.x; f < F; f += BIN_B_THREADS) { cur[f] = 0; hist[f] = 0; }
-    // the segments seg = blockIdx.x, blockIdx.x + nwgB, ... of coarse stream s, enumerated flat; a segment's count is rounded up to whole
-    // 16-byte vectors in that enumeration (its base is 128-byte aligned, so every vector load is aligned; the padding items are masked)
-    const uint32_t nmine = min((g.nwgA - blockIdx.x + g.nwgB - 1u) / g.nwgB, BIN_BS_MAXSEG);
-    if (threadIdx.x < nmine) {
-        const uint64_t n = g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x + threadIdx.x * g.nwgB];
-        scnt[threadIdx.x] = (uint32_t)(n < g.cap1 ? n : g.cap1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (uint32_t i = 0; i < nmine; ++i) { spre[i] = acc; acc += (scnt[i] + 3u) & ~3u; }
-        spre[nmine] = acc;
-    }
-    __syncthreads();
-    const uint32_t total = spre[nmine];
-    constexpr uint32_t PER = BIN_BS_CHUNK / BIN_B_THREADS / 4u;          // 16-byte vectors per thread and chunk
-    uint32_t *const out = (uint32_t *)g.gbuf2 + ((uint64_t)s * F * g.nwgB + blockIdx.x) * g.cap2;      // + slice * fstride
-    const uint64_t fstride = (uint64_t)g.nwgB * g.cap2;
-    uint4 nv[PER];
-    uint32_t nn[PER];                                  // real items of the vector (0..4)
-    auto request = [&](uint32_t c0) {
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r) {
-            const uint32_t gi = c0 + (r * BIN_B_THREADS + threadIdx.x) * 4u;
-            nv[r] = make_uint4(0, 0, 0, 0); nn[r] = 0;
-            if (gi < total) {
-                uint32_t lo = 0, hi = nmine;
-                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (spre[mid] <= gi) lo = mid; else hi = mid; }
-                const uint32_t at = gi - spre[lo];
-                nn[r] = min(4u, scnt[lo] > at ? scnt[lo] - at : 0u);
-                const uint32_t *src = g.gbuf1 + ((uint64_t)s * g.nwgA + blockIdx.x + (uint64_t)lo * g.nwgB) * g.cap1 + at;
-                if (nn[r]) nv[r] = *(const uint4 *)src;
-            }
-        }
-    };
-    request(0);
-    for (uint32_t c0 = 0; c0 < total; c0 += BIN_BS_CHUNK) {
-        uint32_t it[PER][4], rank[PER][4], have[PER];
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r) { it[r][0] = nv[r].x; it[r][1] = nv[r].y; it[r][2] = nv[r].z; it[r][3] = nv[r].w; have[r] = nn[r]; }
-        request(c0 + BIN_BS_CHUNK);                     // the next chunk's items fly while this one is ranked, laid out and stored
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r)
-#pragma unroll
-            for (uint32_t e = 0; e < 4; ++e) rank[r][e] = e < have[r] ? atomicAdd(&hist[slice_of(it[r][e])], 1u) : 0u;
-        __syncthreads();
-        {   // exclusive scan of the chunk's histogram (F <= 512: one slice per thread); the slice's run starts at slot cur[f] of its segment
-            const uint32_t f = threadIdx.x;
-            const uint32_t h = f < F ? hist[f] : 0u;
-            uint32_t incl = h;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            if (lane == 63) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t before = incl - h;
-            for (uint32_t wv = 0; wv < wave; ++wv) before += wsum[wv];
-            if (f < F) {
-                off[f] = before;
-                const uint32_t at = cur[f];
-                cur[f] = at + h;
-                hist[f] = at - before;                  // slot = sorted position + this (mod 2^32)
-            }
-            if (threadIdx.x == BIN_B_THREADS - 1) chunk_items = before + h;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r)
-#pragma unroll
-            for (uint32_t e = 0; e < 4; ++e)
-                if (e < have[r]) bimg[off[slice_of(it[r][e])] + rank[r][e]] = it[r][e];
-        __syncthreads();
-        const uint32_t n = chunk_items;
-        for (uint32_t q = threadIdx.x; q < n; q += BIN_B_THREADS) {
-            const uint32_t item = bimg[q], f = slice_of(item), slot = q + hist[f];
-            if (slot < (uint32_t)g.cap2) out[(uint64_t)f * fstride + slot] = fine_of(item);
-            else spill_item(g, (int)t, (((uint64_t)c * F + f) << SB) | (item & OFFMASK), (item >> BIN_W_SHIFT) + 1u);
-        }
-        __syncthreads();
-        for (uint32_t f = threadIdx.x; f < F; f += BIN_B_THREADS) hist[f] = 0;
-        __syncthreads();
-    }
-    for (uint32_t f = threadIdx.x; f < F; f += BIN_B_THREADS)
-        g.gcnt2[((uint64_t)s * F + f) * g.nwgB + blockIdx.x] = min(cur[f], (uint32_t)g.cap2);
 }
 
 // ---- stage C -----------------------------------------------------------------------------
@@ -883,15 +655,15 @@ __device__ __forceinline__ uint32_t lds_addw4(uint32_t *lds, const uint32_t (&w)
 // short.  Table sizes and pointers come by value; the segment counts, the overflow flag and -- unless the tables are
 // zero by decree -- the slice itself are requested together; every thread then requests ALL its item vectors at once
 // (up to MAXV; slices with more fall back to the pipelined loop for the rest) before it applies the first.
-template <int STORAGE, bool W, int SBITS>
-__global__ __launch_bounds__(SBITS == BIN_SLICE_BITS_W ? BIN_CW_THREADS : BIN_C_THREADS) void k_bin_apply(const SketchDev *__restrict__ sk, BinGeom g)
+template <int STORAGE, bool W>
+__global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__restrict__ sk, BinGeom g)
 {
     typedef typename std::conditional<W, uint32_t, uint16_t>::type Item;
     constexpr uint32_t VEC = 16u / sizeof(Item);                  // items per 16-byte vector
-    constexpr uint32_t SB = SBITS, SLICE = 1u << SB;
-    constexpr uint32_t THREADS = SBITS == BIN_SLICE_BITS_W ? BIN_CW_THREADS : BIN_C_THREADS;
+    constexpr uint32_t SB = BIN_SLICE_BITS, SLICE = 1u << SB;
+    constexpr uint32_t THREADS = BIN_C_THREADS;
     constexpr int MAXV = W ? 4 : 3;
-    __shared__ __attribute__((aligned(16))) uint32_t lds[SLICE / 4];   // one slice: 65536 (32768 weighted) counters of <= 8 bits
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SLICE / 4];   // one slice: 65536 counters of <= 8 bits
     const int t = blockIdx.y;
     const uint32_t slice = blockIdx.x;
     if (slice >= g.nslices[t]) return;
@@ -1142,12 +914,9 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) { g.tsize[t] = s->h.size[t]; g.ttab[t] = s->h.tab[t]; }
     g.tile_lds = lds_front;
     g.dbg = kv_knob("KV_BIN_DEBUG") ? (uint32_t)atoi(kv_knob("KV_BIN_DEBUG")) : 0u;
-    uint64_t pmin = UINT64_MAX, pmax = 0;
-    for (int t = 0; t < g.T; ++t) { pmin = std::min(pmin, s->h.size[t]); pmax = std::max(pmax, s->h.size[t]); }
-    // 32768-bin slices for weighted items (KV_BIN_SLICE15=1) were measured at config 2: stage C 2.20 instead of 2.25 ms,
-    // stage B 1.26-1.36 instead of 1.0 ms -- stage C is not held back by the overlap of its phases; the default stays 65536
-    g.sbits = weighted && kv_knob("KV_BIN_SLICE15") && atoi(kv_knob("KV_BIN_SLICE15")) && ((pmax + 32767) >> 15) <= 64ull * 384ull
-                  ? BIN_SLICE_BITS_W : BIN_SLICE_BITS;
+    uint64_t pmin = UINT64_MAX;
+    for (int t = 0; t < g.T; ++t) pmin = std::min(pmin, s->h.size[t]);
+    g.sbits = BIN_SLICE_BITS;
     uint32_t maxsl = 1;
     for (int t = 0; t < g.T; ++t) {
         g.nslices[t] = (uint32_t)((s->h.size[t] + (1ull << g.sbits) - 1) >> g.sbits);
@@ -1159,22 +928,14 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     // beyond 2^30 bins.  Fewer buckets = fewer distinct lines per stage-A store instruction (that stage is bound by
     // L2 write requests): measured per 525 M k-mers into 5e8-bin tables, A/B/C = 10.5/5.0/4.0 ms with 32 buckets,
     // 8.7/4.9/4.0 with 20, 8.3/6.1/4.0 with 16 (F = 478: rings too big for three workgroups).
-    // (weighted items: up to 64 buckets with the 512-thread front end -- its cursors are sized by T * C -- and F <= 1024)
-    int cmax = weighted && g.sbits == BIN_SLICE_BITS_W ? (int)std::min<uint32_t>(BIN_C, std::max<uint32_t>(4u, (maxsl + 383u) / 384u))
-                              : (maxsl <= 32u * BIN_MAX_F ? (int)std::min<uint32_t>(32u, std::max<uint32_t>(4u, (maxsl + 383u) / 384u)) : BIN_C);
+    int cmax = maxsl <= 32u * BIN_MAX_F ? (int)std::min<uint32_t>(32u, std::max<uint32_t>(4u, (maxsl + 383u) / 384u)) : BIN_C;
     if (const char *e = kv_knob("KV_BIN_C")) cmax = std::max(1, std::min<int>(BIN_C, atoi(e)));      // experiments: coarse buckets per table
     plan->cmax = cmax;
     g.F = (int)((maxsl + (uint32_t)cmax - 1) / (uint32_t)cmax);
     g.C = (int)((maxsl + (uint32_t)g.F - 1) / (uint32_t)g.F);
     g.recipF = g.F == 1 ? 0u : (uint32_t)((1ull << 32) / (uint64_t)g.F + 1);   // F == 1: kernels take slice as is
-    auto ring_for = [&](uint32_t streams, uint32_t budget) {
-        uint32_t r = weighted && budget == BIN_B_BUDGET ? 32u : BIN_RING_MIN;
-        while (r * 2 <= BIN_RING_MAX && (uint64_t)r * 2 * streams <= budget) r *= 2;
-        return r;
-    };
-    const uint32_t budgetA = cmax <= 32 ? 8192u : 16384u;
-    g.ringA = ring_for((uint32_t)(g.T * g.C), budgetA);
-    g.ringB = ring_for((uint32_t)g.F, BIN_B_BUDGET);       // budget in entries: u32 rings get half the entries per byte
+    g.ringB = weighted ? 32u : BIN_RING_MIN;                // budget in entries: u32 rings get half the entries per byte
+    while (g.ringB * 2 <= BIN_RING_MAX && (uint64_t)g.ringB * 2 * g.F <= BIN_B_BUDGET) g.ringB *= 2;
     if (weighted) while (g.ringB > 32u && (uint64_t)g.ringB * g.F * 4 > 2u * BIN_B_BUDGET) g.ringB /= 2;
     const int cus = kv_device_cus();
     const double expected = (double)(nbands > 0 && !use_mask ? n_items_max / (uint64_t)nbands + 1 : n_items_max);
@@ -1238,39 +999,28 @@ int kv_bin_finish(kv_sketch *s, BinPlan &plan, bool added_from_ctr, uint64_t n_a
         KvProfScope prof(plan.weighted ? "k_bin_split_w" : "k_bin_split");
         const size_t isz = plan.weighted ? 4 : 2;
         const size_t lds = (((size_t)g.F * g.ringB * isz + 15) & ~(size_t)15) + (size_t)g.F * 2 * 4;
-        if (plan.weighted && g.sbits == BIN_SLICE_BITS_W) {
-            ensure_dynamic_lds((k_bin_split<true, BIN_SLICE_BITS_W>), lds);
-            hipLaunchKernelGGL((k_bin_split<true, BIN_SLICE_BITS_W>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
-        } else if (plan.weighted && (g.nwgA + g.nwgB - 1) / g.nwgB <= BIN_BS_MAXSEG && (uint32_t)g.F <= BIN_B_THREADS &&
-                   kv_knob("KV_BIN_SPLIT") && !strcmp(kv_knob("KV_BIN_SPLIT"), "sorted")) {
-            // weighted items, 65536-bin slices, ranked and laid out in LDS, copied out in runs: only by name (KV_BIN_SPLIT=sorted) -- it gives
-            // the same segments and measured SLOWER than the ring kernel, 3.98 against 3.24 ms per step of config 2 (profiles/README.md)
-            const size_t lds2 = (size_t)BIN_BS_CHUNK * 4;
-            ensure_dynamic_lds((k_bin_split_sorted<BIN_SLICE_BITS>), lds2);
-            hipLaunchKernelGGL((k_bin_split_sorted<BIN_SLICE_BITS>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds2, st, g);
-        } else if (plan.weighted) {
-            ensure_dynamic_lds((k_bin_split<true, BIN_SLICE_BITS>), lds);
-            hipLaunchKernelGGL((k_bin_split<true, BIN_SLICE_BITS>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
+        if (plan.weighted) {
+            ensure_dynamic_lds((k_bin_split<true>), lds);
+            hipLaunchKernelGGL((k_bin_split<true>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
         } else {
-            ensure_dynamic_lds((k_bin_split<false, BIN_SLICE_BITS>), lds);
-            hipLaunchKernelGGL((k_bin_split<false, BIN_SLICE_BITS>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
+            ensure_dynamic_lds((k_bin_split<false>), lds);
+            hipLaunchKernelGGL((k_bin_split<false>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
         }
     }
     {
         KvProfScope prof(plan.weighted ? "k_bin_apply_w" : "k_bin_apply");
         const dim3 gridC(plan.maxsl, (unsigned)g.T);
         const SketchDev *d = (const SketchDev *)s->d_desc;
-#define KV_LAUNCH_APPLY(ST_, W_, SB_) \
-        hipLaunchKernelGGL((k_bin_apply<ST_, W_, SB_>), gridC, dim3(SB_ == BIN_SLICE_BITS_W ? BIN_CW_THREADS : BIN_C_THREADS), 0, st, d, g)
-#define KV_LAUNCH_APPLY_ST(W_, SB_)                                               \
-        do {                                                                       \
-            if (s->h.storage == ST_BYTE) KV_LAUNCH_APPLY(ST_BYTE, W_, SB_);        \
-            else if (s->h.storage == ST_NIBBLE) KV_LAUNCH_APPLY(ST_NIBBLE, W_, SB_); \
-            else KV_LAUNCH_APPLY(ST_BIT, W_, SB_);                                 \
+#define KV_LAUNCH_APPLY(ST_, W_) \
+        hipLaunchKernelGGL((k_bin_apply<ST_, W_>), gridC, dim3(BIN_C_THREADS), 0, st, d, g)
+#define KV_LAUNCH_APPLY_ST(W_)                                               \
+        do {                                                                  \
+            if (s->h.storage == ST_BYTE) KV_LAUNCH_APPLY(ST_BYTE, W_);        \
+            else if (s->h.storage == ST_NIBBLE) KV_LAUNCH_APPLY(ST_NIBBLE, W_); \
+            else KV_LAUNCH_APPLY(ST_BIT, W_);                                 \
         } while (0)
-        if (plan.weighted && g.sbits == BIN_SLICE_BITS_W) KV_LAUNCH_APPLY_ST(true, BIN_SLICE_BITS_W);
-        else if (plan.weighted) KV_LAUNCH_APPLY_ST(true, BIN_SLICE_BITS);
-        else KV_LAUNCH_APPLY_ST(false, BIN_SLICE_BITS);
+        if (plan.weighted) KV_LAUNCH_APPLY_ST(true);
+        else KV_LAUNCH_APPLY_ST(false);
 #undef KV_LAUNCH_APPLY_ST
 #undef KV_LAUNCH_APPLY
     }
@@ -1324,7 +1074,6 @@ int kv_consume_binned(kv_sketch *s, const kv_reads *reads, const uint64_t *d_lis
     }
     BinGeom &g = plan.g;
     const int cmax = plan.cmax;
-    const uint64_t ns = (uint64_t)g.T * g.C;
     const SketchDev *d_mask = mask ? mask->d_desc : nullptr;
     if (two_bit) {
         KvProfScope prof("k_bin_hash_2bit");
@@ -1338,45 +1087,26 @@ int kv_consume_binned(kv_sketch *s, const kv_reads *reads, const uint64_t *d_lis
         else if (!kw2) hipLaunchKernelGGL((k_bin_hash_2bit<1024, 1>), dim3(g.nwgA), dim3(1024), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
         else hipLaunchKernelGGL((k_bin_hash_2bit<1024, 2>), dim3(g.nwgA), dim3(1024), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
     } else if (reads) {
-        // default: direct stores through LDS cursors (k_bin_hash_direct); KV_BIN_DIRECT=0 selects the LDS-ring
-        // variant, which measured ~10% slower on this stage (profiles/README.md)
-        const bool direct = !(kv_knob("KV_BIN_DIRECT") && atoi(kv_knob("KV_BIN_DIRECT")) == 0);
-        KvProfScope prof(direct ? "k_bin_hash_direct" : "k_bin_hash");
-        const size_t lds = (size_t)g.tile_lds + ns * g.ringA * 4 + ns * 8;
+        KvProfScope prof("k_bin_hash_direct");
         const unsigned grid = g.nwgA;
         const int k = s->h.ksize;
         const int nw = (s->h.hashfam == HF_MURMUR && !kv_knob("KV_NO_ROLL")) ? (k <= 32 ? 8 : (k <= 64 ? 16 : 0)) : 0;
-#define KV_LAUNCH_BIN_HASH(THREADS_, NW_)                                                                         \
-        do {                                                                                                      \
-            ensure_dynamic_lds(k_bin_hash<THREADS_, NW_>, lds);                                                   \
-            hipLaunchKernelGGL((k_bin_hash<THREADS_, NW_>), dim3(grid), dim3(THREADS_), lds, st, reads_dev(reads), \
-                               reads->n_tiles, (const SketchDev *)s->d_desc, d_mask, filter, g);                  \
-        } while (0)
 #define KV_LAUNCH_BIN_DIRECT(THREADS_, NW_)                                                                       \
         do {                                                                                                      \
             ensure_dynamic_lds(k_bin_hash_direct<THREADS_, NW_>, (size_t)g.tile_lds);                             \
             hipLaunchKernelGGL((k_bin_hash_direct<THREADS_, NW_>), dim3(grid), dim3(THREADS_), g.tile_lds, st,    \
                                reads_dev(reads), reads->n_tiles, (const SketchDev *)s->d_desc, d_mask, filter, g); \
         } while (0)
-        if (direct && cmax <= 32) {
+        if (cmax <= 32) {
             if (nw == 8) KV_LAUNCH_BIN_DIRECT(512, 8);
             else if (nw == 16) KV_LAUNCH_BIN_DIRECT(512, 16);
             else KV_LAUNCH_BIN_DIRECT(512, 0);
-        } else if (direct) {
+        } else {
             if (nw == 8) KV_LAUNCH_BIN_DIRECT(1024, 8);
             else if (nw == 16) KV_LAUNCH_BIN_DIRECT(1024, 16);
             else KV_LAUNCH_BIN_DIRECT(1024, 0);
-        } else if (cmax <= 32) {
-            if (nw == 8) KV_LAUNCH_BIN_HASH(512, 8);
-            else if (nw == 16) KV_LAUNCH_BIN_HASH(512, 16);
-            else KV_LAUNCH_BIN_HASH(512, 0);
-        } else {
-            if (nw == 8) KV_LAUNCH_BIN_HASH(1024, 8);
-            else if (nw == 16) KV_LAUNCH_BIN_HASH(1024, 16);
-            else KV_LAUNCH_BIN_HASH(1024, 0);
         }
 #undef KV_LAUNCH_BIN_DIRECT
-#undef KV_LAUNCH_BIN_HASH
     } else {
         KvProfScope prof(weighted_list ? "k_bin_list_w" : "k_bin_list");
         const SketchDev *d = (const SketchDev *)s->d_desc;

@@ -1212,10 +1212,7 @@ const KvKnobDef g_knobs[] = {
     {"KV_LAZY_CLEAR", T_, "0: kv_sketch_clear zeroes the tables at once instead of leaving it to the apply stage"},
     {"KV_NO_ROLL", T_, "hash every k-mer from scratch (no rolling 2-bit window)"},
     {"KV_BIN_2BIT", T_, "0: stage A never hashes from the 2-bit form"},
-    {"KV_BIN_DIRECT", T_, "0: stage A writes items through LDS rings instead of direct stores"},
     {"KV_BIN_FAST4", T_, "0: no FP64-quotient remainders for four tables"},
-    {"KV_BIN_SPLIT", T_, "sorted: stage B sorts a chunk in LDS before it stores"},
-    {"KV_BIN_SLICE15", T_, "1: 32 K-bin slices for weighted items"},
     {"KV_BIN_C", T_, "coarse buckets per table"},
     {"KV_SKM_S1", T_, "tile | wave | lane: pin the record cutter"},
     {"KV_SKM_S2", T_, "plain | sorted: pin the fine split"},
@@ -1225,11 +1222,7 @@ const KvKnobDef g_knobs[] = {
     {"KV_SKM_LANE_MAXWG", T_, "2 | 3: workgroups per CU the lane cutter asks for"},
     {"KV_SKM_LANE_FLUSH", T_, "blocks between two flushes of the lane cutter's run list"},
     {"KV_SKM_SEG1", T_, "bucket: S1 segments laid out bucket-major"},
-    {"KV_SKM_ORIENT", T_, "0: records keep the read's strand (no oriented keys)"},
     {"KV_SKM_COMPACT", T_, "0: never the 16-byte records without positions"},
-    {"KV_SKM_DEDUP", T_, "1: identical records merged before the k-mer table (k = 31)"},
-    {"KV_SKM_DEDUP_MAXN", T_, "longest record the record table takes"},
-    {"KV_SKM_DEDUP_RS", T_, "record-table slots (1024: two workgroups per CU)"},
     {"KV_SKM_ANY_K", T_, "use the kernels with k at run time, not the k = 31 / 51 instances"},
     {"KV_SKM_BUCKET_KMERS", T_, "k-mer occurrences aimed at per bucket (tests: many buckets on small inputs)"},
     {"KV_SKM_CAP_PCT", T_, "segment capacity in per cent of the estimate (tests: push records through the loose list)"},

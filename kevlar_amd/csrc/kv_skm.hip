@@ -62,12 +62,10 @@ struct SkmGeom {
     // that is not going to be scanned from this batch.  Loose records keep the classic form: lrecw = 1 + nbw words each.
     uint32_t compact;
     int lrecw;
-    // oriented: a record whose minimizer stands reversed in the read (strand bit of its value, skm_order_s) holds the REVERSE COMPLEMENT
-    // of the read's bases (header flag), so every k-mer of every record is stored on the strand on which its minimizer is canonical --
-    // and that strand is the k-mer's key in the bucket tables: the walk takes k-mers as they stand, no second strand, no comparison.
-    // The exchange layouts keep classic records (canonical = the smaller strand, computed by the walk).
-    uint32_t oriented;
-    uint32_t dd_maxn;                // k_skm_count combines identical records first (records of up to dd_maxn k-mers; 0: it does not)
+    // (records are oriented: a record whose minimizer stands reversed in the read (strand bit of its value, skm_order_s) holds the
+    // REVERSE COMPLEMENT of the read's bases (header flag), so every k-mer of every record is stored on the strand on which its minimizer
+    // is canonical -- and that strand is the k-mer's key in the bucket tables: the walk takes k-mers as they stand, no second strand, no
+    // comparison.  The exchange layouts cut them the same way.)
     uint32_t passes;                 // k_skm_route takes a bucket's k-mers in at least this many passes (0 / 1: one) -- buckets bigger than its LDS table
     uint32_t bpt;                    // buckets per ticket of the bucket kernels' work counter (a power of two)
 };
@@ -405,7 +403,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
                 uint64_t bw[3];
 #pragma unroll
                 for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? skm_bases32(wl, b + 32u * t) : 0ull;
-                const uint32_t rev = sg.oriented ? (minv & 1u) : 0u;
+                const uint32_t rev = minv & 1u;
                 if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
                 const uint64_t hdr = skm_header(pos, n, fine, rev);
                 const uint32_t p = atomicAdd(&cur[coarse], 1u);
@@ -587,7 +585,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
                     uint64_t bw[3];
 #pragma unroll
                     for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? skm_bases32(wl, b + 32u * t) : 0ull;
-                    const uint32_t rev = sg.oriented ? (sval[i] & 1u) : 0u;
+                    const uint32_t rev = sval[i] & 1u;
                     if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
                     const uint64_t hdr = skm_header(pos, n, fine, rev);
                     const uint32_t p = atomicAdd(&cur[coarse], 1u);
@@ -754,7 +752,7 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
         bool pf_waited = !more;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (sg.oriented) {
+        {
             // every lane reverses and complements its own read once: the 16 wpr base slots of its words turned round (word order and
             // the bases inside each word), complemented, and the 16 wpr - L slots of padding that came to the front shifted out.  A
             // reversed run's bases are then read from this image exactly as a forward run's are read from the words.
@@ -773,7 +771,7 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
             uint32_t coarse, fine;
             skm_bucket_of(v, sg.C1, sg.fbits, coarse, fine);
             uint64_t pos = (sg.read_base + r0 + r) * sg.stride + j;
-            const uint32_t rev = sg.oriented ? (v & 1u) : 0u;
+            const uint32_t rev = v & 1u;
             const uint32_t *src = rev ? rcl : wl;
             uint32_t bidx = r * wpr * 16u + j;                        // the piece's first base in the read (in wl)
             while (left) {
@@ -1237,10 +1235,10 @@ __device__ __forceinline__ void skm_walk_loose(const SkmGeom &sg, bool alone, co
     }
 }
 
-// body(canonical k-mer, forward k-mer, position of the occurrence) -> true if the occurrence could not be combined and
-// must travel alone through the loose list; WANT_POS = false skips fetching the header (count pass)
-// ORI: the bucket's records are oriented (SkmGeom::oriented): a k-mer's key is the k-mer as the record holds it
-template <int KW, bool WANT_POS, int FK = 0, bool COMPACT = false, bool ORI = false, typename Body>
+// body(k-mer, position of the occurrence) -> true if the occurrence could not be combined and must travel alone through the
+// loose list; WANT_POS = false skips fetching the header (count pass).  The records are oriented: a k-mer's key is the k-mer as
+// the record holds it.
+template <int KW, bool WANT_POS, int FK = 0, bool COMPACT = false, typename Body>
 __device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, uint32_t *sbits_all, Body body)
 {
     static_assert(!COMPACT || (KW == 1 && !WANT_POS), "compact records: one-word keys, no positions");
@@ -1309,8 +1307,6 @@ __device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, u
             const uint32_t j0 = t < total ? (t - (oe & 0xffffu)) * G : 0u;
             const uint32_t cnt = t < total ? min(G, (oe >> 16) - j0) : 0u;     // k-mers of this unit: 1..G (0: no unit)
             SkmKey<KW> fw = skm_kmer_of<KW>(o0, o1, o2, j0, k);
-            SkmKey<KW> rc = fw;
-            if (!ORI) rc = skm_revcomp<KW>(fw, k);
             const uint32_t tail = (uint32_t)skm_window64(o0, o1, o2, j0 + (uint32_t)k);   // the bases that enter k-mers 1 .. G - 1
             // read position of the unit's first k-mer and the step to the next: a reversed record's k-mer j stands at pos + n - 1 - j
             uint64_t pos0 = 0;
@@ -1322,13 +1318,10 @@ __device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, u
             }
 #pragma unroll
             for (uint32_t u = 0; u < G; ++u) {
-                if (u) {
-                    if (ORI) { SkmKey<KW> other = fw; skm_roll<KW>(fw, other, (tail >> (2u * (u - 1u))) & 3u, k); }      // (the other strand is dead code here)
-                    else skm_roll<KW>(fw, rc, (tail >> (2u * (u - 1u))) & 3u, k);
-                }
+                if (u) { SkmKey<KW> other = fw; skm_roll<KW>(fw, other, (tail >> (2u * (u - 1u))) & 3u, k); }      // (the other strand is dead code here)
                 const uint64_t posu = pos0 + (uint64_t)(int64_t)(step * (int)u);
                 bool alone = false;
-                if (u < cnt) alone = body(ORI ? fw : skm_canonical<KW>(fw, rc), fw, posu);
+                if (u < cnt) alone = body(fw, posu);
                 skm_walk_loose<KW, WANT_POS>(sg, alone, fw, hdr, owner, posu, j0, u, lane, sg.lrecw);
             }
         }
@@ -1340,167 +1333,6 @@ __device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, u
             const uint64_t *rec = sg.seg2 + (((uint64_t)b * sg.nwg2 + sgm) * sg.cap2 + g * 64u + lane) * (uint64_t)recw;
             load(rec, hdr, b0, b1, b2);
         }
-    }
-}
-
-// ---- identical records first (the k = 31 instances of the count) ------------------------------------------------------
-// (KV_SKM_DEDUP=1 only -- an experiment that did not pay, kept for the next attempt: see the end of this comment.)
-// Reads that cover the same stretch of the genome cut the same super-k-mers out of it: at 30 x, 61 % of a bucket's records repeat
-// another record of the bucket base for base (measured on the synthetic trio; the rest were cut short by a read's end or hold an
-// error), and they hold 60 % of the k-mer occurrences.  So the count first puts the bucket's RECORDS into a small LDS table (key = the
-// bases the record's k-mers use + their number; value = how many records said the same), and only then walks every distinct record
-// once, adding its weight to each of its k-mers: 2.5 x fewer cut-outs and table inserts for one insert per record.
-// Anything irregular -- no room in the record table, a record longer than dd_maxn k-mers, a k-mer that finds the k-mer table full --
-// only raises a flag: the workgroup then empties its tables and walks the bucket the plain way (skm_walk_bucket), whose loose
-// records carry the positions of the occurrences themselves.  (Saturating adds compose in any grouping: weights are exact.)
-// Measured (config 2, one stream, ms per step for the three samples): k_skm_count 9.25 without, 10.2 with 512 record slots + 3072 k-mer
-// slots (114 k buckets instead of 64 k: S2 2.24 -> 2.65 as well), 10.15 with 1024 + 4096 slots at two workgroups per CU (64 k buckets).
-// The walk and the inserts it saves (1.5 of 3.1 ms per sample, 60 % of them) are outweighed by what it adds per bucket: a phase that
-// only waits for the records and three dependent LDS atomics, a second barrier, and a walk whose groups of 64 slots hold ~22 records.
-#define SKM_REC_MAXPROBE 16
-template <int RS>
-struct SkmRecTable {
-    unsigned long long k0[RS], k1[RS];
-    uint32_t w[RS];
-};
-
-template <int RS>
-__device__ __forceinline__ void skm_rec_table_clear(SkmRecTable<RS> &rt)
-{
-    for (uint32_t i = threadIdx.x; i < RS; i += blockDim.x) { rt.k0[i] = SKM_EMPTY; rt.k1[i] = SKM_EMPTY; rt.w[i] = 0u; }
-}
-
-// every record of bucket b into the table; true if one of this thread's records could not be put there
-template <int RS, bool COMPACT>
-__device__ __forceinline__ bool skm_rec_combine(const SkmGeom &sg, uint32_t b, SkmRecTable<RS> &rt, int k)
-{
-    static_assert((RS & (RS - 1)) == 0, "record table: 2^n slots");
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    constexpr uint32_t recw = COMPACT ? 2u : 3u;
-    const uint32_t *cnt2 = sg.cnt2 + (uint64_t)b * sg.nwg2;
-    bool failed = false;
-    uint32_t p = wave;
-    uint32_t g = p / sg.nwg2, sgm = p - g * sg.nwg2;
-    uint64_t b0 = 0, w1 = 0;
-    auto load = [&](const uint64_t *rec) {
-        if (COMPACT) {
-            typedef uint64_t u64x2a __attribute__((ext_vector_type(2), aligned(16)));
-            const u64x2a both = *(const u64x2a *)rec;
-            b0 = both.x; w1 = skm_c_b1(both.y) | ((uint64_t)skm_c_n(both.y) << 40);
-        } else {
-            const uint32_t n = skm_hdr_n(rec[0]);
-            b0 = rec[1];
-            // (more than 20 bases in the second word: not a record this table takes -- the number of k-mers says so below)
-            w1 = (rec[2] & ((1ull << 40) - 1ull)) | ((uint64_t)n << 40);
-        }
-    };
-    {   // (as in skm_walk_bucket: the first records are requested together with the segment counts)
-        const uint32_t at = min(g * 64u + lane, sg.cap2 - 1u);
-        load(sg.seg2 + (((uint64_t)b * sg.nwg2 + sgm) * sg.cap2 + at) * (uint64_t)recw);
-    }
-    uint32_t maxc = 0;
-    for (uint32_t s2 = 0; s2 < sg.nwg2; ++s2) maxc = max(maxc, cnt2[s2]);
-    for (;;) {
-        if (g * 64u >= maxc) break;
-        if (g * 64u + lane < cnt2[sgm]) {
-            const uint32_t n = (uint32_t)(w1 >> 40), nb = n + (uint32_t)k - 1u;          // the bases its k-mers use: k .. 52
-            if (n == 0u || n > sg.dd_maxn || nb > SKM_C_BASES) {
-                failed = true;
-            } else {
-                // bases behind the last k-mer are whatever followed in the read: not part of the key
-                const uint64_t key0 = nb >= 32u ? b0 : b0 & ((1ull << (2u * nb)) - 1ull);
-                const uint64_t key1 = (nb > 32u ? w1 & ((1ull << (2u * (nb - 32u))) - 1ull) : 0ull) | ((uint64_t)n << 40);
-                uint32_t y = (uint32_t)key0 * 0x9e3779b1u ^ (uint32_t)(key0 >> 32) * 0x85ebca6bu ^ (uint32_t)key1 * 0xc2b2ae35u ^ (uint32_t)(key1 >> 32) * 0x27d4eb2fu;
-                y ^= y >> 15;
-                y *= 0x2c1b3c6du;
-                uint32_t slot = y >> (32 - __builtin_ctz(RS));
-                const uint32_t step = ((y >> 3) & 30u) | 1u;
-                bool placed = false;
-                if (key0 != SKM_EMPTY) {
-                    for (int probe = 0; probe < SKM_REC_MAXPROBE; ++probe) {
-                        const unsigned long long old0 = atomicCAS(&rt.k0[slot], SKM_EMPTY, (unsigned long long)key0);
-                        if (old0 == SKM_EMPTY || old0 == key0) {
-                            const unsigned long long old1 = atomicCAS(&rt.k1[slot], SKM_EMPTY, (unsigned long long)key1);
-                            if (old1 == SKM_EMPTY || old1 == key1) { atomicAdd(&rt.w[slot], 1u); placed = true; break; }
-                        }
-                        slot = (slot + step) & (uint32_t)(RS - 1);
-                    }
-                }
-                failed = failed || !placed;
-            }
-        }
-        p += nwaves;
-        g = p / sg.nwg2; sgm = p - g * sg.nwg2;
-        if (g * 64u >= maxc) break;
-        if (g * 64u + lane < cnt2[sgm])
-            load(sg.seg2 + (((uint64_t)b * sg.nwg2 + sgm) * sg.cap2 + g * 64u + lane) * (uint64_t)recw);
-    }
-    return failed;
-}
-
-// every distinct record of the table once (the table is emptied on the way): body(k-mer as the record holds it, weight) for each of
-// its k-mers, dealt to the lanes in units of SKM_UNIT k-mers like skm_walk_bucket deals them
-template <int RS, typename Body>
-__device__ __forceinline__ void skm_rec_walk(const SkmGeom &sg, SkmRecTable<RS> &rt, uint32_t *sbits_all, int k, Body body)
-{
-    constexpr uint32_t G = SKM_UNIT;
-    __shared__ uint8_t lane_of_all[SKM_THREADS3];       // the wave's occupied slots in order: the r-th of them sits in lane lane_of[r]
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    uint32_t *sbits = sbits_all + wave * sg.sbw;
-    uint8_t *lane_of = lane_of_all + wave * 64u;
-    for (uint32_t s0 = wave * 64u; s0 < (uint32_t)RS; s0 += nwaves * 64u) {
-        const uint32_t s = s0 + lane;
-        const uint64_t b0 = rt.k0[s];
-        uint64_t b1 = 0;
-        uint32_t nk = 0, wgt = 0;
-        if (b0 != SKM_EMPTY) {
-            const uint64_t w1 = rt.k1[s];
-            wgt = rt.w[s];
-            rt.k0[s] = SKM_EMPTY; rt.k1[s] = SKM_EMPTY; rt.w[s] = 0u;
-            nk = (uint32_t)(w1 >> 40);
-            b1 = w1 & ((1ull << 40) - 1ull);
-        }
-        const unsigned long long occ = __ballot(nk != 0u);
-        if (!occ) continue;
-        if (nk) lane_of[__popcll(occ & ((1ull << lane) - 1ull))] = (uint8_t)lane;      // (ordered with the reads below by the fences around the start bits)
-        const uint32_t nu = (nk + G - 1u) / G;
-        uint32_t incl = nu;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        const uint32_t total = __shfl(incl, 63), excl = incl - nu;
-        const uint32_t exnk = excl | (nk << 16);
-        const uint32_t nwords = (total >> 5) + 2u;
-        for (uint32_t wd = lane; wd < nwords; wd += 64) sbits[wd] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (nu) atomicOr(&sbits[excl >> 5], 1u << (excl & 31));
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t before = 0;
-        for (uint32_t t0 = 0; t0 < total; t0 += 64) {
-            const uint64_t starts = (uint64_t)__hip_atomic_load(&sbits[t0 >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) |
-                                    ((uint64_t)__hip_atomic_load(&sbits[(t0 >> 5) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) << 32);
-            const uint32_t t = t0 + lane;
-            // (the start bits number the records that have units: empty slots lie between them here, hence the look-up)
-            const uint32_t owner = lane_of[(before + (uint32_t)__popcll(starts & ((2ull << lane) - 1ull)) - 1u) & 63u];
-            before += (uint32_t)__popcll(starts);
-            const uint32_t oe = (uint32_t)__shfl((int)exnk, (int)owner);
-            const uint32_t ow = (uint32_t)__shfl((int)wgt, (int)owner);
-            const uint64_t o0 = skm_shfl64(b0, owner), o1 = skm_shfl64(b1, owner);
-            const uint32_t j0 = t < total ? (t - (oe & 0xffffu)) * G : 0u;
-            const uint32_t cnt = t < total ? min(G, (oe >> 16) - j0) : 0u;
-            SkmKey<1> fw = skm_kmer_of<1>(o0, o1, 0ull, j0, k);
-            const uint32_t tail = (uint32_t)skm_window64(o0, o1, 0ull, j0 + (uint32_t)k);
-#pragma unroll
-            for (uint32_t u = 0; u < G; ++u) {
-                if (u) { SkmKey<1> other = fw; skm_roll<1>(fw, other, (tail >> (2u * (u - 1u))) & 3u, k); }
-                if (u < cnt) body(fw, ow);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
     }
 }
 
@@ -1516,8 +1348,7 @@ __host__ __device__ inline uint32_t skm_wave_scratch_words(uint32_t sbw) { retur
 #if !defined(SKM_K2_WAVES)
 #define SKM_K2_WAVES 6
 #endif
-// RS: slots of the table of records (above) the instance combines identical records in before it walks them; 0: it walks them all
-// The instances for a fixed k (FK != 0, no record table) take the two murmurs from the product tables (skm_key_hash_pl: P1 / P2, 4 KB of
+// The instances for a fixed k (FK != 0) take the two murmurs from the product tables (skm_key_hash_pl: P1 / P2, 4 KB of
 // dynamic LDS in place of the 1 KB ASCII table) and keep their occurrence counters as 16-bit halves of a word -- that is where the
 // 3 KB come from with three workgroups on a CU; the host launches them only for buckets that cannot hold 65536 occurrences
 // (skm_count_pl_fits), the instances with k at run time count in 32 bits.  -DSKM_PL=0: A/B builds without either.
@@ -1537,16 +1368,14 @@ __host__ __device__ inline uint32_t skm_wave_scratch_words(uint32_t sbw) { retur
 // entries of one bucket the scan from the distinct list takes (k_skm_novel_list): a bucket's list has at most as many entries as the
 // count kernel's LDS table has slots
 #define SKM_LIST_MAX 4096u
-template <int KW, int TS, bool KNOBS, int FK, bool COMPACT = false, bool ORI = false, int RS = 0>
-__global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : (RS >= 1024 ? 4 : 6)) void k_skm_count(SkmGeom sg, const SketchDev *__restrict__ sk,
+template <int KW, int TS, bool KNOBS, int FK, bool COMPACT = false>
+__global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_skm_count(SkmGeom sg, const SketchDev *__restrict__ sk,
                                                            const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
 {
-    static_assert(RS == 0 || (KW == 1 && ORI && !KNOBS), "records are combined in the oriented one-word instances");
     static_assert((uint32_t)TS <= SKM_LIST_MAX, "a bucket's distinct list (one entry per occupied slot) must fit what k_skm_novel_list takes");
-    constexpr bool PL = SKM_PL && FK != 0 && RS == 0;
+    constexpr bool PL = SKM_PL && FK != 0;
     __shared__ SkmTable<KW, TS> tb;
     __shared__ uint32_t cnt[PL ? TS / 2 : TS];   // occurrences of the key in the same slot (PL: slot s in half s & 1 of word s >> 1)
-    __shared__ SkmRecTable<RS ? RS : 1> rt;
     __shared__ uint32_t next_bucket;
     __shared__ uint32_t abl_cur, abl_b0, abl_prev;      // abundance list: entries appended so far, ... when the bucket began, the bucket
     __shared__ uint32_t dl_cur, dl_b0;                  // distinct list: the same two
@@ -1559,7 +1388,6 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : (RS >= 1024 
         if (PL) { P1[threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C1); P2[threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C2); }
         else lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     }
-    const int k = FK ? FK : sg.k;
     const HashParams hp = FK ? make_hash_params(FK, f.hp.hashfam) : f.hp;
     uint64_t n_added = 0, n_distinct = 0;
     const uint32_t cap1 = (uint32_t)g.cap1;
@@ -1578,7 +1406,6 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : (RS >= 1024 
     // while the current bucket is processed
     skm_table_clear(tb);
     for (uint32_t i = threadIdx.x; i < (PL ? TS / 2 : TS); i += SKM_THREADS3) cnt[i] = 0;
-    if constexpr (RS != 0) skm_rec_table_clear(rt);
     if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[3], 1ull) * sg.bpt; abl_cur = 0; abl_b0 = 0; abl_prev = 0xffffffffu; dl_cur = 0; dl_b0 = 0; }
     // where the finished bucket's entries of the abundance list lie (nothing if the workgroup's stretch ran out)
     auto abl_close = [&]() {
@@ -1614,27 +1441,8 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : (RS >= 1024 
                 }
             }
         }
-        // combine the occurrences of the bucket: identical records first where the instance has the table for them
-        bool plain = true;
-        if constexpr (RS != 0) {
-            bool failed = skm_rec_combine<RS, COMPACT>(sg, b, rt, k);
-            __syncthreads();
-            skm_rec_walk<RS>(sg, rt, scratch, k, [&](const SkmKey<1> &c1, uint32_t wgt) {
-                SkmKey<KW> c;
-                c.w[0] = c1.w[0];
-                const int slot = skm_table_insert(tb, c);
-                if (slot >= 0) atomicAdd(&cnt[slot], wgt);
-                else failed = true;
-            });
-            plain = __syncthreads_or(failed ? 1 : 0) != 0;
-            if (plain) {                         // (a bucket in thousands: too many distinct records or k-mers for the tables) start over
-                skm_table_clear(tb);
-                for (uint32_t i = threadIdx.x; i < TS; i += SKM_THREADS3) cnt[i] = 0;
-                if (threadIdx.x == 0) atomicAdd(&sg.ctr[12], 1ull);
-                __syncthreads();
-            }
-        }
-        if (plain && !(SKM_DBG(sg) & 2u)) skm_walk_bucket<KW, false, FK, COMPACT, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t) {
+        // combine the occurrences of the bucket
+        if (!(SKM_DBG(sg) & 2u)) skm_walk_bucket<KW, false, FK, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
             if (SKM_DBG(sg) & 128u) { n_added += c.w[0] & 1; return false; }
             // (KV_SKM_FORCE_LOOSE: one key in 64 is treated like a key that found its table full -- every occurrence travels alone;
             // results stay exact, tests use it to put single k-mers on the loose list of a batch that otherwise fits)
@@ -1859,7 +1667,7 @@ __device__ __forceinline__ void skm_route_item(const KvRouteSink &rs, const uint
     else skm_route_overflow(SkmOverflowSink{rs.ctr, rs.ovf, rs.ovf_dest, rs.ovf_cap, rs.ndest}, d, h, count);
 }
 
-template <int KW, int TS, bool ORI = false, bool COMPACT = false>
+template <int KW, int TS, bool COMPACT = false>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashParams hp, KvRouteSink rs)
 {
     __shared__ SkmTable<KW, TS> tb;
@@ -1934,7 +1742,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashP
         const uint32_t passes = passes_of(b);
         for (uint32_t pass = 0; pass < passes; ++pass) {
         if (pass) __syncthreads();                       // (the drain of the pass before empties the table)
-        skm_walk_bucket<KW, false, 0, COMPACT, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t) {
+        skm_walk_bucket<KW, false, 0, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
             if (!skm_cacheable<KW>(c)) return pass == 0u;                                           // (travels alone, once)
             if (passes > 1u && __umulhi(skm_slot_hash<KW>(c) * 0x9E3779B1u, passes) != pass) return false;       // (bits the slot and the probe step do not come from)
             const int slot = skm_table_insert(tb, c);
@@ -2045,7 +1853,7 @@ __device__ __forceinline__ void skm_mark(const NovelParams &p, const ReadsDev &r
     atomicOr(&p.mask[bit >> 5], 1u << (bit & 31));
 }
 
-template <int KW, int TS, bool ORI = false>
+template <int KW, int TS>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
 {
     constexpr bool KNOBS = true;
@@ -2085,7 +1893,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
             any_hit = 0;
         }
         // collect the distinct k-mers
-        skm_walk_bucket<KW, true, 0, false, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t) {
+        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
             const int slot = skm_cacheable<KW>(c) ? skm_table_insert(tb, c) : -1;
             return slot < 0;
         });
@@ -2115,7 +1923,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
         __syncthreads();
         if (any_hit == 0 || (SKM_DBG(sg) & 8u)) continue;
         // mark every occurrence of an interesting k-mer (an occurrence whose key is absent went to the loose list)
-        skm_walk_bucket<KW, true, 0, false, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t pos) {
+        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
             if (!skm_cacheable<KW>(c)) return false;
             const int slot = skm_table_find(tb, c);
             if (slot >= 0 && ((flag[slot >> 5] >> (slot & 31)) & 1u)) skm_mark(p, rd, pos, sg.stride);
@@ -2153,7 +1961,7 @@ __global__ __launch_bounds__(256) void k_case_bits(const uint8_t *__restrict__ t
 // are any are the bucket's records walked, to mark their occurrences.  Occurrences that missed the count pass's LDS tables are in
 // the loose list already (k_skm_loose_novel evaluates them one by one).  A bucket's list has at most as many entries as the count
 // kernel's LDS table has slots.
-template <int KW, int TSM, bool KNOBS, bool ORI = false>
+template <int KW, int TSM, bool KNOBS>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
 {
 #if defined(SKM_LIST_E)
@@ -2172,7 +1980,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
     skm_table_clear(itb);
     if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt; n_int = 0; n_cand = 0; }
     auto mark_pass = [&](uint32_t b) {
-        skm_walk_bucket<KW, true, 0, false, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t pos) {
+        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
             if (skm_cacheable<KW>(c) && skm_table_find(itb, c) >= 0) skm_mark(p, rd, pos, sg.stride);
             return false;
         });
@@ -2356,7 +2164,7 @@ __device__ __forceinline__ void set_hit_store(const NovelParams &p, const SetHit
     for (int c = 0; c < S; ++c) out.abund[at * (uint64_t)S + c] = p.set_abund[slot * (uint64_t)S + c];
 }
 #define SKM_HIT_STAGE 1024u
-template <int KW, int TSM, bool ORI = false>
+template <int KW, int TSM>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, NovelParams p, SetHitSink out)
 {
     __shared__ SkmTable<KW, TSM> itb;            // the bucket's members of the set
@@ -2394,7 +2202,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, No
         }
         __syncthreads();
         if (n_int == 0) continue;
-        skm_walk_bucket<KW, true, 0, false, ORI>(sg, b, scratch, [&](const SkmKey<KW> &c, const SkmKey<KW> &, uint64_t pos) {
+        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
             if (!skm_cacheable<KW>(c)) return false;
             const int at = skm_table_find(itb, c);
             if (at < 0) return false;
@@ -2819,18 +2627,7 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
     g.dbg = kv_knob("KV_SKM_DEBUG") ? (uint32_t)atoi(kv_knob("KV_SKM_DEBUG")) : 0u;
     if (kv_knob("KV_SKM_FORCE_LOOSE")) g.dbg |= 4096u;
     g.bpt = skm_default_bpt();
-    // KV_SKM_DEDUP=1 (k = 31, oriented records): k_skm_count combines identical records before their k-mers (skm_rec_combine): a 3072-slot
-    // k-mer table beside a 512-slot table of records, or KV_SKM_DEDUP_RS=1024: 4096 beside 1024 at two workgroups per CU.  Off unless asked
-    // for: measured SLOWER (k_skm_count 9.25 -> 10.2 ms per step of config 2 either way, profiles/README.md round 5).
-    // KV_SKM_DEDUP_MAXN=n: records of more than n k-mers send their bucket down the plain walk (tests: n = 5 sends nearly every bucket there)
-    {
-        const char *eo = kv_knob("KV_SKM_ORIENT"), *ed = kv_knob("KV_SKM_DEDUP"), *em = kv_knob("KV_SKM_DEDUP_MAXN");
-        const bool dd = k == 31 && !(eo && atoi(eo) == 0) && (ed && atoi(ed) == 1) && !g.dbg && !kv_knob("KV_SKM_ANY_K");
-        g.dd_maxn = dd ? (uint32_t)(SKM_C_BASES + 1 - k) : 0u;
-        if (dd && em) g.dd_maxn = (uint32_t)std::max(0, std::min(atoi(em), SKM_C_BASES + 1 - k));
-    }
-    const bool dd_big = g.dd_maxn && kv_knob("KV_SKM_DEDUP_RS") && atoi(kv_knob("KV_SKM_DEDUP_RS")) >= 1024;      // (experiment: 1024 record slots beside 4096 k-mer slots, two workgroups per CU)
-    const uint32_t table_slots = g.kw == 1 ? (g.dd_maxn && !dd_big ? 3072u : 4096u) : 2048u;
+    const uint32_t table_slots = g.kw == 1 ? 4096u : 2048u;
     const char *tgt_env = kv_knob("KV_SKM_BUCKET_KMERS");      // tests shrink the buckets to exercise many of them on small inputs
     // k-mers per fine bucket: as many as leave the LDS table ~0.4 full (0.29 for two-word keys, whose longer windows put
     // fewer, bigger minimizer loci into a bucket: more variance) given the share of distinct k-mers the previous batch
@@ -2841,8 +2638,6 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
     // (two-word keys at 0.35: 2.2 M occurrences per 30x sample missed the tables and took the spill path, 67 ms per step of config 5; 0.29: 62 ms)
     uint64_t target = (uint64_t)((g.kw == 1 ? 0.4 : 0.29) * table_slots / frac);
     target = std::max<uint64_t>(table_slots / 2, std::min<uint64_t>(target, g.kw == 1 ? 2ull * table_slots : table_slots + table_slots / 2));
-    // (the table of records: ~4 % of a 30x bucket's occurrences are distinct records -- 195 of 512 slots at 4608 occurrences)
-    if (g.dd_maxn && !dd_big) target = std::min<uint64_t>(target, 4608);
     if (tgt_env) target = std::max<uint64_t>(64, strtoull(tgt_env, nullptr, 10));
     uint64_t nfine = std::max<uint64_t>(1, (n_kmers + target - 1) / target);
     {
@@ -2919,7 +2714,6 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
     g.seg1 = (uint64_t *)base; base += b_seg1;
     g.cnt1 = (uint32_t *)base; base += b_cnt1;
     { const char *e = kv_knob("KV_SKM_SEG1"); g.seg1_wmajor = (e && !strcmp(e, "bucket")) ? 0u : 1u; }
-    { const char *e = kv_knob("KV_SKM_ORIENT"); g.oriented = (e && atoi(e) == 0) ? 0u : 1u; }
     g.seg2 = (uint64_t *)base; base += b_seg2;
     g.cnt2 = (uint32_t *)base; base += b_cnt2;
     g.loose = (uint64_t *)base; base += b_loose;
@@ -3086,28 +2880,8 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
             pl = false;
             if (sg.k == 31 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31, true>; pl = true; }
         }
-        // (BASELINE.json configs[4]: k = 51 -- two-word keys, 128-bit reverse complement, three murmur blocks + a 3-byte tail)
+        // (BASELINE.json configs[4]: k = 51 -- two-word keys, three murmur blocks + a 3-byte tail)
         if (sg.k == 51 && sg.recw == 4 && fixed_k) { kernel = k_skm_count<2, SKM_TS51, false, 51>; pl = true; }
-        if (sg.oriented) {      // oriented records: the same instances with the walk that takes k-mers as they stand
-            kernel = sg.kw == 1 ? (sg.dbg ? k_skm_count<1, 4096, true, 0, false, true> : k_skm_count<1, 4096, false, 0, false, true>)
-                                : (sg.dbg ? k_skm_count<2, 2048, true, 0, false, true> : k_skm_count<2, 2048, false, 0, false, true>);
-            pl = false;
-            if (sg.k == 31 && sg.recw == 3 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31, false, true>; pl = true; }
-            if (sg.compact) {
-                kernel = sg.dbg ? k_skm_count<1, 4096, true, 0, true, true> : k_skm_count<1, 4096, false, 0, true, true>;
-                pl = false;
-                if (sg.k == 31 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31, true, true>; pl = true; }
-            }
-            if (sg.k == 51 && sg.recw == 4 && fixed_k) { kernel = k_skm_count<2, SKM_TS51, false, 51, false, true>; pl = true; }
-            // k = 31: identical records are combined before their k-mers are (skm_rec_combine; skm_build sized the buckets for it)
-            if (sg.dd_maxn && sg.k == 31 && (sg.compact || sg.recw == 3) && !sg.dbg) {
-                pl = false;
-                kernel = sg.compact ? k_skm_count<1, 3072, false, 31, true, true, 512> : k_skm_count<1, 3072, false, 31, false, true, 512>;
-                if (kv_knob("KV_SKM_DEDUP_RS") && atoi(kv_knob("KV_SKM_DEDUP_RS")) >= 1024)
-                    kernel = sg.compact ? k_skm_count<1, 4096, false, 31, true, true, 1024> : k_skm_count<1, 4096, false, 31, false, true, 1024>;
-            }
-        }
-        if (!sg.oriented) sg.dd_maxn = 0;
         const size_t lds = ((pl && SKM_PL ? 1024 : 256) + ((ns + 3u) & ~3u) + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
         hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
     }
@@ -3128,7 +2902,7 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         // what the batch looked like: if most k-mers are distinct (low coverage per batch) cutting and bucketing the
         // reads buys nothing, and if many occurrences missed the LDS tables the buckets were too full; either way
         // the next batches into this sketch take the one-item-per-k-mer partition (until the sketch is cleared)
-        unsigned long long sc[13] = {0};
+        unsigned long long sc[10] = {0};
         const bool got = hipMemcpy(sc, sg.ctr, sizeof(sc), hipMemcpyDeviceToHost) == hipSuccess;
         idx.dl_valid = dl_new && got && rc == KV_OK && sc[9] == 0;
         if (dl_new && kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] distinct list: %s (%llu workgroups ran out of %u entries)\n", idx.dl_valid ? "kept" : "dropped", sc[9], idx.dl_cap_wg);
@@ -3142,8 +2916,8 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
             s->skm_distinct = distinct;
             { std::lock_guard<std::mutex> glk(g_skm_mu); g_skm_last_distinct = distinct; }
             if (kv_knob("KV_SKM_VERBOSE"))
-                fprintf(stderr, "[kv_skm] batch of %llu k-mers: %.1f%% distinct, %.2f%% outside the LDS tables, %llu of %llu records (%d bytes each) outside their segments, %llu of %u buckets walked record by record%s\n",
-                        (unsigned long long)n_kmers, 100 * distinct, 100 * alone, sc[6], sc[5], 8 * sg.recw, sg.dd_maxn ? sc[12] : (unsigned long long)sg.n_buckets, sg.n_buckets,
+                fprintf(stderr, "[kv_skm] batch of %llu k-mers: %.1f%% distinct, %.2f%% outside the LDS tables, %llu of %llu records (%d bytes each) outside their segments%s\n",
+                        (unsigned long long)n_kmers, 100 * distinct, 100 * alone, sc[6], sc[5], 8 * sg.recw,
                         s->skm_off ? " -> next batches take the plain partition" : "");
         }
     }
@@ -3262,8 +3036,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
         sg.dl_keys = idx->dl_keys; sg.dl_hash = idx->dl_hash; sg.dl_bstart = idx->dl_bstart; sg.dl_bcount = idx->dl_bcount; sg.dl_cap_wg = idx->dl_cap_wg;
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
         void (*kernel)(SkmGeom, ReadsDev, NovelParams, SkmAblSet) =
-            sg.oriented ? (sg.kw == 1 ? (sg.dbg ? k_skm_novel_list<1, 2048, true, true> : k_skm_novel_list<1, 2048, false, true>) : (sg.dbg ? k_skm_novel_list<2, 1024, true, true> : k_skm_novel_list<2, 1024, false, true>))
-                        : (sg.kw == 1 ? (sg.dbg ? k_skm_novel_list<1, 2048, true> : k_skm_novel_list<1, 2048, false>) : (sg.dbg ? k_skm_novel_list<2, 1024, true> : k_skm_novel_list<2, 1024, false>));
+            sg.kw == 1 ? (sg.dbg ? k_skm_novel_list<1, 2048, true> : k_skm_novel_list<1, 2048, false>) : (sg.dbg ? k_skm_novel_list<2, 1024, true> : k_skm_novel_list<2, 1024, false>);
         hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, pl, abls);
         if (p.ab_keys) hipLaunchKernelGGL(k_ab_fill, dim3(2048), dim3(256), 0, st, p);
         if (p.ab_list && kv_knob("KV_SKM_VERBOSE")) {
@@ -3275,10 +3048,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     } else {
         KvProfScope prof("k_skm_novel");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
-        if (sg.oriented) {
-            if (sg.kw == 1) hipLaunchKernelGGL((k_skm_novel<1, 4096, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
-            else hipLaunchKernelGGL((k_skm_novel<2, 2048, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
-        } else if (sg.kw == 1) hipLaunchKernelGGL((k_skm_novel<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
+        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_novel<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
         else hipLaunchKernelGGL((k_skm_novel<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
     }
     {
@@ -3320,10 +3090,7 @@ int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, in
     {
         KvProfScope prof("k_skm_route");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
-        if (sg.oriented) {
-            if (sg.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
-            else hipLaunchKernelGGL((k_skm_route<2, 2048, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
-        } else if (sg.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
+        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
         else hipLaunchKernelGGL((k_skm_route<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
     }
     {
@@ -3441,8 +3208,7 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
     KV_REQUIRE(reads->n_tiles == 0 || (reads->tile_max_bases > 0 && reads->tile_max_bases <= 8192u), KV_ERR_ARG, "kv_mex_emit: reads too long for the super-k-mer front end");
     g.read_base = read_base;
     // (the exchange's records are oriented like a single GPU's: every rank cuts with the same rule, so the owner of a bucket finds a
-    // k-mer under one key whichever shard it came from; KV_SKM_ORIENT=0 on every rank keeps the classic form)
-    { const char *e = kv_knob("KV_SKM_ORIENT"); g.oriented = (e && atoi(e) == 0) ? 0u : 1u; }
+    // k-mer under one key whichever shard it came from)
     g.seg1 = d_seg; g.cnt1 = d_cnt;
     g.loose_cap = 1u << 16;
     const size_t b_loose = kv_round_up(g.loose_cap * (size_t)g.lrecw * 8, 256), b_ctr = 256;
@@ -3510,7 +3276,6 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
     const uint32_t Cl = plan->c_lo[my_dest + 1] - plan->c_lo[my_dest];
     g.C1 = Cl; g.F2 = plan->F2; g.fbits = plan->fbits; g.n_buckets = Cl * g.F2;
     g.nwg1 = plan->nwg1; g.cap1 = plan->cap1; g.n_src = (uint32_t)n_src;
-    { const char *e = kv_knob("KV_SKM_ORIENT"); g.oriented = (e && atoi(e) == 0) ? 0u : 1u; }       // as kv_skm_mex_emit cut them
     g.seg1 = const_cast<uint64_t *>(d_recv_seg); g.cnt1 = const_cast<uint32_t *>(d_recv_cnt);
     g.stride = plan->read_len - (uint32_t)plan->ksize + 1u;
     if (Cl == 0) { *n_kmers_in = 0; KvRouteSink rs; memset(&rs, 0, sizeof(rs)); return alloc(ctx, 1, &rs); }
@@ -3629,13 +3394,8 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
     {
         KvProfScope prof("k_skm_route");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(g.sbw)) * 4;
-        if (g.compact) {
-            if (g.oriented) hipLaunchKernelGGL((k_skm_route<1, 4096, true, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-            else hipLaunchKernelGGL((k_skm_route<1, 4096, false, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-        } else if (g.oriented) {
-            if (g.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-            else hipLaunchKernelGGL((k_skm_route<2, 2048, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-        } else if (g.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
+        if (g.compact) hipLaunchKernelGGL((k_skm_route<1, 4096, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
+        else if (g.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
         else hipLaunchKernelGGL((k_skm_route<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
     }
     {
@@ -3698,10 +3458,7 @@ int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8
     {
         KvProfScope prof("k_skm_set_hits");
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
-        if (sg.oriented) {
-            if (sg.kw == 1) hipLaunchKernelGGL((k_skm_set_hits<1, 2048, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
-            else hipLaunchKernelGGL((k_skm_set_hits<2, 1024, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
-        } else if (sg.kw == 1) hipLaunchKernelGGL((k_skm_set_hits<1, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
+        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_set_hits<1, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
         else hipLaunchKernelGGL((k_skm_set_hits<2, 1024>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
         if (sg.kw == 1) hipLaunchKernelGGL(k_skm_loose_set_hits<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, p, out);
         else hipLaunchKernelGGL(k_skm_loose_set_hits<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, p, out);
