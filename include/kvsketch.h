@@ -74,9 +74,8 @@ int kv_table_cache_trim(void);
 int kv_scratch_trim(void);
 const char *kv_version(void);
 /* The environment variables the library looks at are one table (kevlar_amd/csrc/kv_knobs.h, kv_host.hip): SETTINGS a user may set
- * (cache sizes, host threads, progress on stderr), TUNING switches that pin a path or shrink a geometry for tests and A/B runs -- same
- * results on every path; honoured only while KV_TUNING=1 is set -- and EXPERIMENTS that skip parts of kernels (wrong results; only a
- * library built with -DKV_EXPERIMENTS honours them).  kv_knobs_describe: whole_table = 0 writes what is set right now as
+ * (cache sizes, host threads, progress on stderr) and TUNING switches that pin a path or shrink a geometry for tests and A/B runs --
+ * same results on every path; honoured only while KV_TUNING=1 is set.  kv_knobs_describe: whole_table = 0 writes what is set right now as
  * "NAME=value ..." ("ignored:NAME=value" for a knob that is set but not honoured), 1 the table as "name<TAB>class<TAB>what it does"
  * lines.  kv_knob_get: 1 and the value if `name` is set and honoured, 0 if not, KV_ERR_ARG for a name outside the table (the Python
  * wrapper reads its own switches through this, so there is one registry).                                                           */

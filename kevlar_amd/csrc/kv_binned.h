@@ -37,7 +37,6 @@ struct BinGeom {
     unsigned long long *ctr;         // [0] spill count, [1] overflow flag, [2] k-mers added, [3] occupancy delta, [4] work ticket
     uint64_t tsize[BIN_MAX_T];       // table sizes and base pointers by value: stage C starts without a round trip to the descriptor
     uint8_t *ttab[BIN_MAX_T];
-    uint32_t dbg;                    // KV_BIN_DEBUG: timing experiments that skip parts of stage C (results are then wrong)
     int zero_tables;                 // the tables are all zero by decree (kv_sketch::lazy_zero): stage C writes every slice without loading it
     // fast4: four tables of 2^16 <= size < 2^31 bins each and less than 2^32 coarse-item slots in all: the super-k-mer count's drain then
     // takes h % size with the FP64 quotient and 32-bit remainders (the remainder's sign is bit 31) and appends its four items with 32-bit

@@ -689,9 +689,9 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
     const uint32_t *counts = g.gcnt2 + stream * g.nwgB;
     {
         uint32_t myc = 0;
-        if (threadIdx.x < g.nwgB) myc = (g.dbg & 16u) ? 4u : counts[threadIdx.x];
+        if (threadIdx.x < g.nwgB) myc = counts[threadIdx.x];
         unsigned long long flag = 0;
-        if (threadIdx.x == THREADS - 1 && !(g.dbg & 8u)) flag = g.ctr[1];          // overflow flag: leave the tables untouched for the fallback
+        if (threadIdx.x == THREADS - 1) flag = g.ctr[1];          // overflow flag: leave the tables untouched for the fallback
         if (!g.zero_tables)
             for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) l4[j] = tab[j];
         if (threadIdx.x < g.nwgB) seg_cnt[threadIdx.x] = myc;
@@ -733,7 +733,6 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
         Vec r;
         r.q = make_uint4(0, 0, 0, 0); r.n = 0;
         if (v >= total_vec) return r;
-        if (g.dbg & 32u) { r.n = VEC; r.q = *(const uint4 *)(items + (uint64_t)v * VEC); return r; }     // same bytes, one contiguous run
         uint32_t lo = 0, hi = g.nwgB;      // largest segment with vpre[seg] <= v (empty segments share their successor's prefix)
         if (v < (uint32_t)MAXV * THREADS) {
             lo = segof[v];
@@ -750,7 +749,7 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
     };
     Vec first[MAXV];
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) first[i] = (g.dbg & 2u) ? Vec{make_uint4(0, 0, 0, 0), 0u} : fetch(threadIdx.x + (uint32_t)i * THREADS);
+    for (int i = 0; i < MAXV; ++i) first[i] = fetch(threadIdx.x + (uint32_t)i * THREADS);
     if (g.zero_tables)
         for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) l4[j] = make_uint4(0, 0, 0, 0);
     __syncthreads();
@@ -758,11 +757,10 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const uint32_t w[4] = {first[i].q.x, first[i].q.y, first[i].q.z, first[i].q.w};
-        if (g.dbg & 1u) { fresh += w[0] ^ w[1] ^ w[2] ^ w[3]; continue; }
         // (an absent vector would still issue its compare-and-swaps, all on word 0: same-address LDS atomics serialise)
         if (first[i].n) fresh += W ? lds_addw4<STORAGE>(lds, w, first[i].n) : lds_inc8<STORAGE>(lds, w, first[i].n);
     }
-    if (total_vec > (uint32_t)MAXV * THREADS && !(g.dbg & 3u)) {
+    if (total_vec > (uint32_t)MAXV * THREADS) {
         // a fuller slice: the rest through a software pipeline, two vectors ahead
         const uint32_t v_start = (uint32_t)MAXV * THREADS + threadIdx.x;
         Vec v0 = fetch(v_start), v1 = fetch(v_start + THREADS);
@@ -781,8 +779,7 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
         if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&fresh_sh, tot);
     }
     __syncthreads();
-    if (!(g.dbg & 4u))
-        for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) tab[j] = l4[j];
+    for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) tab[j] = l4[j];
     if (t == 0 && threadIdx.x == 0 && fresh_sh) atomicAdd(&g.ctr[3], (unsigned long long)fresh_sh);
 }
 
@@ -913,7 +910,6 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     g.T = s->h.ntables;
     for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) { g.tsize[t] = s->h.size[t]; g.ttab[t] = s->h.tab[t]; }
     g.tile_lds = lds_front;
-    g.dbg = kv_knob("KV_BIN_DEBUG") ? (uint32_t)atoi(kv_knob("KV_BIN_DEBUG")) : 0u;
     uint64_t pmin = UINT64_MAX;
     for (int t = 0; t < g.T; ++t) pmin = std::min(pmin, s->h.size[t]);
     g.sbits = BIN_SLICE_BITS;

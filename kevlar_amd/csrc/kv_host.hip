@@ -1188,7 +1188,6 @@ extern "C" int kv_reads_num_kmers(const kv_reads *r, int ksize, uint64_t *n_kmer
 namespace {
 #define S_ KV_KNOB_SETTING
 #define T_ KV_KNOB_TUNING
-#define X_ KV_KNOB_EXPERIMENT
 const KvKnobDef g_knobs[] = {
     // settings: a user may set these
     {"KV_TABLE_CACHE_GB", S_, "table buffers of destroyed sketches kept for the next sketch of the same size, in GB (default 32; 0: none)"},
@@ -1227,7 +1226,7 @@ const KvKnobDef g_knobs[] = {
     {"KV_SKM_BUCKET_KMERS", T_, "k-mer occurrences aimed at per bucket (tests: many buckets on small inputs)"},
     {"KV_SKM_CAP_PCT", T_, "segment capacity in per cent of the estimate (tests: push records through the loose list)"},
     {"KV_SKM_LOOSE_CAP", T_, "entries of the loose list"},
-    {"KV_SKM_FORCE_LOOSE", T_, "every record through the loose list"},
+    {"KV_SKM_FORCE_LOOSE", T_, "one key in 64 is counted as if its table were full: its occurrences travel through the loose list"},
     {"KV_SKM_NWG1", T_, "S1 writers (upper bound)"},
     {"KV_SKM_NWG2", T_, "S2 writers per coarse stream"},
     {"KV_SKM_BPT", T_, "buckets per work ticket of stage S3"},
@@ -1261,14 +1260,9 @@ const KvKnobDef g_knobs[] = {
     {"KV_MEX_PAIRS", T_, "9: (hash, count) pairs travel in the 9-byte block form"},
     {"KV_MEX_TEST_DECLINE", T_, "point:rank -- that rank fails at that point of the exchange (tests of the agreed fallbacks)"},
     {"KV_ROUTE_OVF_CAP", T_, "entries of the route's overflow list (tests: force the capacity error)"},
-    // experiments: parts of kernels skipped for timing, RESULTS ARE WRONG; a -DKV_EXPERIMENTS build only
-    {"KV_SKM_DEBUG", X_, "bit mask: phases of the super-k-mer count kernels to skip"},
-    {"KV_SKM_SCAN_DEBUG", X_, "bit mask: phases of k_skm_novel_list to skip"},
-    {"KV_BIN_DEBUG", X_, "bit mask: phases of k_bin_apply to skip"},
 };
 #undef S_
 #undef T_
-#undef X_
 }  // namespace
 
 const KvKnobDef *kv_knob_table(size_t *n)
@@ -1281,12 +1275,7 @@ static bool knob_honoured(KvKnobClass cls)
 {
     if (cls == KV_KNOB_SETTING) return true;
     const char *t = getenv("KV_TUNING");                 // (the registry's own switch: the one getenv of the library besides the lookup below)
-    if (!(t && atoi(t) == 1)) return false;
-#if defined(KV_EXPERIMENTS)
-    return true;
-#else
-    return cls != KV_KNOB_EXPERIMENT;
-#endif
+    return t && atoi(t) == 1;
 }
 
 const char *kv_knob(const char *name)
@@ -1313,7 +1302,7 @@ extern "C" int kv_knobs_describe(int whole_table, char *out, uint64_t cap)
 {
     KV_REQUIRE(out && cap > 0, KV_ERR_ARG, "kv_knobs_describe: no buffer");
     std::string s;
-    static const char *cls_name[] = {"setting", "tuning", "experiment"};
+    static const char *cls_name[] = {"setting", "tuning"};
     for (const KvKnobDef &d : g_knobs) {
         if (whole_table) {
             s += d.name; s += '\t'; s += cls_name[d.cls]; s += '\t'; s += d.doc; s += '\n';

@@ -41,7 +41,7 @@ struct SkmGeom {
     uint32_t n_buckets, quota3;
     uint32_t sbw;                    // words of record-start bits per wave in the bucket walk
     uint64_t bucket_kmers;           // average k-mers per fine bucket
-    uint32_t dbg;                    // KV_SKM_DEBUG: timing experiments that skip parts of kernels (results are then wrong)
+    uint32_t force_loose;            // KV_SKM_FORCE_LOOSE: k_skm_count sends one key in 64 through the loose list
     // abundance list the count pass writes (KvAbundList; abl_keys == nullptr: off): every workgroup appends to its own
     // stretch of abl_cap_wg entries and notes where each bucket's entries start
     uint64_t *abl_keys; uint8_t *abl_cnts; uint32_t *abl_bstart, *abl_bcount; uint32_t abl_cap_wg;
@@ -71,10 +71,6 @@ struct SkmGeom {
 };
 
 // segment `seg` of coarse bucket c in seg1 / cnt1, counted in segments
-// Phase switches of the dissection scripts (scratch/skm_phases.py, scan_phases.py) and KV_SKM_FORCE_LOOSE of the tests.  The three
-// long kernels exist twice: the instance that looks at the switches is launched only when one is set (the tests in the occurrence loop
-// of k_skm_count cost 0.07 ms per sample, 0.4 ms per step of config 2).
-#define SKM_DBG(sg) (KNOBS ? (sg).dbg : 0u)
 __device__ __forceinline__ uint64_t skm_seg1_slot(const SkmGeom &sg, uint32_t c, uint32_t seg)
 {
     if (sg.seg1_wmajor) return (uint64_t)seg * sg.C1 + c;
@@ -99,9 +95,7 @@ struct SkmAblSet {
 namespace {
 
 #define SKM_THREADS1 512
-#if !defined(SKM_S1_WAVE_THREADS_DEFAULT)
 #define SKM_S1_WAVE_THREADS_DEFAULT 512u      // threads per workgroup of k_skm_emit_wave (1024: one workgroup per CU, see the kernel)
-#endif
 #define SKM_THREADS3 512
 #define SKM_MAXPROBE 48
 // One global counter hands out work; a returning atomic on one word saturates at ~90 per microsecond on this chip
@@ -175,7 +169,6 @@ __device__ __forceinline__ uint32_t skm_search(const uint32_t *pre, uint32_t n, 
 template <int CH>
 __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint32_t n_tiles, SkmGeom sg)   // 6 waves per SIMD: three workgroups per CU
 {
-    constexpr bool KNOBS = true;
     __shared__ SkmTile sh;
     __shared__ uint32_t cur[256];
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -291,7 +284,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
         const uint32_t NB = sh.bpre[nr];
         // P1: one thread per packed word: the order values of the m-mers starting at its 16 bases
         const uint32_t mmask = m == 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u);
-        for (uint32_t wi = threadIdx.x; wi < ((SKM_DBG(sg) & 512u) ? 0u : nwords); wi += SKM_THREADS1) {
+        for (uint32_t wi = threadIdx.x; wi < nwords; wi += SKM_THREADS1) {
             const uint32_t r = sh.uni_wpr ? skm_div(wi, sh.uni_wpr, sh.inv_wpr) : skm_search(sh.wpre, nr, wi);
             const uint32_t j0 = (wi - sh.wpre[r]) * 16u, L = sh.len[r];
             const uint32_t q0 = sh.bpre[r] + j0;
@@ -315,7 +308,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
         // w - 1 - CH values every window contains + a growing prefix) and where it changes.  A run is a stretch of k-mers with the
         // same minimizer VALUE (its bucket is a function of that value, taken once per run in P4; two values that share a bucket
         // -- one pair in C1 x F2 -- merely give two records where one would have done).
-        const uint32_t nchunks = (SKM_DBG(sg) & 32u) ? 0u : sh.cpre[nr];             // <= 8192 / CH + 64 < 3 * SKM_THREADS1
+        const uint32_t nchunks = sh.cpre[nr];                                      // <= 8192 / CH + 64 < 3 * SKM_THREADS1
         const uint32_t nrounds = (nchunks + SKM_THREADS1 - 1u) / SKM_THREADS1;
         uint32_t my_q[3], my_starts[3];
 #pragma unroll
@@ -383,7 +376,6 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
                 }
             }
         }
-        if (SKM_DBG(sg) & 16u) nstart = 0;
         __syncthreads();
         // P4: one thread per run: measure it, cut it into records of <= ncap k-mers, store them
         for (uint32_t i = threadIdx.x; i < nstart; i += SKM_THREADS1) {
@@ -407,8 +399,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
                 if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
                 const uint64_t hdr = skm_header(pos, n, fine, rev);
                 const uint32_t p = atomicAdd(&cur[coarse], 1u);
-                if (SKM_DBG(sg) & 1024u) n_rec += hdr ^ bw[0] ^ bw[1];
-                else if (p < sg.cap1) skm_store_record(sg.seg1 + (skm_seg1_slot(sg, coarse, blockIdx.x) * sg.cap1 + p) * (uint64_t)sg.recw, hdr, bw, sg.nbw);
+                if (p < sg.cap1) skm_store_record(sg.seg1 + (skm_seg1_slot(sg, coarse, blockIdx.x) * sg.cap1 + p) * (uint64_t)sg.recw, hdr, bw, sg.nbw);
                 else skm_loose_push(sg, hdr, bw);
                 n_rec += 1;
                 left -= n; pos += n; b += n;
@@ -444,7 +435,7 @@ __host__ __device__ inline uint32_t skm_wave_slice_words(uint32_t R, uint32_t L,
 // open cache line per coarse bucket, and the L2 of an XCD (4 MB) merges a record's 16- and 8-byte stores into whole lines only while
 // the open lines of the XCD's workgroups fit beside the rest of its traffic: 251 buckets x 96 workgroups x 128 B = 3 MB do not
 // (WRITE_SIZE 2.5-2.7 GB per 1.36 GB of records, measured with 512 and with 768 writers), 251 x 32 x 128 B = 1 MB do (1.0 x).
-template <int CH, bool KNOBS, int THREADS>
+template <int CH, int THREADS>
 __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_wave(ReadsDev rd, SkmGeom sg, uint32_t R, uint32_t n_mt, uint32_t quota_mt, uint32_t per_ticket)
 {
     constexpr uint32_t PS = CH == 16 ? 4u : 3u;
@@ -499,7 +490,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
         if (more) { pf = words_of(mt + 1u); pf_mt = mt + 1u; }
         // P1: the order values of the m-mers starting at the 16 bases of this lane's word.  (Values of m-mers that run past the
         // end of their read are garbage: no window of a k-mer of the read contains them.)
-        if (lane < nwords && !(SKM_DBG(sg) & 512u)) {
+        if (lane < nwords) {
             const uint32_t up = (uint32_t)__shfl_down((int)word, 1);
             const uint64_t win = (uint64_t)word | ((uint64_t)(lane == 63u ? 0u : up) << 32);
             const uint64_t rcw = ~skm_rev2_64(win);
@@ -514,7 +505,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
         __builtin_amdgcn_wave_barrier();
         // P2: a lane per chunk of CH k-mer starts: window minima (shared suffix of the chunk + the values every window of the chunk
         // contains + a growing prefix) and where they change; then every run start with its minimizer, in position order
-        const uint32_t nchunks = (SKM_DBG(sg) & 32u) ? 0u : nr * cpr;
+        const uint32_t nchunks = nr * cpr;
         uint32_t startmask = 0, q = 0;
         uint32_t v[CH];
 #pragma unroll
@@ -551,8 +542,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
             const uint32_t upv = __shfl_up(incl, d);
             if (lane >= (uint32_t)d) incl += upv;
         }
-        uint32_t nstart = (uint32_t)__shfl((int)incl, 63);
-        if (SKM_DBG(sg) & 16u) nstart = 0;
+        const uint32_t nstart = (uint32_t)__shfl((int)incl, 63);
         if (more) wl0[66u * (parity ^ 1u) + lane] = pf;
         for (uint32_t lo = 0; lo < nstart; lo += SKM_WAVE_RUNS) {
             // runs lo .. lo + SKM_WAVE_RUNS (one more than are processed: the end of the last one), listed by the lanes that found them
@@ -589,8 +579,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
                     if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
                     const uint64_t hdr = skm_header(pos, n, fine, rev);
                     const uint32_t p = atomicAdd(&cur[coarse], 1u);
-                    if (SKM_DBG(sg) & 1024u) n_rec += hdr ^ bw[0] ^ bw[1];
-                    else if (p < sg.cap1) skm_store_record_wide(my_seg + coarse * cstride + p * (uint32_t)sg.recw, hdr, bw, sg.nbw);
+                    if (p < sg.cap1) skm_store_record_wide(my_seg + coarse * cstride + p * (uint32_t)sg.recw, hdr, bw, sg.nbw);
                     else skm_loose_push(sg, hdr, bw);
                     n_rec += 1;
                     left -= n; pos += n; b += n;
@@ -628,27 +617,15 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
 // useful size would leave a tail of a ticket, and the device-wide counter is not in the picture.
 // Instances: w = 20 (k = 31: C = 1) and w = 40 (k = 51: C = 2), m = 12, reads of up to 16 x NW bases; everything else takes the kernels above.
 #define SKM_LANE_B 20
-#if !defined(SKM_LANE_FULL)
-#define SKM_LANE_FULL 0           // 1: blocks in the middle of a read run without the per-position scalar tests (measured: slower)
-#endif
-#if !defined(SKM_LANE_BRANCHFREE)
-#define SKM_LANE_BRANCHFREE 0     // 1: every lane writes an entry at every k-mer, lanes without a finished run to a dummy slot (no exec regions)
-#endif
-#if !defined(SKM_LANE_CAP)
 #define SKM_LANE_CAP 320u         // finished runs a wave lists between two flushes (64 reads x 40 k-mers bring ~250; what does not fit is written at once)
-#endif
 #define SKM_LANE_THREADS 512
-#if !defined(SKM_LANE_WAVES)
 #define SKM_LANE_WAVES 6          // waves per SIMD the kernel is compiled for (3 workgroups per CU)
-#endif
 // a wave's slice of LDS: the group's words, their reverse complement read by read (oriented records), the run list
 __host__ __device__ inline uint32_t skm_lane_slice_words(uint32_t wpr) { return 2u * (64u * wpr + 4u) + 2u * SKM_LANE_CAP + 2u; }
 
 // one block of B m-mers for every lane's read: Sold holds the suffix minima of the block the finishing k-mers START in (C blocks
 // back) and receives this block's values; Smid (C = 2) the suffix minima of the block between, Smid[0] its minimum
-// FULL: every m-mer of the block exists and a k-mer > 0 of the read ends at each of them (the blocks in the middle of a read: no
-// per-position tests, which are scalar but not free -- a compare and a branch each, 13 scalar instructions per m-mer with them)
-template <int C, bool FULL, typename Append>
+template <int C, typename Append>
 __device__ __forceinline__ void skm_lane_block(const uint32_t *wl, uint32_t rbase, uint32_t lane, uint32_t b, uint32_t npos, uint32_t nk,
                                                uint32_t (&Sold)[SKM_LANE_B], const uint32_t (&Smid)[SKM_LANE_B], uint32_t &prev_v, uint32_t &start_prev,
                                                uint32_t &n_ent, Append append)
@@ -663,17 +640,17 @@ __device__ __forceinline__ void skm_lane_block(const uint32_t *wl, uint32_t rbas
 #pragma unroll
     for (int j = 0; j < B; ++j) {
         const uint32_t p = (uint32_t)B * b + (uint32_t)j;
-        if (!FULL && p >= npos) break;                                 // (the same for every lane: a scalar branch)
+        if (p >= npos) break;                                          // (the same for every lane: a scalar branch)
         const uint32_t f = (uint32_t)(X >> (2 * j)) & 0xffffffu, rv = (uint32_t)(R >> (40 - 2 * j)) & 0xffffffu;
         const uint32_t val = skm_order_s(f, rv);
         pre = min(pre, val);
-        if (FULL || p + 1u >= (uint32_t)(C * B)) {
+        if (p + 1u >= (uint32_t)(C * B)) {
             const uint32_t i = p + 1u - (uint32_t)(C * B);             // the k-mer whose window ends at this m-mer
-            if (FULL || i < nk) {
+            if (i < nk) {
                 uint32_t minv;
                 if (C == 1) minv = j == B - 1 ? pre : min(Sold[j == B - 1 ? 0 : j + 1], pre);
                 else minv = j == B - 1 ? min(Smid[0], pre) : min(min(Sold[j == B - 1 ? 0 : j + 1], Smid[0]), pre);
-                if (!FULL && i == 0u) {
+                if (i == 0u) {
                     prev_v = minv; start_prev = lane;                 // lane | first k-mer << 6: the upper word of the run's entry, but for its end
                 } else {
                     // (a lane that finds the list full keeps its run open and asks again at the next k-mer, after the flush that full
@@ -682,13 +659,7 @@ __device__ __forceinline__ void skm_lane_block(const uint32_t *wl, uint32_t rbas
                     // (lanes without a read walk words of zeros: one minimizer from end to end, no run ever finishes)
                     const bool want = minv != prev_v;
                     const unsigned long long bal = __ballot(want);
-#if SKM_LANE_BRANCHFREE
-                    const bool done = append(bal, want, prev_v, start_prev, i);
-                    prev_v = done ? minv : prev_v;
-                    start_prev = done ? (lane | (i << 6)) : start_prev;
-#else
-                    if (want && append(bal, true, prev_v, start_prev, i)) { prev_v = minv; start_prev = lane | (i << 6); }
-#endif
+                    if (want && append(bal, prev_v, start_prev, i)) { prev_v = minv; start_prev = lane | (i << 6); }
                     n_ent += (uint32_t)__popcll(bal);
                 }
             }
@@ -798,19 +769,11 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
         };
         uint32_t n_ent = 0;
         // an entry: the run's minimizer | (lane | first k-mer << 6 | the k-mer behind its last << 18) << 32
-        auto append = [&](unsigned long long bal, bool want, uint32_t v, uint32_t lane_start, uint32_t end) -> bool {
-            uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, n_ent));
-#if SKM_LANE_BRANCHFREE
-            const bool ok = want && slot < SKM_LANE_CAP;
-            slot = ok ? slot : SKM_LANE_CAP;                          // (slot CAP: the word nobody reads)
-            ent[slot] = (unsigned long long)v | ((unsigned long long)(lane_start | (end << 18)) << 32);
-            return ok;
-#else
-            (void)want;
+        auto append = [&](unsigned long long bal, uint32_t v, uint32_t lane_start, uint32_t end) -> bool {
+            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, n_ent));
             if (slot >= SKM_LANE_CAP) return false;                   // (a wave of reads that change minimizer at nearly every k-mer)
             ent[slot] = (unsigned long long)v | ((unsigned long long)(lane_start | (end << 18)) << 32);
             return true;
-#endif
         };
         auto flush = [&]() {
             if (!pf_waited) {
@@ -837,14 +800,8 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
         const uint32_t rbase = lane * wpr;
         uint32_t since = 0;
         for (uint32_t b = 0; b < nblocks; b += (C == 2 ? 2u : 1u)) {
-            // block b is FULL when its first m-mer ends k-mer 1 or a later one and its last m-mer ends a k-mer of the read
-            auto full = [&](uint32_t bb) { return (uint32_t)B * bb + 1u > (uint32_t)(C * B) && (uint32_t)B * bb + (uint32_t)B <= nk + (uint32_t)(C * B) - 1u; };
-            if (SKM_LANE_FULL && full(b)) skm_lane_block<C, true>(wl, rbase, lane, b, npos, nk, Sa, Sb, prev_v, start_prev, n_ent, append);
-            else skm_lane_block<C, false>(wl, rbase, lane, b, npos, nk, Sa, Sb, prev_v, start_prev, n_ent, append);
-            if (C == 2 && b + 1u < nblocks) {
-                if (SKM_LANE_FULL && full(b + 1u)) skm_lane_block<C, true>(wl, rbase, lane, b + 1u, npos, nk, Sb, Sa, prev_v, start_prev, n_ent, append);
-                else skm_lane_block<C, false>(wl, rbase, lane, b + 1u, npos, nk, Sb, Sa, prev_v, start_prev, n_ent, append);
-            }
+            skm_lane_block<C>(wl, rbase, lane, b, npos, nk, Sa, Sb, prev_v, start_prev, n_ent, append);
+            if (C == 2 && b + 1u < nblocks) skm_lane_block<C>(wl, rbase, lane, b + 1u, npos, nk, Sb, Sa, prev_v, start_prev, n_ent, append);
             since += (C == 2 ? 2u : 1u);
             // (the last block's runs leave with the final ones; a list that is filling up is flushed whatever the count says)
             if ((since >= flush_blocks || n_ent + 192u > SKM_LANE_CAP) && n_ent && b + (C == 2 ? 2u : 1u) < nblocks) { flush(); since = 0; }
@@ -853,7 +810,7 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
         if (n_ent + 64u > SKM_LANE_CAP) flush();
         {
             const unsigned long long bal = __ballot(active);
-            if (active) (void)append(bal, true, prev_v, start_prev, nk);
+            if (active) (void)append(bal, prev_v, start_prev, nk);
             n_ent += (uint32_t)__popcll(bal);
         }
         flush();
@@ -925,11 +882,7 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split(SkmGeom sg)
 // SKM_S2_CHUNK records at a time, ranks them by fine bucket (LDS atomics: rank inside the chunk's share of the bucket),
 // lays them out bucket by bucket in LDS and copies that image out with consecutive lanes on consecutive words: a bucket's
 // records of one chunk leave as one contiguous run.  Used while a chunk holds at least ~2 records per bucket.
-#if defined(SKM_S2_CHUNK_OVERRIDE)
-#define SKM_S2_CHUNK SKM_S2_CHUNK_OVERRIDE
-#else
 #define SKM_S2_CHUNK 2048u
-#endif
 #define SKM_S2_MAXF 1024u
 template <int RECW>
 __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
@@ -1060,17 +1013,11 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
 }
 
 // ---- LDS combining table -------------------------------------------------------------------------------
-// the step from a slot to the next one tried: 1 (linear probing), or an odd number taken from the key's hash (double hashing: two keys
-// that meet in one slot part ways at once, no clusters -- the wave waits for the lane with the longest chain)
-// (k_skm_count 3.23 -> 3.04 ms per sample of config 2; -DSKM_LINEAR_PROBE keeps the old order for A/B builds)
-#if defined(SKM_LINEAR_PROBE)
-#define SKM_PROBE_STEP(h) 1u
-#else
-#if !defined(SKM_STEP_MASK)
+// the step from a slot to the next one tried: an odd number taken from the key's hash (double hashing: two keys that meet in one slot
+// part ways at once, no clusters -- the wave waits for the lane with the longest chain)
+// (k_skm_count 3.23 -> 3.04 ms per sample of config 2 against linear probing, a step of 1)
 #define SKM_STEP_MASK 62u
-#endif
 #define SKM_PROBE_STEP(h) ((((h) >> 20) & SKM_STEP_MASK) | 1u)
-#endif
 // slot a hash starts at / the slot `step` further on, for tables of 2^n slots and of any other size (3072: the count's instances that
 // share their LDS with a table of records) -- there the top bits of the hash pick the slot, so the step comes from the low ones
 template <int TS>
@@ -1345,35 +1292,27 @@ __host__ __device__ inline uint32_t skm_wave_scratch_words(uint32_t sbw) { retur
 // murmur tail become constants -- 3 % of the kernel.  FK = 0 reads k from the geometry.
 // waves per SIMD the two-word-key instances are compiled for (6: three workgroups per CU at 80 VGPRs, 13-19 of them spilled; 4: two
 // workgroups at up to 128 VGPRs, nothing spilled)
-#if !defined(SKM_K2_WAVES)
 #define SKM_K2_WAVES 6
-#endif
 // The instances for a fixed k (FK != 0) take the two murmurs from the product tables (skm_key_hash_pl: P1 / P2, 4 KB of
 // dynamic LDS in place of the 1 KB ASCII table) and keep their occurrence counters as 16-bit halves of a word -- that is where the
 // 3 KB come from with three workgroups on a CU; the host launches them only for buckets that cannot hold 65536 occurrences
-// (skm_count_pl_fits), the instances with k at run time count in 32 bits.  -DSKM_PL=0: A/B builds without either.
-#if !defined(SKM_PL)
-#define SKM_PL 1
-#endif
+// (skm_count_pl_fits), the instances with k at run time count in 32 bits.
 // slots of the k = 51 instances' table: their buckets are sized for 2048 slots (the scan kernels' tables), the count's own table may be
 // roomier -- fewer occurrences on the loose list, shorter probe chains -- as long as three workgroups fit a CU (2560: 52.7 KB each)
-#if !defined(SKM_TS51)
 #define SKM_TS51 2560
-#endif
 // (k = 31: 4608 slots measured 1 % faster than 4096 -- and let a bucket's distinct list outgrow what the list scan takes, SKM_LIST_MAX:
 // scratch/fuzz_list.py seed 702, trial 149 lost 8 % of its hits; the table stays at 4096, the assertion below holds every instance to it)
-#if !defined(SKM_TS31)
 #define SKM_TS31 4096
-#endif
 // entries of one bucket the scan from the distinct list takes (k_skm_novel_list): a bucket's list has at most as many entries as the
 // count kernel's LDS table has slots
 #define SKM_LIST_MAX 4096u
-template <int KW, int TS, bool KNOBS, int FK, bool COMPACT = false>
+// FORCE_LOOSE: the instances KV_SKM_FORCE_LOOSE runs (sg.force_loose); the others leave its test out of the occurrence loop (0.07 ms per sample)
+template <int KW, int TS, bool FORCE_LOOSE, int FK, bool COMPACT = false>
 __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_skm_count(SkmGeom sg, const SketchDev *__restrict__ sk,
                                                            const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
 {
     static_assert((uint32_t)TS <= SKM_LIST_MAX, "a bucket's distinct list (one entry per occupied slot) must fit what k_skm_novel_list takes");
-    constexpr bool PL = SKM_PL && FK != 0;
+    constexpr bool PL = FK != 0;
     __shared__ SkmTable<KW, TS> tb;
     __shared__ uint32_t cnt[PL ? TS / 2 : TS];   // occurrences of the key in the same slot (PL: slot s in half s & 1 of word s >> 1)
     __shared__ uint32_t next_bucket;
@@ -1442,13 +1381,12 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
             }
         }
         // combine the occurrences of the bucket
-        if (!(SKM_DBG(sg) & 2u)) skm_walk_bucket<KW, false, FK, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
-            if (SKM_DBG(sg) & 128u) { n_added += c.w[0] & 1; return false; }
+        skm_walk_bucket<KW, false, FK, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
             // (KV_SKM_FORCE_LOOSE: one key in 64 is treated like a key that found its table full -- every occurrence travels alone;
             // results stay exact, tests use it to put single k-mers on the loose list of a batch that otherwise fits)
-            const bool forced = (SKM_DBG(sg) & 4096u) && ((c.w[0] * 0x9e3779b97f4a7c15ull) >> 58) == 0;
+            const bool forced = FORCE_LOOSE && sg.force_loose && ((c.w[0] * 0x9e3779b97f4a7c15ull) >> 58) == 0;
             const int slot = skm_cacheable<KW>(c) && !forced ? skm_table_insert(tb, c) : -1;
-            if (slot >= 0 && !(SKM_DBG(sg) & 256u)) {
+            if (slot >= 0) {
                 if (PL) atomicAdd(&cnt[(uint32_t)slot >> 1], 1u << (((uint32_t)slot & 1u) * 16u));
                 else atomicAdd(&cnt[slot], 1u);
             }
@@ -1471,11 +1409,9 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
                 cnt[slot] = 0;
             }
             n_distinct += 1;
-            if (SKM_DBG(sg) & 1u) return;
             uint64_t h;
             if constexpr (PL) h = skm_key_hash_pl<KW, FK>(c, P1, P2);
             else h = skm_key_hash<KW>(c, lut, hp);
-            if (SKM_DBG(sg) & 64u) { n_added += h & 1; return; }
             // distinct list: key and hash of every k-mer in here (the scan of this batch then neither combines nor hashes again)
             if (sg.dl_keys) {
                 const unsigned long long here = __ballot(true);
@@ -1856,7 +1792,6 @@ __device__ __forceinline__ void skm_mark(const NovelParams &p, const ReadsDev &r
 template <int KW, int TS>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
 {
-    constexpr bool KNOBS = true;
     __shared__ SkmTable<KW, TS> tb;
     __shared__ uint32_t flag[TS / 32];           // bit per slot: the key is interesting
     __shared__ uint32_t rej[TS / 32];            // bit per slot: a control's abundance list rejects the key (no probe needed)
@@ -1913,7 +1848,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
         }
         __syncthreads();
         // evaluate each of them once
-        if (!(SKM_DBG(sg) & 4u)) skm_for_occupied<TS>(tb.key[0], (uint16_t *)scratch, skm_wave_scratch_words(sg.sbw) * 2u, [&](uint32_t slot) {
+        skm_for_occupied<TS>(tb.key[0], (uint16_t *)scratch, skm_wave_scratch_words(sg.sbw) * 2u, [&](uint32_t slot) {
             SkmKey<KW> c;
             c.w[0] = tb.key[0][slot];
             if (KW == 2) c.w[KW - 1] = tb.key[KW - 1][slot];
@@ -1921,7 +1856,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
             if (band_pass(p, h) && novel_test_fast(ns, p, h, nullptr, 0ull)) { atomicOr(&flag[slot >> 5], 1u << (slot & 31)); any_hit = 1; }
         }, rej);            // (keys a control's list rejects are not queued: 25 M of 106 M at config 2, lanes that used to sit out their wave's hashes)
         __syncthreads();
-        if (any_hit == 0 || (SKM_DBG(sg) & 8u)) continue;
+        if (any_hit == 0) continue;
         // mark every occurrence of an interesting k-mer (an occurrence whose key is absent went to the loose list)
         skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
             if (!skm_cacheable<KW>(c)) return false;
@@ -1961,14 +1896,10 @@ __global__ __launch_bounds__(256) void k_case_bits(const uint8_t *__restrict__ t
 // are any are the bucket's records walked, to mark their occurrences.  Occurrences that missed the count pass's LDS tables are in
 // the loose list already (k_skm_loose_novel evaluates them one by one).  A bucket's list has at most as many entries as the count
 // kernel's LDS table has slots.
-template <int KW, int TSM, bool KNOBS>
+template <int KW, int TSM>
 __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
 {
-#if defined(SKM_LIST_E)
-    constexpr uint32_t E = SKM_LIST_E;
-#else
     constexpr uint32_t E = 4;                    // entries a thread has in flight (2 / 4 / 6 measured: 2.64 / 2.6-2.8 / 2.52 ms, within the spread between runs)
-#endif
     __shared__ SkmTable<KW, TSM> rtb;            // rejected by a control's list
     __shared__ SkmTable<KW, TSM> itb;            // interesting
     __shared__ NovelShared ns;
@@ -2027,7 +1958,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
             }
         }
         __syncthreads();
-        for (uint32_t base = 0; base < ((SKM_DBG(sg) & 4u) ? 0u : en); base += E * SKM_THREADS3) {
+        for (uint32_t base = 0; base < en; base += E * SKM_THREADS3) {
             if (base) request(base);
             bool live[E];
             uint32_t v[E];
@@ -2067,7 +1998,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
             // marks in instalments
             if (n_int > TSM / 4 && j0 + SKM_THREADS3 < nc) mark_pass(b);
         }
-        if (n_int != 0 && !(SKM_DBG(sg) & 8u)) mark_pass(b);
+        if (n_int != 0) mark_pass(b);
     }
 }
 
@@ -2411,7 +2342,6 @@ static bool skm_lane_fits_len(const SkmGeom &g, uint32_t L)
     // (w = 40, k = 51: two arrays of suffix minima; that instance is compiled for 4 waves per SIMD and skm_build starts two workgroups
     // per CU for it -- at six waves it spilled and measured slower than the wave kernel, 5.5 against 4.1 ms per step of config 5)
     if (g.w != SKM_LANE_B && e1 && !strcmp(e1, "lane6")) return false;
-    if (g.dbg & ~4096u) return false;                           // the phase switches of the dissection scripts live in the older kernels
     // three workgroups per CU for reads of up to 112 bases (seven packed words and their reverse complement per lane), two up to 224
     return skm_lane_wgs_per_cu(L) >= 2u;
 }
@@ -2448,9 +2378,9 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
         const uint32_t quota_mt = (uint32_t)std::min<uint64_t>(kv_round_up(per_wave, per_ticket), 0xfffffff0ull);
         void (*kernel)(ReadsDev, SkmGeom, uint32_t, uint32_t, uint32_t, uint32_t);
         if (threads == 1024)
-            kernel = ch == 16 ? (g.dbg ? k_skm_emit_wave<16, true, 1024> : k_skm_emit_wave<16, false, 1024>) : (g.dbg ? k_skm_emit_wave<8, true, 1024> : k_skm_emit_wave<8, false, 1024>);
+            kernel = ch == 16 ? k_skm_emit_wave<16, 1024> : k_skm_emit_wave<8, 1024>;
         else
-            kernel = ch == 16 ? (g.dbg ? k_skm_emit_wave<16, true, 512> : k_skm_emit_wave<16, false, 512>) : (g.dbg ? k_skm_emit_wave<8, true, 512> : k_skm_emit_wave<8, false, 512>);
+            kernel = ch == 16 ? k_skm_emit_wave<16, 512> : k_skm_emit_wave<8, 512>;
         kv_ensure_dynamic_lds((const void *)kernel, lds);
         hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(threads), lds, st, reads_dev(reads), g, R, (uint32_t)n_mt, quota_mt, per_ticket);
         return;
@@ -2586,7 +2516,6 @@ void skm_geom_k(SkmGeom &g, int k)
     g.lrecw = g.recw;
     g.ncap = 32 * g.nbw - k + 1;
     g.sbw = ((64u * (uint32_t)g.ncap) >> 5) + 2u;
-    g.dbg = kv_knob("KV_SKM_DEBUG") ? (uint32_t)atoi(kv_knob("KV_SKM_DEBUG")) : 0u;
     g.bpt = skm_default_bpt();
 }
 
@@ -2609,24 +2538,12 @@ __global__ void k_mex_sum_kmers(const uint64_t *seg, const uint32_t *cnt, const 
 int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hipStream_t st, double distinct_frac = 0.0, bool want_pos = true)
 {
     SkmGeom &g = idx.g;
-    memset(&g, 0, sizeof(g));
     idx.valid = false;
     idx.mex_scan_ready = false;
     idx.dl_valid = false;
     idx.builds += 1;
-    g.k = k;
-    g.m = skm_minimizer_len(k);
-    g.w = k - g.m + 1;
-    g.wpow = 1;
-    while (g.wpow * 2 <= g.w) g.wpow *= 2;
-    g.kw = k <= 32 ? 1 : 2;
-    g.nbw = g.kw + 1;
-    g.recw = 1 + g.nbw;
-    g.lrecw = g.recw;
-    g.ncap = 32 * g.nbw - k + 1;
-    g.dbg = kv_knob("KV_SKM_DEBUG") ? (uint32_t)atoi(kv_knob("KV_SKM_DEBUG")) : 0u;
-    if (kv_knob("KV_SKM_FORCE_LOOSE")) g.dbg |= 4096u;
-    g.bpt = skm_default_bpt();
+    skm_geom_k(g, k);
+    g.force_loose = kv_knob("KV_SKM_FORCE_LOOSE") ? 1u : 0u;
     const uint32_t table_slots = g.kw == 1 ? 4096u : 2048u;
     const char *tgt_env = kv_knob("KV_SKM_BUCKET_KMERS");      // tests shrink the buckets to exercise many of them on small inputs
     // k-mers per fine bucket: as many as leave the LDS table ~0.4 full (0.29 for two-word keys, whose longer windows put
@@ -2870,19 +2787,19 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         KvProfScope prof("k_skm_count");
         const uint32_t ns = (uint32_t)(plan.g.T * plan.g.C);
         // the fixed-k instances count a key's occurrences in 16 bits (k_skm_count, PL): only for buckets that cannot hold 65536 of them
-        const bool fixed_k = !sg.dbg && !kv_knob("KV_SKM_ANY_K") && (!SKM_PL || (uint64_t)sg.nwg2 * sg.cap2 * (uint64_t)sg.ncap < 65536ull);
+        const bool fixed_k = !sg.force_loose && !kv_knob("KV_SKM_ANY_K") && (uint64_t)sg.nwg2 * sg.cap2 * (uint64_t)sg.ncap < 65536ull;
         void (*kernel)(SkmGeom, const SketchDev *, const SketchDev *, ConsumeFilter, BinGeom) =
-            sg.kw == 1 ? (sg.dbg ? k_skm_count<1, 4096, true, 0> : k_skm_count<1, 4096, false, 0>) : (sg.dbg ? k_skm_count<2, 2048, true, 0> : k_skm_count<2, 2048, false, 0>);
+            sg.kw == 1 ? (sg.force_loose ? k_skm_count<1, 4096, true, 0> : k_skm_count<1, 4096, false, 0>) : (sg.force_loose ? k_skm_count<2, 2048, true, 0> : k_skm_count<2, 2048, false, 0>);
         bool pl = false;         // a fixed-k instance: 4 KB of product tables where the others keep 1 KB of ASCII
         if (sg.k == 31 && sg.recw == 3 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31>; pl = true; }
         if (sg.compact) {       // 16-byte records (sg.recw == 2): their own instances
-            kernel = sg.dbg ? k_skm_count<1, 4096, true, 0, true> : k_skm_count<1, 4096, false, 0, true>;
+            kernel = sg.force_loose ? k_skm_count<1, 4096, true, 0, true> : k_skm_count<1, 4096, false, 0, true>;
             pl = false;
             if (sg.k == 31 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31, true>; pl = true; }
         }
         // (BASELINE.json configs[4]: k = 51 -- two-word keys, three murmur blocks + a 3-byte tail)
         if (sg.k == 51 && sg.recw == 4 && fixed_k) { kernel = k_skm_count<2, SKM_TS51, false, 51>; pl = true; }
-        const size_t lds = ((pl && SKM_PL ? 1024 : 256) + ((ns + 3u) & ~3u) + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
+        const size_t lds = ((pl ? 1024 : 256) + ((ns + 3u) & ~3u) + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
         hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
     }
     {
@@ -3017,7 +2934,6 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     }
     if (kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] scan: %d of %d controls bring an abundance list in this bucket geometry\n", abls.n, p.host_nctrl);
     if (kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] scan: %s\n", from_list ? "from the count pass's distinct list" : "by walking the buckets");
-    if (const char *e = kv_knob("KV_SKM_SCAN_DEBUG")) sg.dbg = (uint32_t)atoi(e);       // scratch/scan_phases.py
     NovelParams pl = p;
     pl.case0_bits = nullptr;
     // (KV_NOVEL_BITS=0: probe the table.  Measured at config 2: the bit map costs 0.135 ms, the list scan goes from 2.57-2.77 to 2.34 ms)
@@ -3036,7 +2952,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
         sg.dl_keys = idx->dl_keys; sg.dl_hash = idx->dl_hash; sg.dl_bstart = idx->dl_bstart; sg.dl_bcount = idx->dl_bcount; sg.dl_cap_wg = idx->dl_cap_wg;
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
         void (*kernel)(SkmGeom, ReadsDev, NovelParams, SkmAblSet) =
-            sg.kw == 1 ? (sg.dbg ? k_skm_novel_list<1, 2048, true> : k_skm_novel_list<1, 2048, false>) : (sg.dbg ? k_skm_novel_list<2, 1024, true> : k_skm_novel_list<2, 1024, false>);
+            sg.kw == 1 ? k_skm_novel_list<1, 2048> : k_skm_novel_list<2, 1024>;
         hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, pl, abls);
         if (p.ab_keys) hipLaunchKernelGGL(k_ab_fill, dim3(2048), dim3(256), 0, st, p);
         if (p.ab_list && kv_knob("KV_SKM_VERBOSE")) {

@@ -1,12 +1,12 @@
 #!/bin/bash
-# WRITE_SIZE and duration of the two record-moving kernels under different writer counts
+# WRITE_SIZE of the two record-moving kernels under different writer counts
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_w; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for cfg in "768 4" "512 4" "512 2" "256 2" "768 2" "768 8"; do
   set -- $cfg
   export KV_SKM_NWG1=$1 KV_SKM_NWG2=$2
-  python3 $REPO/scratch/skm_phases.py 0 2>/dev/null | tail -1 | sed "s/^/nwg1=$1 nwg2=$2 time /"
+  echo "nwg1=$1 nwg2=$2"
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/w_$1_$2 -- python3 $REPO/scratch/pmc_count.py > /dev/null 2>&1
   python3 - <<PY
 import csv, glob, collections, re

@@ -894,11 +894,11 @@ def test_exchange_plans_are_host_arithmetic_every_rank_repeats():
     assert lib.kv_mex_plan_make(0, 12, 1000, 100, 8, ctypes.byref(p)) != 0          # k below the super-k-mer front end's range
 
 
-def test_every_environment_switch_is_in_the_one_registry(monkeypatch):
+def test_every_environment_switch_is_in_the_one_registry_of_two_classes(monkeypatch):
     """kevlar_amd/csrc/kv_knobs.h: the library and its wrapper look at the environment through ONE table (kv_host.hip).  No source
     calls getenv() beside the registry; every name a source asks for is registered with a class and a description; a TUNING switch is
-    ignored unless KV_TUNING=1 -- a stray KV_* in a user's shell changes nothing -- and an EXPERIMENT switch (wrong results) is never
-    honoured by the product build."""
+    ignored unless KV_TUNING=1 -- a stray KV_* in a user's shell changes nothing -- and the phase-skip switches of old timing
+    experiments (wrong results) are gone: not registered, not listed, not asked for."""
     import glob
     from kevlar_amd import _lib
     import ctypes
@@ -907,7 +907,7 @@ def test_every_environment_switch_is_in_the_one_registry(monkeypatch):
     table = {}
     for line in buf.value.decode().splitlines():
         name, cls, doc = line.split('\t')
-        assert name not in table and cls in ('setting', 'tuning', 'experiment') and len(doc) > 10, line
+        assert name not in table and cls in ('setting', 'tuning') and len(doc) > 10, line
         table[name] = cls
     asked = set()
     csrc = os.path.join(ROOT, 'kevlar_amd', 'csrc')
@@ -937,17 +937,23 @@ def test_every_environment_switch_is_in_the_one_registry(monkeypatch):
     monkeypatch.setenv('KV_COUNT_PATH', 'atomic')
     monkeypatch.setenv('KV_TABLE_CACHE_GB', '1')
     monkeypatch.setenv('KV_SKM_DEBUG', '3')
-    assert _lib.knob('KV_COUNT_PATH') is None and _lib.knob('KV_TABLE_CACHE_GB') == '1' and _lib.knob('KV_SKM_DEBUG', 'no') == 'no'
-    assert sorted(_lib.knobs_active().split()) == ['KV_TABLE_CACHE_GB=1', 'ignored:KV_COUNT_PATH=atomic', 'ignored:KV_SKM_DEBUG=3']
+    assert _lib.knob('KV_COUNT_PATH') is None and _lib.knob('KV_TABLE_CACHE_GB') == '1'
+    assert sorted(_lib.knobs_active().split()) == ['KV_TABLE_CACHE_GB=1', 'ignored:KV_COUNT_PATH=atomic']
+    with pytest.raises(ValueError):
+        _lib.knob('KV_SKM_DEBUG')
     monkeypatch.setenv('KV_TUNING', '1')
     assert _lib.knob('KV_COUNT_PATH') == 'atomic'
-    assert _lib.knob('KV_SKM_DEBUG') is None, 'the product build must not honour the wrong-result switches'
-    assert sorted(_lib.knobs_active().split()) == ['KV_COUNT_PATH=atomic', 'KV_TABLE_CACHE_GB=1', 'ignored:KV_SKM_DEBUG=3']
+    assert sorted(_lib.knobs_active().split()) == ['KV_COUNT_PATH=atomic', 'KV_TABLE_CACHE_GB=1']
+    with pytest.raises(ValueError):
+        _lib.knob('KV_SKM_DEBUG')
     with pytest.raises(ValueError):
         _lib.knob('KV_NO_SUCH_SWITCH')
-    # no compile-time switch of the kernels changes results either: the timing hacks of round 5 live in scratch/patches/
+    # no compile-time switch of the kernels changes results or picks a variant either
     for path in glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h')):
-        assert 'SKM_HACK' not in open(path).read() and 'SKM_LANE_DISSECT' not in open(path).read(), path
+        text = open(path).read()
+        for word in ('SKM_HACK', 'SKM_LANE_DISSECT', 'KV_EXPERIMENTS', 'SKM_DBG', 'SKM_LINEAR_PROBE', 'SKM_LANE_FULL', 'SKM_LANE_BRANCHFREE',
+                     'KV_FASTMOD_NO_FP'):
+            assert word not in text, (path, word)
 
 
 def test_bench_clock_watch_never_raises_and_reports_nothing_without_a_card():
