@@ -322,6 +322,15 @@ int kv_novel_scan_set(const kv_reads *reads, int kind, int ksize, int nsamples, 
  * tag ~0) and come back as an ordinary kv_hits in (read, offset) order                            */
 int kv_hits_from_tagged(const void *d_tags, const void *d_abund, uint64_t n_total, uint64_t n_valid,
                         int nsamples, kv_hits **out);
+/* merge nruns runs of hits: run r is rows run_starts[r] .. run_starts[r + 1] - 1 (run_starts: HOST array of nruns + 1
+ * entries, the first 0) of d_read (u32), d_offset (u32) and d_abund (nsamples bytes per row); every run sorted by
+ * (read, offset), the runs pairwise disjoint in (read, offset) -- the hits of the bands of a banded scan: a k-mer
+ * occurrence is judged by one band.  Returns an ordinary hits handle, its list of discarded reads empty, with all rows in (read, offset)
+ * order, the pair compared as one 64-bit key: any offset, any read index.  Empty runs and nruns = 1 are legal; fewer than
+ * 2^32 rows in all.  A run that is not strictly ascending, or a pair that is in two runs, is the caller's error:
+ * KV_ERR_ARG, no handle.                                                                           */
+int kv_hits_merge(const void *d_read, const void *d_offset, const void *d_abund, const uint64_t *run_starts, int nruns,
+                  int nsamples, kv_hits **out);
 
 /* ---- partition: read graph connected components (kevlar/readgraph.py:43-84,104-137) --- */
 /* One annotation = one interesting k-mer occurrence (read index in `reads`, offset).

@@ -125,7 +125,8 @@ SIGNATURES = {
     'kv_novel_scan_distinct': (i32, [vpp, i32, vpp, i32, vp, u64, i32, i32, vp, vp, u64, u64p]),
     'kv_novel_scan_set': (i32, [vp, i32, i32, i32, vp, vp, u64, vpp]),
     'kv_hits_from_tagged': (i32, [vp, vp, u64, u64, i32, vpp]),
-    'kv_argsort_u64': (i32, [vp, u64, vp]),
+    'kv_hits_merge': (i32, [vp, vp, vp, u64p, i32, i32, vpp]),
+    'kv_argsort_u64':(i32, [vp, u64, vp]),
     'kv_argsort_rows': (i32, [vp, u64, ctypes.c_uint32, vp]),
     'kv_mex_plan_make': (i32, [i32, i32, u64, u32, i32, vp]),
     'kv_mex_plan_short': (i32, [vp]),

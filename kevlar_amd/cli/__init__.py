@@ -2,8 +2,8 @@
 
 Flag names, defaults and dispatch follow the reference (kevlar/cli/__init__.py:31-108 and
 kevlar/cli/{count,novel,filter,partition,unband,dist}.py); only the subcommands on the
-novel-k-mer path exist here.  `novel` has one extra switch, --ref-band-quirk (see
-kevlar_amd/novel.py).
+novel-k-mer path exist here.  `novel` has extra switches: --ref-band-quirk (see
+kevlar_amd/novel.py) and --all-bands / --distributed / --dist-backend (kevlar_amd/allbands.py).
 """
 import argparse
 import sys
@@ -54,6 +54,14 @@ def _novel(sub):
     b.add_argument('--band', type=int, default=None, metavar='I', help='band to process, 1..N')
     b.add_argument('--ref-band-quirk', action='store_true',
                    help='apply the reference\'s literal low-bits band test during the scan')
+    b.add_argument('--all-bands', action='store_true',
+                   help='run all N bands in this one command, one after the other, merge their hits on the GPU and write ONE '
+                   'output: what `kevlar unband` makes of the N per-band outputs, in input order')
+    b.add_argument('--distributed', action='store_true',
+                   help='with --all-bands: share the bands between the ranks of a torch.distributed launch, one GPU per rank '
+                   '(python -m torch.distributed.run --nproc-per-node W -m kevlar_amd novel ...); rank 0 writes the output')
+    b.add_argument('--dist-backend', choices=('nccl', 'gloo'), default=None,
+                   help='transport between the ranks: nccl (default when the node has a GPU per rank) or gloo (ranks sharing a GPU)')
     o = p.add_argument_group('Output settings')
     o.add_argument('-o', '--out', metavar='FILE', help='output augmented FASTQ (stdout)')
     o.add_argument('--save-case-counts', metavar='CT', nargs='+', help='save the case sketches')

@@ -16,6 +16,8 @@
 //                   k_route_tail pack the segments into that destination's contiguous send buffer.
 //   kv_hits_from_tagged  radix sort (rocPRIM) of the gathered (tag, abundances) hits back into the
 //                   (read, offset) order of the reference's output.
+//   kv_hits_merge   the bands' hits of one scan batch -- sorted, pairwise disjoint runs -- merged by rank on the full
+//                   (read, offset) key (k_merge_keys, k_merge_rank): `kevlar novel --all-bands`.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -332,6 +334,115 @@ struct DevBuf {
     hipError_t alloc(size_t n) { return kv_hip_malloc(&p, n ? n : 4); }
     template <typename T> T *as() { return (T *)p; }
 };
+
+// ---- kv_hits_merge: R runs of hits, each sorted by (read, offset) and pairwise disjoint, into one sorted list ------------------
+// Merge by rank: the place of a hit in the output is its index in its own run plus, for every other run, the number of
+// keys below its own -- a binary search over that run's keys.  A workgroup takes MERGE_TILE consecutive hits (of one run,
+// or of two where a tile straddles a boundary), MERGE_ITEMS per lane; its lanes first find, side by side, where the tile's
+// smallest and largest key fall in every run, and a lane's own searches then only walk that window: about as many keys as
+// the tile holds where the runs interleave evenly, ten steps through lines its neighbours touch as well.  Every search of
+// a (tile, run) takes the same number of steps -- the window's size decides, not the key -- so a lane's MERGE_ITEMS searches
+// advance together and their loads are in flight side by side.
+#define MERGE_THREADS 256
+#define MERGE_ITEMS 4
+#define MERGE_TILE (MERGE_THREADS * MERGE_ITEMS)
+#define MERGE_RUNS 64            // runs whose windows are kept in LDS at a time
+
+__global__ void k_merge_keys(const uint32_t *read, const uint32_t *offset, uint64_t n, unsigned long long *keys)
+{
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        keys[i] = ((unsigned long long)read[i] << 32) | offset[i];
+}
+
+// first index in [lo, hi) whose key is not below `key` (hi if there is none)
+__device__ __forceinline__ uint64_t merge_lower_bound(const unsigned long long *keys, uint64_t lo, uint64_t hi, unsigned long long key)
+{
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// starts[R + 1]: run r is keys[starts[r] : starts[r + 1]].  *bad becomes non-zero if a run is not strictly ascending
+// (bit 0) or a key is met in two runs (bit 1: two hits would be ranked to one slot).
+__global__ void __launch_bounds__(MERGE_THREADS) k_merge_rank(const unsigned long long *keys, const uint8_t *abund, const uint64_t *starts, int R,
+                                                              uint64_t n, int S, uint32_t *out_read, uint32_t *out_off, uint8_t *out_abund,
+                                                              uint32_t *bad)
+{
+    __shared__ unsigned long long s_min, s_max;
+    __shared__ uint64_t s_lo[MERGE_RUNS], s_hi[MERGE_RUNS];
+    const uint64_t n_tiles = (n + MERGE_TILE - 1) / MERGE_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        if (threadIdx.x == 0) { s_min = ~0ull; s_max = 0ull; }
+        __syncthreads();
+        unsigned long long key[MERGE_ITEMS];
+        uint64_t dest[MERGE_ITEMS];
+        int mine[MERGE_ITEMS];      // the run of the hit: the last r with starts[r] <= i (runs may be empty)
+        unsigned long long kmin = ~0ull, kmax = 0ull;
+#pragma unroll
+        for (int m = 0; m < MERGE_ITEMS; ++m) {
+            const uint64_t i = tile * MERGE_TILE + (uint64_t)m * MERGE_THREADS + threadIdx.x;
+            key[m] = 0; dest[m] = 0; mine[m] = -1;
+            if (i < n) {
+                key[m] = keys[i];
+                int lo = 0, hi = R;     // starts[lo] <= i < starts[hi]
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (starts[mid] <= i) lo = mid; else hi = mid;
+                }
+                mine[m] = lo;
+                dest[m] = i - starts[lo];
+                if (i > starts[lo] && keys[i - 1] >= key[m]) atomicOr(bad, 1u);
+                kmin = min(kmin, key[m]);
+                kmax = max(kmax, key[m]);
+            }
+        }
+        if (kmin <= kmax) { atomicMin(&s_min, kmin); atomicMax(&s_max, kmax); }
+        __syncthreads();
+        const unsigned long long tmin = s_min, tmax = s_max;
+        for (int r0 = 0; r0 < R; r0 += MERGE_RUNS) {
+            const int nr = min(MERGE_RUNS, R - r0);
+            for (int t = threadIdx.x; t < 2 * nr; t += MERGE_THREADS) {    // the tile's window in run r0 + t / 2: one end per lane
+                const int r = r0 + (t >> 1);
+                const uint64_t at = merge_lower_bound(keys, starts[r], starts[r + 1], (t & 1) ? tmax : tmin);
+                if (t & 1) s_hi[t >> 1] = at; else s_lo[t >> 1] = at;
+            }
+            __syncthreads();
+            for (int q = 0; q < nr; ++q) {
+                const int r = r0 + q;
+                const uint64_t end = starts[r + 1];
+                const uint64_t lo = s_lo[q];
+                uint64_t len = s_hi[q] > lo ? s_hi[q] - lo : 0;       // (a window is never negative for sorted runs; for others: stay in bounds)
+                uint64_t at[MERGE_ITEMS];
+#pragma unroll
+                for (int m = 0; m < MERGE_ITEMS; ++m) at[m] = lo;
+                while (len > 1) {               // branch-free lower bound, the same steps for every hit of the tile
+                    const uint64_t half = len >> 1;
+#pragma unroll
+                    for (int m = 0; m < MERGE_ITEMS; ++m) at[m] += keys[at[m] + half - 1] < key[m] ? half : 0;
+                    len -= half;
+                }
+#pragma unroll
+                for (int m = 0; m < MERGE_ITEMS; ++m) {
+                    if (len == 1 && keys[at[m]] < key[m]) ++at[m];
+                    if (mine[m] < 0 || mine[m] == r) continue;
+                    if (at[m] < end && keys[at[m]] == key[m]) atomicOr(bad, 2u);
+                    dest[m] += at[m] - starts[r];
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int m = 0; m < MERGE_ITEMS; ++m) {
+            if (mine[m] < 0) continue;          // dest < n whatever the input: every term is at most its run's length, the own one less
+            const uint64_t i = tile * MERGE_TILE + (uint64_t)m * MERGE_THREADS + threadIdx.x;
+            out_read[dest[m]] = (uint32_t)(key[m] >> 32);
+            out_off[dest[m]] = (uint32_t)key[m];
+            for (int c = 0; c < S; ++c) out_abund[dest[m] * (uint64_t)S + c] = abund[i * (uint64_t)S + c];
+        }
+    }
+}
 
 }  // namespace
 
@@ -834,5 +945,68 @@ extern "C" int kv_hits_from_tagged(const void *d_tags, const void *d_abund, uint
         kv_set_error("kv_hits_from_tagged failed: %s", hipGetErrorString(e));
         return KV_ERR_HIP;
     }
+    return KV_OK;
+}
+
+// R runs of hits on the device -- run r is rows run_starts[r] .. run_starts[r + 1] of d_read / d_offset / d_abund, sorted by
+// (read, offset), the runs pairwise disjoint -- merged into one ordinary kv_hits in (read, offset) order.  The key is the
+// full (read u32, offset u32) pair: no limit on the offset, no host path.
+extern "C" int kv_hits_merge(const void *d_read, const void *d_offset, const void *d_abund, const uint64_t *run_starts, int nruns,
+                             int nsamples, kv_hits **out)
+{
+    KV_REQUIRE(out && run_starts && nruns >= 1 && nsamples >= 1 && nsamples <= KV_MAX_SAMPLES, KV_ERR_ARG, "kv_hits_merge: bad argument");
+    KV_REQUIRE(run_starts[0] == 0, KV_ERR_ARG, "kv_hits_merge: the first run starts at row 0");
+    for (int r = 0; r < nruns; ++r)
+        KV_REQUIRE(run_starts[r] <= run_starts[r + 1], KV_ERR_ARG, "kv_hits_merge: run %d ends before it starts", r);
+    const uint64_t n = run_starts[nruns];
+    KV_REQUIRE(n == 0 || (d_read && d_offset && d_abund), KV_ERR_ARG, "kv_hits_merge: null buffer");
+    KV_REQUIRE(n < (1ull << 32), KV_ERR_ARG, "kv_hits_merge: too many hits");
+    *out = nullptr;
+    kv_hits *hits = new kv_hits();
+    hits->nsamples = nsamples;
+    if (n == 0) { *out = hits; return KV_OK; }
+    hipStream_t st = kv_stream();
+    DevBuf keys, starts, bad, o_read, o_off, o_abund;
+    KvReadback back;
+    const uint32_t *flag = nullptr;
+    hipError_t e = keys.alloc(n * 8);
+    if (e == hipSuccess) e = starts.alloc(((size_t)nruns + 1) * 8);
+    if (e == hipSuccess) e = bad.alloc(4);
+    if (e == hipSuccess) e = o_read.alloc(n * 4);
+    if (e == hipSuccess) e = o_off.alloc(n * 4);
+    if (e == hipSuccess) e = o_abund.alloc(n * (uint64_t)nsamples);
+    if (e == hipSuccess) e = hipMemcpyAsync(starts.p, run_starts, ((size_t)nruns + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(bad.p, 0, 4, st);
+    if (e == hipSuccess) {
+        KvProfScope prof("merge_hits");
+        const uint64_t n_tiles = (n + MERGE_TILE - 1) / MERGE_TILE;
+        const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, 8192);
+        hipLaunchKernelGGL(k_merge_keys, dim3(grid), dim3(MERGE_THREADS), 0, st, (const uint32_t *)d_read, (const uint32_t *)d_offset, n,
+                           keys.as<unsigned long long>());
+        hipLaunchKernelGGL(k_merge_rank, dim3(grid), dim3(MERGE_THREADS), 0, st, keys.as<unsigned long long>(), (const uint8_t *)d_abund,
+                           starts.as<uint64_t>(), nruns, n, nsamples, o_read.as<uint32_t>(), o_off.as<uint32_t>(), o_abund.as<uint8_t>(),
+                           bad.as<uint32_t>());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) flag = back.add(bad.as<uint32_t>(), 1, st, &e);
+    if (e == hipSuccess) e = hits->read.resize(n);
+    if (e == hipSuccess) e = hits->offset.resize(n);
+    if (e == hipSuccess) e = hits->abund.resize(n * (uint64_t)nsamples);
+    if (e == hipSuccess) e = hipMemcpyAsync(hits->read.data(), o_read.p, n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hits->offset.data(), o_off.p, n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hits->abund.data(), o_abund.p, n * (uint64_t)nsamples, hipMemcpyDeviceToHost, st);
+    const hipError_t waited = hipStreamSynchronize(st);        // (also after a failed enqueue: the run starts leave a caller's array)
+    if (e == hipSuccess) e = waited;
+    if (e != hipSuccess) {
+        delete hits;
+        kv_set_error("kv_hits_merge failed: %s", hipGetErrorString(e));
+        return KV_ERR_HIP;
+    }
+    if (*flag) {
+        delete hits;
+        kv_set_error("kv_hits_merge: %s", (*flag & 1u) ? "a run is not sorted by (read, offset)" : "a (read, offset) pair is in two runs");
+        return KV_ERR_ARG;
+    }
+    *out = hits;
     return KV_OK;
 }

@@ -1080,6 +1080,18 @@ def hits_from_tagged(tags_ptr, abund_ptr, n_total, n_valid, nsamples):
     return r, o, a
 
 
+def hits_merge(read_ptr, offset_ptr, abund_ptr, run_starts, nsamples):
+    """Merge runs of hits in HBM -- run r is rows run_starts[r]:run_starts[r + 1] of the u32 read and offset columns and the
+    [n, nsamples] abundance bytes, each run sorted by (read, offset), the runs disjoint (the bands of a banded scan) -- into
+    one list in (read, offset) order (kv_hits_merge); returns (read, offset, abund, discarded) as novel_scan does, the
+    discarded list empty.  Raises KvArgError if a run is not sorted or a (read, offset) pair is in two runs."""
+    starts = np.ascontiguousarray(run_starts, dtype=np.uint64)
+    hits = ctypes.c_void_p()
+    check(_lib.load().kv_hits_merge(ctypes.c_void_p(read_ptr), ctypes.c_void_p(offset_ptr), ctypes.c_void_p(abund_ptr), _u64p(starts),
+                                    len(starts) - 1, int(nsamples), ctypes.byref(hits)))
+    return _hits_arrays(hits, nsamples)
+
+
 class _HitsHandle(object):
     def __init__(self, handle):
         self._h = handle

@@ -289,15 +289,10 @@ def _load_side_by_side(args, band, keep=None):
             kevlar_amd.plog('[kevlar::novel] Case samples loaded in {:.2f} sec'.format(took['case']))
 
 
-def main(args):
-    if (not args.num_bands) != (not args.band):
-        raise ValueError('Must specify --num-bands and --band together')
-    band = args.band - 1 if args.band else None
-    clock = kevlar_amd.Timer()
-    for key in (None, 'loadall', 'loadctrl'):
+def _load(args, band, kept, clock):
+    """(controls, cases): the sketches of one run -- of one band of it -- loaded or counted, with the log lines of the reference"""
+    for key in ('loadall', 'loadctrl'):
         clock.start(key)
-    # a case sample that was counted as one batch is scanned from that batch (no second pass over its file)
-    kept = {} if not _lib.knob('KV_NOVEL_REREAD') else None
     if not _side_by_side((args.control or []) + (args.case or [])) or args.control_counts or args.case_counts:
         kevlar_amd.plog('[kevlar::novel] Loading control samples')
         controls = load_samples(args.control_counts, args.control, args.ksize, args.memory, args.max_fpr, args.num_bands, band,
@@ -312,6 +307,21 @@ def main(args):
         controls, cases = _load_side_by_side(args, band, keep=kept)
         clock.stop('loadctrl')
     kevlar_amd.plog('[kevlar::novel] All samples loaded in {:.2f} sec'.format(clock.stop('loadall')))
+    return controls, cases
+
+
+def main(args):
+    if getattr(args, 'all_bands', False) or getattr(args, 'distributed', False):
+        from kevlar_amd import allbands            # every band in this one run, merged on the device
+        return allbands.main(args)
+    if (not args.num_bands) != (not args.band):
+        raise ValueError('Must specify --num-bands and --band together')
+    band = args.band - 1 if args.band else None
+    clock = kevlar_amd.Timer()
+    clock.start()
+    # a case sample that was counted as one batch is scanned from that batch (no second pass over its file)
+    kept = {} if not _lib.knob('KV_NOVEL_REREAD') else None
+    controls, cases = _load(args, band, kept, clock)
 
     clock.start('iter')
     kevlar_amd.plog('[kevlar::novel]', 'Iterating over reads from {:d} case sample(s)'.format(len(args.case)))
