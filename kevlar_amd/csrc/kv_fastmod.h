@@ -10,6 +10,8 @@
 //    correction.  12 instructions against the 30 of the 64 x 64 -> 128-bit Barrett form, four times per distinct k-mer in
 //    the count kernel and once per probe in the scan.
 //  * otherwise: Barrett with magic = floor((2^64 - 1) / size); the quotient is at most 2 short.
+// And a third for a caller that knows more: kv_fastmod32, the FP64 form with a 32-bit remainder, for 2^16 <= size < 2^31
+// (the drain of the super-k-mer count with four such tables, k_skm_count's fast4 branch).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -71,5 +73,35 @@ KVF_HD uint64_t fastmod(uint64_t h, uint64_t size, uint64_t magic)
     uint64_t r = h - q * size;
     r -= r >= size ? size : 0;       // twice, branch-free: the quotient is at most 2 short
     r -= r >= size ? size : 0;
+    return r;
+}
+
+// the hash as a double, rounded once: what the FP64 form multiplies (a k-mer's hash goes into four tables: convert once)
+KVF_HD double kv_fastmod_hd(uint64_t h)
+{
+    return fma((double)(uint32_t)(h >> 32), 4294967296.0, (double)(uint32_t)h);
+}
+
+// h % size for 2^16 <= size < 2^31 with the remainder in 32 bits; hd = kv_fastmod_hd(h), magic = kv_fastmod_magic(size).
+// The quotient estimate is h / size rounded to nearest, give or take the 0.07 of the three roundings (see above): floor(h / size) or
+// one more, so h - q size lies in (-size, size) -- in about [-size / 2, size / 2] -- and its low word is the remainder, or the
+// remainder + 2^32 - size; size < 2^31 makes bit 31 tell the two apart.
+KVF_HD uint32_t kv_fastmod32(uint64_t h, double hd, uint32_t size, uint64_t magic)
+{
+    double inv;
+#if defined(__HIP_DEVICE_COMPILE__)
+    inv = __longlong_as_double((long long)magic);
+#else
+    memcpy(&inv, &magic, 8);
+#endif
+    const double q = fma(hd, inv, 4503599627370496.0);
+    uint64_t qb;
+#if defined(__HIP_DEVICE_COMPILE__)
+    qb = (uint64_t)__double_as_longlong(q);
+#else
+    memcpy(&qb, &q, 8);
+#endif
+    uint32_t r = (uint32_t)h - (uint32_t)qb * size;
+    r += (uint32_t)((int32_t)r >> 31) & size;
     return r;
 }

@@ -1436,16 +1436,10 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
                 const bool pass = !f.use_band || (h >= f.band_lo && h < f.band_hi);
                 added = pass ? seen : 0u;
                 if (pass) {
-                    const double hd = fma((double)(uint32_t)(h >> 32), 4294967296.0, (double)(uint32_t)h);
+                    const double hd = kv_fastmod_hd(h);
                     uint32_t bin[4];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const double q = fma(hd, __longlong_as_double((long long)g.tmagic[t]), 4503599627370496.0);
-                        const uint32_t psz = (uint32_t)g.tsize[t];
-                        uint32_t r = (uint32_t)h - (uint32_t)__double_as_longlong(q) * psz;
-                        r += (uint32_t)((int32_t)r >> 31) & psz;
-                        bin[t] = r;
-                    }
+                    for (int t = 0; t < 4; ++t) bin[t] = kv_fastmod32(h, hd, (uint32_t)g.tsize[t], g.tmagic[t]);
                     uint32_t left = min(seen, 255u);
                     const uint32_t omask = (1u << g.sbits) - 1u, stride32 = (uint32_t)seg_stride;
                     while (left) {

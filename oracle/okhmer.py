@@ -232,7 +232,8 @@ class _Sketch(object):
     def table_bytes(self, i):
         n = ctypes.c_uint64()
         p = lib.kvo_table_bytes(self._h, i, ctypes.byref(n))
-        return ctypes.string_at(p, n.value)
+        # (not ctypes.string_at: its length is a C int, and a table of more than 2^31 - 1 bytes came back as a SystemError)
+        return bytes((ctypes.c_uint8 * n.value).from_address(ctypes.addressof(p.contents)))
 
     # -- hashing
     def hash(self, kmer):

@@ -57,4 +57,11 @@ void h_fastmod(const uint64_t *h, uint64_t n, uint64_t size, uint64_t *out)
     const uint64_t magic = kv_fastmod_magic(size);
     for (uint64_t i = 0; i < n; ++i) out[i] = fastmod(h[i], size, magic);
 }
+// out[i] = kv_fastmod32(h[i], size): the 32-bit remainder of k_skm_count's fast4 branch (2^16 <= size < 2^31)
+void h_fastmod32(const uint64_t *h, uint64_t n, uint64_t size, uint64_t *out)
+{
+    const uint64_t magic = kv_fastmod_magic(size);
+    for (uint64_t i = 0; i < n; ++i) out[i] = kv_fastmod32(h[i], kv_fastmod_hd(h[i]), (uint32_t)size, magic);
+}
+int h_fastmod_fp(uint64_t size) { return kv_fastmod_fp(size) ? 1 : 0; }
 }

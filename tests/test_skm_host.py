@@ -195,3 +195,39 @@ def test_fastmod_is_the_remainder(lib):
         out = np.empty_like(h)
         lib.h_fastmod(h.ctypes.data, len(h), size, out.ctypes.data)
         assert np.array_equal(out, h % np.uint64(size)), size
+
+
+FAST4_SIZES = [65536, 65537, 1073741789, 1073741827, 1999999973, 2147483629, 2147483647]
+
+
+def test_fast4_remainder_is_the_remainder(lib):
+    """kv_fastmod32, the 32-bit remainder the super-k-mer count takes when all four tables have fewer than 2^31 bins (k_skm_count's
+    fast4 branch: the sign of h - q size sits in bit 31 of its low word), at both ends of its range, on both sides of 2^30, at
+    bench.py's cfg4-band size and at random sizes, for the hashes of test_fastmod_is_the_remainder"""
+    import numpy as np
+    from bigtables_common import crafted_hashes
+    lib.h_fastmod32.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+    rng = np.random.default_rng(12)
+    sizes = FAST4_SIZES + [int(x) for x in rng.integers(65536, 2**31, 40, dtype=np.uint64)]
+    for size in sizes:
+        assert 65536 <= size < 2**31
+        h = crafted_hashes(size, rng)
+        out = np.empty_like(h)
+        lib.h_fastmod32(h.ctypes.data, len(h), size, out.ctypes.data)
+        want = h % np.uint64(size)
+        bad = np.flatnonzero(out != want)
+        assert len(bad) == 0, 'size {}: hash {} gives {}, the remainder is {}'.format(size, int(h[bad[0]]), int(out[bad[0]]), int(want[bad[0]]))
+
+
+def test_fastmod_fp_range(lib):
+    """the FP64 form is chosen exactly for 2^16 <= size < 2^32"""
+    import numpy as np
+    lib.h_fastmod_fp.argtypes = [ctypes.c_uint64]
+    rng = np.random.default_rng(13)
+    inside = [65536, 65537, 2**31 - 1, 2**31, 2**31 + 11, 2**32 - 5, 2**32 - 1] + [int(x) for x in rng.integers(65536, 2**32, 200, dtype=np.uint64)]
+    outside = [1, 2, 97, 65521, 65535, 2**32, 2**32 + 15, 5999999989, 2**40, 2**63 + 9, 2**64 - 1] + [int(x) for x in rng.integers(1, 65536, 100, dtype=np.uint64)] + \
+        [int(x) for x in rng.integers(2**32, 2**64, 200, dtype=np.uint64)]
+    for size in inside:
+        assert lib.h_fastmod_fp(size) == 1, size
+    for size in outside:
+        assert lib.h_fastmod_fp(size) == 0, size
