@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from kevlar_amd import _lib, khmer
-from kevlar_amd.sequence import KmerOfInterest, Record
+from kevlar_amd.sequence import PLAIN_BASES, KmerOfInterest, Record
 
 
 def _host_cores():
@@ -229,6 +229,21 @@ class AnnotatedReads(object):
                 ctypes.cast(ctypes.c_char_p(self.seqs), ctypes.c_void_p), offs.ctypes.data_as(ctypes.c_void_p), self.n, flags.ctypes.data_as(ctypes.c_void_p)))
             self._made['odd'] = np.flatnonzero(flags)
         return self._made['odd']
+
+    def kmer_texts(self, which=None):
+        """the annotated k-mers as text, in stream order (which: indices of annotations; None: all).  One Python string per
+        annotation: for the host path of the read graph only, whose streams are small"""
+        which = range(len(self)) if which is None else which
+        starts = self.seq_offs[self.read].astype(np.int64) + self.offset.astype(np.int64)
+        return [self.seqs[int(starts[j]):int(starts[j]) + self.ksize].decode('latin-1') for j in which]
+
+    def has_odd_kmers(self):
+        """does any ANNOTATED k-mer hold a character outside ACGT?  (only the reads of odd_reads() are looked at)"""
+        odd = self.odd_reads()
+        if not len(odd) or not len(self):
+            return False
+        which = np.concatenate([np.arange(int(self.first[i]), int(self.first[i + 1]), dtype=np.int64) for i in odd.tolist()])
+        return any(not PLAIN_BASES.issuperset(kmer) for kmer in self.kmer_texts(which.tolist()))
 
     def hashes(self, sketch):
         """`sketch`'s hash of every annotated k-mer, in stream order.  K-mers of reads with characters outside ACGT

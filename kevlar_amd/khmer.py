@@ -1126,6 +1126,9 @@ class _Owned(np.ndarray):
         self._owner = getattr(obj, '_owner', None)
 
 
+READGRAPH_MAX_K = 128      # 32 bases per word of the read graph's key: 32 * KEY_WORDS of csrc/kv_graph.hip (held together by tests/test_downstream_reference.py)
+
+
 def readgraph_components(batch, ksize, ann_read, ann_offset, node_of_read, n_nodes, minabund=0,
                          maxabund=0, want_edges=False):
     """labels[node] = smallest node id of its connected component (kv_readgraph_components)."""

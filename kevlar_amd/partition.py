@@ -278,8 +278,15 @@ def partition_file(infile, minabund=None, maxabund=None, dedup=True):
     def component_of(node_of_read, n_nodes):
         mode = ('[kevlar::partition]', 'Building read graph in relaxed mode')
         with _phase(timer, 'buildgraph', mode, 'Graph built in {:.2f} sec'):
-            labels = khmer.readgraph_components(ann.batch, ann.ksize or 1, ann.read, ann.offset, node_of_read, n_nodes,
-                                                minabund or 0, maxabund or 0)
+            if ann.has_odd_kmers():
+                # k-mers the packed reads cannot hold: keyed by their text on the host, as the reference keys them
+                from kevlar_amd import readgraph
+                readgraph.check_ksize(ann.ksize)
+                kevlar_amd.plog('[kevlar::partition]', readgraph.HOST_NOTE)
+                labels = readgraph.text_components(ann.kmer_texts(), node_of_read[ann.read], n_nodes, minabund or 0, maxabund or 0)
+            else:
+                labels = khmer.readgraph_components(ann.batch, ann.ksize or 1, ann.read, ann.offset, node_of_read, n_nodes,
+                                                    minabund or 0, maxabund or 0)
             ann.close()
         return labels
     if ann.n:

@@ -10,6 +10,50 @@ import numpy as np
 
 import kevlar_amd
 from kevlar_amd import khmer
+from kevlar_amd.sequence import PLAIN_BASES
+
+
+HOST_NOTE = 'interesting k-mers with characters outside ACGT: read graph built on the host'
+
+
+def text_components(kmers, ann_node, n_nodes, minabund=0, maxabund=0, want_edges=False):
+    """khmer.readgraph_components() for annotated k-mers given as TEXT (one per annotation, with the node that holds it), on the
+    host: the reference keys the graph by revcommin() of the k-mer's text (kevlar/readgraph.py:71-73), which the 2-bit key of the
+    device cannot follow once a k-mer holds a character outside upper-case ACGT -- there N is packed as A and lower case as upper
+    case, while in the text N stays N and a lower-case k-mer's key is always its (upper-case) reverse complement.  Streams with
+    such annotations do not come out of `novel` (its scan skips these reads) and are small.  Returns what the device returns:
+    labels[node] = smallest node id of its connected component, and with want_edges the number of distinct node pairs that share
+    a retained k-mer."""
+    holders = {}
+    for kmer, node in zip(kmers, ann_node):
+        holders.setdefault(kevlar_amd.revcommin(kmer), set()).add(int(node))
+    parent = list(range(n_nodes))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    edges = set()
+    for nodes in holders.values():
+        n = len(nodes)
+        if (minabund and n < minabund) or (maxabund and n > maxabund):
+            continue
+        nodes = sorted(nodes)
+        for other in nodes[1:]:
+            a, b = find(nodes[0]), find(other)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+        if want_edges:
+            edges.update((a, b) for i, a in enumerate(nodes) for b in nodes[i + 1:])
+    labels = np.array([find(i) for i in range(n_nodes)], dtype=np.uint32)
+    return (labels, len(edges)) if want_edges else labels
+
+
+def check_ksize(ksize):
+    """the bound of the device's key (kv_readgraph_components: khmer.READGRAPH_MAX_K), for the streams that never reach it"""
+    if ksize > khmer.READGRAPH_MAX_K:
+        raise ValueError('partition supports k <= {:d} (got {:d})'.format(khmer.READGRAPH_MAX_K, ksize))
 
 
 class ReadGraph(object):
@@ -127,6 +171,18 @@ class ReadGraph(object):
         if not reads:
             self._labels, self._nedges = np.zeros(0, dtype=np.uint32), 0
             return
+        odd = [r for r in reads if r.annotations and not PLAIN_BASES.issuperset(r.sequence)]
+        if any(not PLAIN_BASES.issuperset(r.ikmerseq(ikmer)) for r in odd for ikmer in r.annotations):
+            check_ksize(ksize)
+            kevlar_amd.plog('[kevlar::partition]', HOST_NOTE)
+            kmers = [r.ikmerseq(ikmer) for r in reads for ikmer in r.annotations]
+            result = text_components(kmers, node_of_read[np.asarray(ann_read, dtype=np.int64)], len(names), self._minabund or 0,
+                                     self._maxabund or 0, want_edges=want_edges)
+            if want_edges:
+                self._labels, self._nedges = result
+            else:
+                self._labels = result
+            return
         batch = khmer.ReadBatch([r.sequence for r in reads])
         result = khmer.readgraph_components(
             batch, ksize or 1, np.asarray(ann_read, dtype=np.uint32), np.asarray(ann_off, dtype=np.uint32),
@@ -165,13 +221,15 @@ class ReadGraph(object):
 
     # ---- kevlar/readgraph.py:127-161 ------------------------------------------------------
     def partitions(self, dedup=True, minabund=None, maxabund=None, abundfilt=False):
-        """Connected components, largest first (ties: by sorted read names, descending)."""
+        """Connected components, largest first (ties: by sorted read names, descending).  With dedup a ReadGraph per component
+        (its nodes in name order); without, the component's names as a sorted LIST -- the reference yields the set itself, whose
+        order changes from run to run, and so did this method until partition()'s output had to equal the file path's."""
         ccs = sorted(self.connected_components(), reverse=True, key=lambda c: (len(c), sorted(c)))
         for cc in ccs:
             if len(cc) == 1 and next(iter(cc)) in self.readnames:
                 continue   # unassembled input read
             if not dedup:
-                yield cc
+                yield sorted(cc)       # (a set in the reference: name order, as with dedup and as the array path writes them)
                 continue
             # The reference iterates a Python set here, so which duplicate survives depends on
             # PYTHONHASHSEED; sorted order makes it deterministic (SURVEY.md 8(a) row P3).

@@ -13,6 +13,7 @@ KmerOfInterest = namedtuple('KmerOfInterest', 'ksize offset abund')
 
 _COMPLEMENT = str.maketrans('ATUGCYRSWKMBDHVNatugcyrswkmbdhvn',
                             'TAACGRYSWMKVHDBNTAACGRYSWMKVHDBN')
+PLAIN_BASES = frozenset('ACGT')       # what the 2-bit packed reads hold as it stands; anything else (N, lower case) is kept as text only
 _MATE_RE = re.compile(r'^#mateseq=(\S+)#\n$')
 
 
