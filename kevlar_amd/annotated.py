@@ -276,7 +276,7 @@ class AnnotatedReads(object):
         threads and writes the file itself (kv_format_records_fd: no text buffer of the output's size, no copy into a Python
         object); otherwise format() + write()."""
         fd = sink.raw_fd() if hasattr(sink, 'raw_fd') else None
-        if fd is None or _lib.knob('KV_FORMAT_FD') == '0':
+        if fd is None:
             sink.write(self.format(reads, keep, case_abund, suffixes, regrouped, suffix_blob))
             return
         self.format(reads, keep, case_abund, suffixes, regrouped, suffix_blob, _fd=fd)

@@ -924,8 +924,7 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     // beyond 2^30 bins.  Fewer buckets = fewer distinct lines per stage-A store instruction (that stage is bound by
     // L2 write requests): measured per 525 M k-mers into 5e8-bin tables, A/B/C = 10.5/5.0/4.0 ms with 32 buckets,
     // 8.7/4.9/4.0 with 20, 8.3/6.1/4.0 with 16 (F = 478: rings too big for three workgroups).
-    int cmax = maxsl <= 32u * BIN_MAX_F ? (int)std::min<uint32_t>(32u, std::max<uint32_t>(4u, (maxsl + 383u) / 384u)) : BIN_C;
-    if (const char *e = kv_knob("KV_BIN_C")) cmax = std::max(1, std::min<int>(BIN_C, atoi(e)));      // experiments: coarse buckets per table
+    const int cmax = maxsl <= 32u * BIN_MAX_F ? (int)std::min<uint32_t>(32u, std::max<uint32_t>(4u, (maxsl + 383u) / 384u)) : BIN_C;
     plan->cmax = cmax;
     g.F = (int)((maxsl + (uint32_t)cmax - 1) / (uint32_t)cmax);
     g.C = (int)((maxsl + (uint32_t)g.F - 1) / (uint32_t)g.F);
@@ -975,7 +974,7 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     g.spill = (unsigned long long *)base; base += b_spill;
     g.ctr = (unsigned long long *)base;
     {
-        bool ok = g.T == 4 && ns * g.nwgA * g.cap1 < (1ull << 32) && !(kv_knob("KV_BIN_FAST4") && atoi(kv_knob("KV_BIN_FAST4")) == 0);
+        bool ok = g.T == 4 && ns * g.nwgA * g.cap1 < (1ull << 32);
         for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) {
             g.tmagic[t] = kv_fastmod_magic(s->h.size[t]);
             ok = ok && kv_fastmod_fp(s->h.size[t]) && s->h.size[t] < (1ull << 31);
@@ -1086,7 +1085,7 @@ int kv_consume_binned(kv_sketch *s, const kv_reads *reads, const uint64_t *d_lis
         KvProfScope prof("k_bin_hash_direct");
         const unsigned grid = g.nwgA;
         const int k = s->h.ksize;
-        const int nw = (s->h.hashfam == HF_MURMUR && !kv_knob("KV_NO_ROLL")) ? (k <= 32 ? 8 : (k <= 64 ? 16 : 0)) : 0;
+        const int nw = s->h.hashfam == HF_MURMUR ? (k <= 32 ? 8 : (k <= 64 ? 16 : 0)) : 0;
 #define KV_LAUNCH_BIN_DIRECT(THREADS_, NW_)                                                                       \
         do {                                                                                                      \
             ensure_dynamic_lds(k_bin_hash_direct<THREADS_, NW_>, (size_t)g.tile_lds);                             \

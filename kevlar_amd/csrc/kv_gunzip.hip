@@ -467,7 +467,7 @@ __device__ __forceinline__ bool gz_met_start(GunzipShared<RBITS> &sh, const unsi
 }
 
 template <int RBITS, bool EXACT>      // EXACT: the segment has stretches that begin inside a block (the target is looked for between symbols too)
-__global__ __launch_bounds__(64, (RBITS <= 10 ? 8 : RBITS == 11 ? 6 : RBITS == 12 ? 3 : RBITS == 13 ? 2 : 1)) void k_gz_decode(const uint8_t *__restrict__ comp, uint64_t n_bytes, int is_file_end, const GzJob *__restrict__ jobs,
+__global__ __launch_bounds__(64, 8) void k_gz_decode(const uint8_t *__restrict__ comp, uint64_t n_bytes, int is_file_end, const GzJob *__restrict__ jobs,
                                                       uint32_t n_jobs, const unsigned long long *__restrict__ starts, const unsigned long long *__restrict__ headers,
                                                       uint64_t terminal_bit, uint16_t *syms,
                                                       GzResult *__restrict__ results, unsigned long long *ctr)
@@ -975,18 +975,9 @@ static int gz_run_jobs(KvGunzip *g, const uint8_t *d_comp, uint64_t n_bytes, boo
         KvProfScope prof("k_gz_decode");
         // the LDS window sets how many stretches a CU holds (1 K symbols: 32 = 8 waves per SIMD); a match that reaches further
         // back reads the symbols the wave itself stored to HBM, behind a workgroup-scope release
-        const char *rb = kv_knob("KV_GUNZIP_RING_BITS");
-        const int bits = rb ? atoi(rb) : 10;
-        const int per_cu = bits >= 14 ? 4 : bits == 13 ? 8 : bits == 12 ? 12 : bits == 11 ? 24 : 32;
-        const unsigned grid = (unsigned)std::min<uint64_t>(n, (uint64_t)per_cu * (uint64_t)kv_device_cus());
-#define KV_LAUNCH_GZ(B_, E_) hipLaunchKernelGGL((k_gz_decode<B_, E_>), dim3(grid), dim3(64), 0, st, d_comp, n_bytes, is_file_end ? 1 : 0, (const GzJob *)d_jobs, (uint32_t)n, d_starts, d_headers, terminal_bit, d_syms, d_results, d_ctr)
-        if (exact) KV_LAUNCH_GZ(10, true);
-        else if (bits >= 14) KV_LAUNCH_GZ(14, false);
-        else if (bits == 13) KV_LAUNCH_GZ(13, false);
-        else if (bits == 12) KV_LAUNCH_GZ(12, false);
-        else if (bits == 11) KV_LAUNCH_GZ(11, false);
-        else KV_LAUNCH_GZ(10, false);
-#undef KV_LAUNCH_GZ
+        const unsigned grid = (unsigned)std::min<uint64_t>(n, 32ull * (uint64_t)kv_device_cus());
+        hipLaunchKernelGGL((exact ? k_gz_decode<10, true> : k_gz_decode<10, false>), dim3(grid), dim3(64), 0, st, d_comp, n_bytes, is_file_end ? 1 : 0, (const GzJob *)d_jobs,
+                           (uint32_t)n, d_starts, d_headers, terminal_bit, d_syms, d_results, d_ctr);
     }
     KV_HIP(hipGetLastError());
     KV_HIP(hipMemcpyAsync(results, d_results, n * sizeof(GzResult), hipMemcpyDeviceToHost, st));
@@ -1062,16 +1053,15 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     }                                                  // (none before the end of the file: the last stretch runs to the end)
     const uint64_t stop_rel = have_terminal ? starts.back() : ~0ull;             // reaching it ends the segment
     // ---- long stretches are cut: symbol boundaries inside their first block, found by letting 64 decoders per cut fall
-    // into step (k_gz_sync).  KV_GUNZIP_SPLIT_KB: compressed bytes a piece should have (0: no cutting)
+    // into step (k_gz_sync)
     std::vector<uint64_t> headers(starts);              // headers[i]: the block header stretch i takes its codes from
     {
-        const char *sk = kv_knob("KV_GUNZIP_SPLIT_KB");
-        // default: only when the block starts alone leave the device short of work (fewer than 24 stretches per CU), and
+        // only when the block starts alone leave the device short of work (fewer than 24 stretches per CU), and
         // then as many pieces as make 32 per CU: every cut costs a header to parse, a tail to resolve and a decoder that
         // looks for its target between symbols too (k_gz_decode<.., true>, ~15 % more instructions per symbol)
         const uint64_t wanted = 32ull * (uint64_t)kv_device_cus();
-        const uint64_t piece = sk ? strtoull(sk, nullptr, 10) * 1024ull * 8ull
-                                  : starts.size() * 4 >= wanted * 3 ? 0 : std::max<uint64_t>(4096ull * 8ull, (seg_end_rel - start_rel) / wanted);
+        // (bits of compressed data a piece should have; 0: no cutting)
+        const uint64_t piece = starts.size() * 4 >= wanted * 3 ? 0 : std::max<uint64_t>(4096ull * 8ull, (seg_end_rel - start_rel) / wanted);
         std::vector<GzGuess> guesses;
         const size_t n_blocks = have_terminal ? starts.size() - 1 : starts.size();
         for (size_t j = 0; j < n_blocks && piece; ++j) {

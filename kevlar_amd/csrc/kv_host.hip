@@ -581,14 +581,7 @@ extern "C" int kv_sketch_clear(kv_sketch *s)
     KV_REQUIRE(s, KV_ERR_ARG, "kv_sketch_clear: null handle");
     std::lock_guard<std::mutex> lk(s->mu);
     s->version++;
-    const char *lazy = kv_knob("KV_LAZY_CLEAR");           // "0": zero the tables here and now
-    if (lazy && atoi(lazy) == 0) {
-        KvProfScope prof("memset_tables");
-        for (int i = 0; i < s->h.ntables; ++i) KV_HIP(hipMemsetAsync(s->h.tab[i], 0, s->alloc_bytes[i], kv_stream()));
-        s->lazy_zero = false;
-    } else {
-        s->lazy_zero = true;
-    }
+    s->lazy_zero = true;                                   // the tables are zeroed by whoever touches them next (kv_sketch_ready)
     s->n_occupied = 0;
     s->n_unique = 0;
     s->occ_dirty = false;
@@ -1208,53 +1201,25 @@ const KvKnobDef g_knobs[] = {
     {"KV_NOVEL_PATH", T_, "tiles | skm: pin the scan path"},
     {"KV_ROUTE_PATH", T_, "plain: the exchange routes one item per k-mer (no combining)"},
     {"KV_SET_SCAN", T_, "skm: a shard's set scan keeps the bucketed kernel"},
-    {"KV_LAZY_CLEAR", T_, "0: kv_sketch_clear zeroes the tables at once instead of leaving it to the apply stage"},
-    {"KV_NO_ROLL", T_, "hash every k-mer from scratch (no rolling 2-bit window)"},
     {"KV_BIN_2BIT", T_, "0: stage A never hashes from the 2-bit form"},
-    {"KV_BIN_FAST4", T_, "0: no FP64-quotient remainders for four tables"},
-    {"KV_BIN_C", T_, "coarse buckets per table"},
-    {"KV_SKM_S1", T_, "tile | wave | lane: pin the record cutter"},
     {"KV_SKM_S2", T_, "plain | sorted: pin the fine split"},
-    {"KV_SKM_S1_THREADS", T_, "512 | 1024: workgroup size of the wave cutter"},
-    {"KV_SKM_R", T_, "reads per wave pass of the wave cutter"},
-    {"KV_SKM_CH", T_, "8 | 16: k-mers per lane chunk of the wave cutter"},
-    {"KV_SKM_LANE_MAXWG", T_, "2 | 3: workgroups per CU the lane cutter asks for"},
-    {"KV_SKM_LANE_FLUSH", T_, "blocks between two flushes of the lane cutter's run list"},
-    {"KV_SKM_SEG1", T_, "bucket: S1 segments laid out bucket-major"},
-    {"KV_SKM_COMPACT", T_, "0: never the 16-byte records without positions"},
     {"KV_SKM_ANY_K", T_, "use the kernels with k at run time, not the k = 31 / 51 instances"},
     {"KV_SKM_BUCKET_KMERS", T_, "k-mer occurrences aimed at per bucket (tests: many buckets on small inputs)"},
     {"KV_SKM_CAP_PCT", T_, "segment capacity in per cent of the estimate (tests: push records through the loose list)"},
     {"KV_SKM_LOOSE_CAP", T_, "entries of the loose list"},
     {"KV_SKM_FORCE_LOOSE", T_, "one key in 64 is counted as if its table were full: its occurrences travel through the loose list"},
-    {"KV_SKM_NWG1", T_, "S1 writers (upper bound)"},
-    {"KV_SKM_NWG2", T_, "S2 writers per coarse stream"},
-    {"KV_SKM_BPT", T_, "buckets per work ticket of stage S3"},
-    {"KV_SKM_WG3_PER_CU", T_, "1..3: S3 workgroups per CU"},
-    {"KV_SKM_ABL", T_, "0: no abundance list from a control's count"},
     {"KV_SKM_DL", T_, "0: no distinct list from a case sample's count; 1: from the first batch on"},
     {"KV_SKM_NO_REUSE", T_, "the scan re-buckets the batch instead of reusing the count's buckets"},
     {"KV_NOVEL_2BIT", T_, "0: the per-k-mer scan keeps the tile kernel"},
     {"KV_NOVEL_BITS", T_, "0: no bit map as the first probe of the scan"},
     {"KV_NOVEL_BITS_MIN", T_, "items from which the pairs scan builds its bit map"},
     {"KV_NOVEL_PAIRS", T_, "0: the set scan answers from hashes alone"},
-    {"KV_NOVEL_ABCACHE", T_, "0: no cache of the interesting k-mers' abundances"},
-    {"KV_NOVEL_VCACHE", T_, "0: no verdict cache in the tile scan"},
-    {"KV_NOVEL_VCSETS", T_, "0: direct-mapped verdict cache"},
-    {"KV_NOVEL_EMIT_TILES", T_, "hits listed by the tile kernel"},
-    {"KV_NOVEL_EMIT_FUSED", T_, "hits listed by the fused kernel"},
     {"KV_NOVEL_REREAD", T_, "`kevlar novel` reads a case file again for the scan instead of keeping its batch"},
     {"KV_HOST_SORT", T_, "partition sorts its keys on the host"},
-    {"KV_FORMAT_FD", T_, "0: annotated reads formatted into a buffer, not written to the descriptor"},
     {"KV_STAGE", T_, "0: uploads straight from the file mapping, no pinned staging"},
     {"KV_INGEST_TEXT_MB", T_, "text per ingest batch in MB (tests: small batches)"},
     {"KV_GUNZIP_TEXT_MIN_MB", T_, "gzip files from this size on are inflated on the device"},
     {"KV_GUNZIP_CHUNK_KB", T_, "1..64: compressed bytes per probe stretch"},
-    {"KV_GUNZIP_RING_BITS", T_, "10..14: LDS window of the gzip decoder"},
-    {"KV_GUNZIP_SPLIT_KB", T_, "cut DEFLATE blocks longer than this"},
-    {"KV_INFLATE_WINDOW_BITS", T_, "10..15: LDS window of the BGZF inflater"},
-    {"KV_MEX_NWG1", T_, "exchange: S1 writers of a shard (the same on every rank)"},
-    {"KV_MEX_CAP2_SLACK", T_, "exchange: S2 segment slack"},
     {"KV_MEX_PASSES", T_, "exchange: combine passes per bucket, at least (1-16)"},
     {"KV_MEX_DL_POOL", T_, "exchange: 1 = the owner's distinct list as a pool of chunks at once (it is the last resort of an owner short of memory)"},
     {"KV_MEX_PAIRS", T_, "9: (hash, count) pairs travel in the 9-byte block form"},

@@ -48,7 +48,7 @@ struct InflateShared {
 };
 
 template <int RBITS>
-__global__ __launch_bounds__(64, (RBITS <= 10 ? 8 : RBITS == 11 ? 5 : RBITS == 12 ? 4 : RBITS == 13 ? 3 : RBITS == 14 ? 2 : 1)) void k_inflate(const uint8_t *__restrict__ comp, const InflateJob *__restrict__ jobs, uint32_t n_jobs,
+__global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ comp, const InflateJob *__restrict__ jobs, uint32_t n_jobs,
                                                  uint8_t *text, unsigned long long *ctr)
 {
     __shared__ InflateShared<RBITS> sh;
@@ -289,19 +289,9 @@ int kv_bgzf_inflate(const uint8_t *d_comp, uint64_t comp_base, const KvBgzfMembe
         // takes (the kernel is then held to 64 VGPRs; what spills is the table construction, not the symbol loop); matches
         // that reach further back (up to 32 KB) read the text from HBM.  Measured on 846 MB of FASTQ text (4 M reads, bgzip
         // level 4), k_inflate alone, one box: 1 KB 27.2 ms, 2 KB 31.4 ms, 4 KB 35.5 ms; on another box 2 KB 42.4, 4 KB 45.9,
-        // 8 KB 52.1, 16 KB ~78, 32 KB (no HBM reads at all) ~100 ms.  KV_INFLATE_WINDOW_BITS = 10 .. 15 for experiments.
-        const char *wb = kv_knob("KV_INFLATE_WINDOW_BITS");
-        const int bits = wb ? atoi(wb) : 10;
-        const int per_cu = bits >= 15 ? 4 : bits == 14 ? 8 : bits == 13 ? 12 : bits == 12 ? 16 : bits == 11 ? 20 : 32;
-        const unsigned grid = (unsigned)std::min<uint64_t>(count, (uint64_t)per_cu * (uint64_t)kv_device_cus());
-#define KV_LAUNCH_INFLATE(B_) hipLaunchKernelGGL(k_inflate<B_>, dim3(grid), dim3(64), 0, st, d_comp, (const InflateJob *)d_jobs, (uint32_t)count, d_text, d_ctr)
-        if (bits >= 15) KV_LAUNCH_INFLATE(15);
-        else if (bits == 14) KV_LAUNCH_INFLATE(14);
-        else if (bits == 13) KV_LAUNCH_INFLATE(13);
-        else if (bits == 12) KV_LAUNCH_INFLATE(12);
-        else if (bits == 11) KV_LAUNCH_INFLATE(11);
-        else KV_LAUNCH_INFLATE(10);
-#undef KV_LAUNCH_INFLATE
+        // 8 KB 52.1, 16 KB ~78, 32 KB (no HBM reads at all) ~100 ms.
+        const unsigned grid = (unsigned)std::min<uint64_t>(count, 32ull * (uint64_t)kv_device_cus());
+        hipLaunchKernelGGL(k_inflate<10>, dim3(grid), dim3(64), 0, st, d_comp, (const InflateJob *)d_jobs, (uint32_t)count, d_text, d_ctr);
     }
     KV_HIP(hipGetLastError());
     unsigned long long ctr[3] = {0, 0, 0};

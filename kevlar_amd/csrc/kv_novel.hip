@@ -494,17 +494,10 @@ std::map<hipStream_t, ScanArenas> g_scan_arenas;
 std::mutex g_scan_arenas_mu;
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-inline int vc_sets_env()
-{
-    const char *e = kv_knob("KV_NOVEL_VCSETS");   // 0: direct-mapped cache in k_novel_mark as well
-    return e ? atoi(e) : -1;
-}
-
 // point p.vcache at this stream's verdict cache, (re)allocating or clearing it as the signature requires
 int attach_vcache(NovelParams &p, kv_sketch *const *ctrls, int ncase, int nctrl, int ctrl_max, uint64_t n_kmers, hipStream_t st)
 {
-    const char *vc_env = kv_knob("KV_NOVEL_VCACHE");
-    if (nctrl > 0 && p.screen == 0 && !(vc_env && atoi(vc_env) == 0)) {
+    if (nctrl > 0 && p.screen == 0) {
         // signature of everything the cached verdicts depend on
         uint64_t sig = 0x9e3779b97f4a7c15ull ^ (uint64_t)(uint32_t)ctrl_max;
         for (int c = ncase; c < ncase + nctrl; ++c) {
@@ -612,7 +605,7 @@ extern "C" int kv_novel_scan(kv_sketch *const *cases, int ncase, kv_sketch *cons
     auto prepare_tile_scan = [&]() -> int {
         const int rc = attach_vcache(p, ctrls, ncase, nctrl, ctrl_max, n_kmers, st);
         if (rc != KV_OK) return rc;
-        if (p.vcache && k >= 16 && k <= 32 && !(vc_sets_env() == 0)) {
+        if (p.vcache && k >= 16 && k <= 32) {
             p.vcache_sets = 1;
             p.vcache_window = VC_WINDOW;
             p.vcache_set_mask = (uint32_t)((1ull << (64 - p.vcache_shift - 3)) - 1ull);   // entries / 8 sets
@@ -687,7 +680,7 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
     uint64_t nhits = 0;
     bool marked_by_skm = use_skm;
     p.ab_keys = nullptr; p.ab_vals = nullptr; p.ab_mask = 0; p.ab_list = nullptr; p.ab_count = nullptr; p.ab_list_cap = 0;
-    if (e == hipSuccess && use_skm && !p.set_keys && kv_skm_list_ready(reads, k) && !(kv_knob("KV_NOVEL_ABCACHE") && atoi(kv_knob("KV_NOVEL_ABCACHE")) == 0)) {
+    if (e == hipSuccess && use_skm && !p.set_keys && kv_skm_list_ready(reads, k)) {
         // room for the abundances of the interesting k-mers (a k-mer in a few thousand is one): 1 / 64 of the k-mers in slots
         uint64_t slots = 1u << 16;
         while (slots < n_kmers / 64 && slots < (1ull << 24)) slots <<= 1;
@@ -755,8 +748,8 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
         p.hit_abund = (uint8_t *)arenas->hits.p + 2 * up256(nhits * 4);
         if (e == hipSuccess) {
             KvProfScope prof("k_novel_emit");
-            const bool from_bits = fam == HF_MURMUR && k <= 64 && !kv_knob("KV_NOVEL_EMIT_TILES");
-            const bool dense = from_bits && k >= SKM_MIN_K && !kv_knob("KV_NOVEL_EMIT_FUSED");
+            const bool from_bits = fam == HF_MURMUR && k <= 64;
+            const bool dense = from_bits && k >= SKM_MIN_K;
             const unsigned grid_hits = (unsigned)std::min<uint64_t>((nhits + 255) / 256, 1u << 16);
             if (dense && k <= 32) {
                 hipLaunchKernelGGL((k_novel_emit_bits<8, false>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
@@ -764,10 +757,8 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
             } else if (dense) {
                 hipLaunchKernelGGL((k_novel_emit_bits<16, false>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
                 hipLaunchKernelGGL(k_hit_abund<2>, dim3(grid_hits), dim3(256), 0, st, reads_dev(reads), p, nhits);
-            } else if (from_bits && k <= 32) {
+            } else if (from_bits) {                          // (k < SKM_MIN_K: one packed word's worth of window)
                 hipLaunchKernelGGL((k_novel_emit_bits<8, true>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
-            } else if (from_bits) {
-                hipLaunchKernelGGL((k_novel_emit_bits<16, true>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
             } else {
                 kv_ensure_dynamic_lds((const void *)k_novel_emit, reads->tile_lds_bytes);
                 hipLaunchKernelGGL(k_novel_emit, dim3(reads->n_tiles), dim3(KV_TILE_THREADS), reads->tile_lds_bytes, st, reads_dev(reads), p);

@@ -618,6 +618,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
 // Instances: w = 20 (k = 31: C = 1) and w = 40 (k = 51: C = 2), m = 12, reads of up to 16 x NW bases; everything else takes the kernels above.
 #define SKM_LANE_B 20
 #define SKM_LANE_CAP 320u         // finished runs a wave lists between two flushes (64 reads x 40 k-mers bring ~250; what does not fit is written at once)
+#define SKM_LANE_FLUSH_BLOCKS 2u  // blocks of B m-mers between two flushes of that list (the kernel takes it as an argument: compiled in, the
+                                  // cut of 24-byte records measured ~5 us of 1040 slower per launch)
 #define SKM_LANE_THREADS 512
 #define SKM_LANE_WAVES 6          // waves per SIMD the kernel is compiled for (3 workgroups per CU)
 // a wave's slice of LDS: the group's words, their reverse complement read by read (oriented records), the run list
@@ -671,7 +673,7 @@ __device__ __forceinline__ void skm_lane_block(const uint32_t *wl, uint32_t rbas
 }
 
 // (C = 2 keeps two arrays of suffix minima: 4 waves per SIMD -- two workgroups per CU, 128 registers -- where C = 1 runs 6; the kernel
-// is bound by instruction issue from 4 waves per SIMD up, so the lower occupancy costs nothing: measured with KV_SKM_NWG1=512 at C = 1)
+// is bound by instruction issue from 4 waves per SIMD up, so the lower occupancy costs nothing: measured with 512 writers at C = 1)
 template <int C, int NW>
 __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void k_skm_emit_lane(ReadsDev rd, SkmGeom sg, uint32_t n_groups, uint32_t flush_blocks)
 {
@@ -2256,26 +2258,19 @@ namespace {
 
 inline uint32_t skm_nwg3(const SkmGeom &g)
 {
-    // persistent workgroups of the bucket kernels: three per CU fill its LDS (KV_SKM_WG3_PER_CU=2 leaves a third of it -- and of the wave
-    // slots -- to whatever another stream has queued: the experiment behind DESIGN.md section 4.1, "samples on separate streams")
-    static const uint32_t per_cu = [] { const char *e = kv_knob("KV_SKM_WG3_PER_CU"); const int v = e ? atoi(e) : 3; return (uint32_t)(v >= 1 && v <= 3 ? v : 3); }();
-    return (uint32_t)std::min<uint64_t>((g.n_buckets + g.bpt - 1) / g.bpt, per_cu * (uint32_t)kv_device_cus());
+    // persistent workgroups of the bucket kernels: three per CU fill its LDS (two, which leave a third of it -- and of the wave slots -- to
+    // whatever another stream has queued, measured slower: DESIGN.md section 4.1, "samples on separate streams")
+    return (uint32_t)std::min<uint64_t>((g.n_buckets + g.bpt - 1) / g.bpt, 3u * (uint32_t)kv_device_cus());
 }
 
-static uint32_t skm_default_bpt()
-{
-    if (const char *e = kv_knob("KV_SKM_BPT")) { const int v = atoi(e); if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) return (uint32_t)v; }
-    return SKM_BUCKETS_PER_TICKET;
-}
 // Buckets per ticket of the work counter.  A ticket costs a returning atomic on a word every workgroup asks for -- ~10 per microsecond
 // device-wide, measured: a sample's 64 k buckets one per ticket took k_skm_count from 3.1 to 6.9 ms, two per ticket to 3.7 -- and a big
 // ticket leaves a tail (16: +0.08 ms, 32: +0.13).  8 for a whole sample; fewer where the buckets are few (a rank's share of the exchange:
-// 7 936 buckets for 768 workgroups -- tickets of 8 give a quarter of them two and the rest one), down to 2.  KV_SKM_BPT overrides.
+// 7 936 buckets for 768 workgroups -- tickets of 8 give a quarter of them two and the rest one), down to 2.
 static void skm_pick_bpt(SkmGeom &g)
 {
     g.bpt = SKM_BUCKETS_PER_TICKET;
     while (g.bpt > 2u && g.n_buckets / g.bpt < 4u * 768u) g.bpt /= 2u;
-    if (kv_knob("KV_SKM_BPT")) g.bpt = skm_default_bpt();
 }
 
 inline uint32_t pow2_ceil(uint64_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
@@ -2284,19 +2279,14 @@ int skm_minimizer_len(int k) { return k >= 24 ? 12 : k / 2; }
 
 // reads per wave and chunk size of the wave kernel for batches of equal-length reads (0: use the tile kernel).  One packed
 // word and one chunk per lane, and about as many runs as lanes: a run per (w + 1) / 2 k-mers, one more per read.
-// threads per workgroup of the wave kernel (KV_SKM_S1_THREADS=512|1024)
-static thread_local uint32_t tl_s1_threads = 0;       // a caller's choice for the launch it is about to make (kv_skm_mex_emit); the variable in the environment wins
-static uint32_t skm_wave_threads()
-{
-    if (const char *e = kv_knob("KV_SKM_S1_THREADS")) return atoi(e) == 512 ? 512u : 1024u;
-    return tl_s1_threads ? tl_s1_threads : SKM_S1_WAVE_THREADS_DEFAULT;
-}
+// threads per workgroup of the wave kernel (512 | 1024)
+static thread_local uint32_t tl_s1_threads = 0;       // a caller's choice for the launch it is about to make (kv_skm_mex_emit)
+static uint32_t skm_wave_threads() { return tl_s1_threads ? tl_s1_threads : SKM_S1_WAVE_THREADS_DEFAULT; }
 
 static uint32_t skm_wave_plan(const SkmGeom &g, const kv_reads *reads, int *ch)
 {
     const uint32_t L = reads->uni_len;
     if (!L || L < (uint32_t)g.k || g.w <= 8) return 0;
-    if (const char *e = kv_knob("KV_SKM_S1")) if (!strcmp(e, "tile")) return 0;
     const uint32_t wpr = (L + 15) / 16, nk = L - (uint32_t)g.k + 1;
     const double runs = 1.0 + (nk - 1) * 2.0 / (g.w + 1) + (double)nk / g.ncap * 0.5;
     uint32_t best = 0;
@@ -2305,10 +2295,8 @@ static uint32_t skm_wave_plan(const SkmGeom &g, const kv_reads *reads, int *ch)
         const uint32_t cpr = (nk + c - 1) / c;
         uint32_t R = std::min<uint32_t>(64 / wpr, 64 / cpr);
         R = std::min<uint32_t>(R, (uint32_t)(58.0 / runs));
-        if (const char *e = kv_knob("KV_SKM_R")) R = std::min<uint32_t>(std::min<uint32_t>(64 / wpr, 64 / cpr), (uint32_t)atoi(e));
         if (R >= best && R > 0) { best = R; *ch = c; }       // equal R: the smaller chunk keeps more lanes busy
     }
-    if (const char *e = kv_knob("KV_SKM_CH")) { const int c = atoi(e); if ((c == 8 || c == 16) && g.w > c) { *ch = c; best = std::min<uint32_t>(best, 64 / ((nk + c - 1) / c)); } }
     if (best < 2) return 0;
     const uint32_t threads = skm_wave_threads();
     // three workgroups of 512 per CU, or one of 1024 -- or the tile kernel
@@ -2316,26 +2304,20 @@ static uint32_t skm_wave_plan(const SkmGeom &g, const kv_reads *reads, int *ch)
     return best;
 }
 
-// the lane-per-read kernel takes batches of equal-length reads with w = 20 or 40 (k = 31, 51: m = 12) and up to 256 bases;
-// KV_SKM_S1=wave|tile keeps the older kernels
+// the lane-per-read kernel takes batches of equal-length reads with w = 20 or 40 (k = 31, 51: m = 12) and up to 256 bases
 // workgroups of the lane-per-read cut a CU holds at once, by their LDS (0: not even two -- other kernels cut such reads)
 static uint32_t skm_lane_wgs_per_cu(uint32_t L)
 {
     const size_t need = (size_t)skm_lane_slice_words((L + 15u) / 16u) * 4 * (SKM_LANE_THREADS / 64) + 1200;
-    const char *e = kv_knob("KV_SKM_LANE_MAXWG");                // (A/B: 3 keeps the cut to the lengths that fit three times)
-    const uint32_t floor_wgs = e ? (uint32_t)std::max(2, std::min(3, atoi(e))) : 2u;
     if (need <= 160000u / (SKM_LANE_WAVES / 2)) return 3u;
-    return (floor_wgs <= 2u && need <= 160000u / 2u) ? 2u : 0u;
+    return need <= 160000u / 2u ? 2u : 0u;
 }
 // (by the read length alone: kv_mex_plan_short, which sees no reads, asks this way)
 static bool skm_lane_fits_len(const SkmGeom &g, uint32_t L)
 {
     if (!L || L < (uint32_t)g.k || g.m != 12 || (g.w != SKM_LANE_B && g.w != 2 * SKM_LANE_B) || L > 256u) return false;
-    const char *e1 = kv_knob("KV_SKM_S1");
-    if (e1 && strcmp(e1, "lane") != 0) return false;
     // (w = 40, k = 51: two arrays of suffix minima; that instance is compiled for 4 waves per SIMD and skm_build starts two workgroups
     // per CU for it -- at six waves it spilled and measured slower than the wave kernel, 5.5 against 4.1 ms per step of config 5)
-    if (g.w != SKM_LANE_B && e1 && !strcmp(e1, "lane6")) return false;
     // three workgroups per CU for reads of up to 112 bases (seven packed words and their reverse complement per lane), two up to 224
     return skm_lane_wgs_per_cu(L) >= 2u;
 }
@@ -2349,13 +2331,11 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
         const uint32_t wpr = (reads->uni_len + 15u) / 16u;
         const size_t lds = (size_t)skm_lane_slice_words(wpr) * 4 * (SKM_LANE_THREADS / 64);
         const uint64_t n_groups = (reads->n_reads + 63) / 64;
-        uint32_t flush_blocks = 2;
-        if (const char *e = kv_knob("KV_SKM_LANE_FLUSH")) flush_blocks = std::max(1, atoi(e));
         void (*kernel)(ReadsDev, SkmGeom, uint32_t, uint32_t);
         if (g.w == SKM_LANE_B) kernel = wpr <= 8 ? k_skm_emit_lane<1, 8> : k_skm_emit_lane<1, 16>;
         else kernel = wpr <= 8 ? k_skm_emit_lane<2, 8> : k_skm_emit_lane<2, 16>;
         kv_ensure_dynamic_lds((const void *)kernel, lds);
-        hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(SKM_LANE_THREADS), lds, st, reads_dev(reads), g, (uint32_t)n_groups, flush_blocks);
+        hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(SKM_LANE_THREADS), lds, st, reads_dev(reads), g, (uint32_t)n_groups, SKM_LANE_FLUSH_BLOCKS);
         return;
     }
     if (const uint32_t R = skm_wave_plan(g, reads, &ch)) {
@@ -2510,7 +2490,7 @@ void skm_geom_k(SkmGeom &g, int k)
     g.lrecw = g.recw;
     g.ncap = 32 * g.nbw - k + 1;
     g.sbw = ((64u * (uint32_t)g.ncap) >> 5) + 2u;
-    g.bpt = skm_default_bpt();
+    g.bpt = SKM_BUCKETS_PER_TICKET;
 }
 
 __global__ void k_mex_sum_kmers(const uint64_t *seg, const uint32_t *cnt, const uint64_t *off, uint64_t n_segments, uint32_t cap1, uint32_t recw,
@@ -2568,11 +2548,10 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
     g.C1 = (uint32_t)std::min<uint64_t>(255, std::max<uint64_t>(1, (nfine + g.F2 - 1) / g.F2));
     g.n_buckets = g.C1 * g.F2;
     // 16-byte records without positions (kv_skm_device.h) when nobody will ask where a k-mer was: the count of a sample that is not
-    // scanned from this very batch.  The lane-per-read S1 writes them, the sorted S2 moves them, k_skm_count reads them; KV_SKM_COMPACT=0: never
+    // scanned from this very batch.  The lane-per-read S1 writes them, the sorted S2 moves them, k_skm_count reads them
     {
-        const char *e = kv_knob("KV_SKM_COMPACT"), *s2 = kv_knob("KV_SKM_S2");
-        g.compact = (!want_pos && g.kw == 1 && k + 1 <= SKM_C_BASES && skm_lane_fits(g, reads) && g.F2 <= SKM_S2_MAXF && !(s2 && strcmp(s2, "sorted") != 0) &&
-                     !(e && atoi(e) == 0)) ? 1u : 0u;
+        const char *s2 = kv_knob("KV_SKM_S2");
+        g.compact = (!want_pos && g.kw == 1 && k + 1 <= SKM_C_BASES && skm_lane_fits(g, reads) && g.F2 <= SKM_S2_MAXF && !(s2 && strcmp(s2, "sorted") != 0)) ? 1u : 0u;
         if (g.compact) { g.recw = 2; g.ncap = std::min(g.ncap, SKM_C_BASES + 1 - k); }
     }
     const int cus = kv_device_cus();
@@ -2591,8 +2570,6 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
         g.quota1 = (uint32_t)std::min<uint64_t>(kv_round_up(avg + avg / 2 + 1, SKM_TILES_PER_TICKET), 0xfffffff0ull);
     }
     g.nwg2 = std::max<uint32_t>(1u, std::min<uint32_t>(16u, 1024u / g.C1));
-    if (const char *e = kv_knob("KV_SKM_NWG1")) g.nwg1 = std::max<uint32_t>(1u, std::min<uint32_t>(g.nwg1, (uint32_t)atoi(e)));
-    if (const char *e = kv_knob("KV_SKM_NWG2")) g.nwg2 = std::max<uint32_t>(1u, std::min<uint32_t>(16u, (uint32_t)atoi(e)));
     g.nwg2 = std::min<uint32_t>(g.nwg2, g.nwg1);
     g.np_max = std::max<uint32_t>(reads->tile_max_bases, 64u);
     const uint64_t min_stride = reads->max_len >= (uint32_t)k ? reads->max_len - (uint32_t)k + 1 : 1;
@@ -2624,7 +2601,7 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
     unsigned char *base = (unsigned char *)idx.arena.p;
     g.seg1 = (uint64_t *)base; base += b_seg1;
     g.cnt1 = (uint32_t *)base; base += b_cnt1;
-    { const char *e = kv_knob("KV_SKM_SEG1"); g.seg1_wmajor = (e && !strcmp(e, "bucket")) ? 0u : 1u; }
+    g.seg1_wmajor = 1u;
     g.seg2 = (uint64_t *)base; base += b_seg2;
     g.cnt2 = (uint32_t *)base; base += b_cnt2;
     g.loose = (uint64_t *)base; base += b_loose;
@@ -2718,12 +2695,11 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         if (rc != KV_OK) return rc;
     }
     const SketchDev *d_mask = mask ? mask->d_desc : nullptr;
-    // abundance list of this batch (KvAbundList): the first super-k-mer count after a clear writes one, unless KV_SKM_ABL=0
+    // abundance list of this batch (KvAbundList): the first super-k-mer count after a clear writes one
     bool abl_new = false;
     {
-        const char *e = kv_knob("KV_SKM_ABL");
         KvAbundList &al = s->abl;
-        if (!(e && atoi(e) == 0) && !al.valid && !s->scan_hint) {            // (a case sample's list would never be asked for: it is scanned, not scanned against)
+        if (!al.valid && !s->scan_hint) {            // (a case sample's list would never be asked for: it is scanned, not scanned against)
             const uint64_t cap_total = std::min<uint64_t>(std::max<uint64_t>(n_kmers / 8, 1u << 16), 0xfffffff0ull);
             const uint64_t cap_wg = std::max<uint64_t>(64, cap_total / nwg3);
             const size_t b_keys = kv_round_up(cap_wg * nwg3 * 8 * sg.kw, 256), b_cnts = kv_round_up(cap_wg * nwg3, 256);
@@ -2916,7 +2892,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     SkmAblSet abls;
     memset(&abls, 0, sizeof(abls));
     abls.ctrl_max = p.ctrl_max;
-    if (p.host_ctrls && !p.set_keys && !(kv_knob("KV_SKM_ABL") && atoi(kv_knob("KV_SKM_ABL")) == 0)) {
+    if (p.host_ctrls && !p.set_keys) {
         const kv_sketch *const *ctrls = (const kv_sketch *const *)p.host_ctrls;
         for (int c = 0; c < p.host_nctrl && abls.n < SKM_MAX_ABL; ++c) {
             const KvAbundList &al = ctrls[c]->abl;
@@ -3057,8 +3033,8 @@ int kv_skm_mex_plan(int ksize, uint64_t n_reads_global, uint32_t read_len, int n
     // Writers per shard; every one owns a segment of every coarse bucket.  One per CU, 1024 threads each: a shard is an N-th of a
     // sample, and with the 768 writers of a whole sample its ~190 000 segments held ~40 records each at N = 8 -- the cut, the packing
     // and the owner's split all pay per segment (per rank of config 2, N = 8 / N = 2: 8.58 / 25.07 ms with 768 writers of 512 threads,
-    // 7.73 / 23.10 with 256 of 1024).  KV_MEX_NWG1 (the same on every rank) overrides.
-    const uint64_t nwg1_max = kv_knob("KV_MEX_NWG1") ? (uint64_t)std::max(1, std::min(768, atoi(kv_knob("KV_MEX_NWG1")))) : 256;
+    // 7.73 / 23.10 with 256 of 1024).
+    const uint64_t nwg1_max = 256;
     const uint32_t nwg1 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tiles + SKM_TILES_PER_TICKET - 1) / SKM_TILES_PER_TICKET, nwg1_max));
     const double rec_est = (double)(shard_reads * nk_read) * 2.2 / (double)(g.w + 1) + (double)shard_reads + 1024.0;
     const double m1 = rec_est / ((double)C1 * nwg1);
@@ -3080,7 +3056,7 @@ int kv_skm_mex_plan_short(kv_mex_plan *plan)
     // (the owner's S2 takes 16-byte records in either form: the sorted split up to 1024 fine buckets, the plain one up to 4096 -- the 12
     // bits the record has for its fine bucket)
     KV_REQUIRE(g.kw == 1 && g.w == SKM_LANE_B && skm_lane_fits_len(g, plan->read_len) &&
-               plan->F2 <= 4096u && !(kv_knob("KV_SKM_COMPACT") && atoi(kv_knob("KV_SKM_COMPACT")) == 0),
+               plan->F2 <= 4096u,
                KV_ERR_NOTIMPL, "kv_mex_plan_short: no 16-byte records for k = %d, reads of %u bases, %u fine buckets", plan->ksize, plan->read_len, plan->F2);
     if (plan->flags & 1u) return KV_OK;
     plan->flags |= 1u;
@@ -3198,9 +3174,8 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
     const double rec_est = (double)n_kmers_exp * 2.2 / (double)(g.w + 1) + (double)plan->n_reads_global / plan->ndest + 1024.0;
     const double m2 = rec_est / ((double)g.n_buckets * g.nwg2);
     // (a geometry at its limit -- 4096 fine buckets per coarse one: a handful of distinct 12-base minimizers per bucket -- has buckets of
-    // very different sizes: at 248 x 4096 buckets a tenth of the records missed segments of 2 x the even share; KV_MEX_CAP2_SLACK overrides)
-    double slack2 = plan->F2 > SKM_S2_MAXF ? 3.0 : 1.4;
-    if (const char *e = kv_knob("KV_MEX_CAP2_SLACK")) slack2 = std::max(1.1, atof(e));
+    // very different sizes: at 248 x 4096 buckets a tenth of the records missed segments of 2 x the even share)
+    const double slack2 = plan->F2 > SKM_S2_MAXF ? 3.0 : 1.4;
     g.cap2 = (uint32_t)kv_round_up((uint64_t)(m2 * slack2 + 8.0 * std::sqrt(m2)) + 32, 16);
     g.loose_cap = (uint64_t)(rec_est / 8.0) + n_kmers_exp / 16 + (1u << 20);
     const size_t rb = (size_t)g.recw * 8;
