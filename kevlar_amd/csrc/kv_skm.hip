@@ -35,9 +35,7 @@ struct SkmGeom {
     uint64_t *seg1; uint32_t *cnt1;  // [C1][nwg1][cap1] records / [C1][nwg1]
     uint64_t *seg2; uint32_t *cnt2;  // [C1 * F2][nwg2][cap2] / [C1 * F2][nwg2]
     uint64_t *loose; uint64_t loose_cap;
-    unsigned long long *ctr;         // [0] loose records, [1] failure, [2] S1 tile ticket, [3] count ticket, [4] scan ticket,
-                                     // [5] records emitted, [6] loose records after S1 + S2, [7] distinct k-mers the count pass found in its LDS tables,
-                                     // [9] workgroups whose stretch of the distinct list ran out
+    unsigned long long *ctr;         // [SKM_CTR_COUNT] counters, zeroed for every batch: the slots are the SkmCtr enumerators below
     uint32_t n_buckets, quota3;
     uint32_t sbw;                    // words of record-start bits per wave in the bucket walk
     uint64_t bucket_kmers;           // average k-mers per fine bucket
@@ -50,7 +48,7 @@ struct SkmGeom {
     // distinct list the count pass writes for a batch that is going to be scanned (SkmIndex::dl; dl_keys == nullptr: off): EVERY
     // distinct k-mer of a bucket with its hash, appended like the abundance list (a stretch per workgroup, start + count per bucket)
     uint64_t *dl_keys, *dl_hash; uint32_t *dl_bstart, *dl_bcount; uint32_t dl_cap_wg;
-    uint32_t dl_chunk, dl_nchunks;   // k_skm_route only: != 0 -- the list is a pool of dl_nchunks chunks of dl_chunk entries that the workgroups draw from (ctr[13]) instead of one stretch each
+    uint32_t dl_chunk, dl_nchunks;   // k_skm_route only: != 0 -- the list is a pool of dl_nchunks chunks of dl_chunk entries that the workgroups draw from (SKM_CTR_POOL_CHUNKS) instead of one stretch each
     uint32_t n_src;
     const uint64_t *seg1_off;        // non-null: segment `slot` starts at record seg1_off[slot] (compacted records) instead of slot * cap1
     uint64_t read_base;              // global index of the batch's first read (record positions of a read shard; 0 otherwise)
@@ -69,6 +67,23 @@ struct SkmGeom {
     uint32_t passes;                 // k_skm_route takes a bucket's k-mers in at least this many passes (0 / 1: one) -- buckets bigger than its LDS table
     uint32_t bpt;                    // buckets per ticket of the bucket kernels' work counter (a power of two)
 };
+
+// the slots of SkmGeom::ctr
+enum SkmCtr {
+    SKM_CTR_LOOSE = 0,               // records on the loose list
+    SKM_CTR_FAIL = 1,                // failure flag: a record was lost (loose list overflow), a table could not take a key, or the pass was given up
+    SKM_CTR_TICKET_S1 = 2, SKM_CTR_TICKET_COUNT = 3, SKM_CTR_TICKET_SCAN = 4,     // work tickets of S1 (tiles), of the count / route pass and of the scan (buckets)
+    SKM_CTR_RECORDS = 5,             // records S1 emitted
+    SKM_CTR_LOOSE_S12 = 6,           // loose records S1 + S2 left behind (the host copies SKM_CTR_LOOSE here before the bucket kernels add theirs)
+    SKM_CTR_DISTINCT = 7,            // distinct k-mers the count / route pass found in its LDS tables
+    SKM_CTR_ARRIVED = 8,             // k-mer occurrences that arrived at an exchange owner (k_mex_sum_kmers)
+    SKM_CTR_DL_RAN_OUT = 9,          // workgroups whose stretch of the distinct list ran out, or draws from its pool of chunks that found it empty
+    SKM_CTR_SET_HITS = 10,           // hits kv_skm_mex_scan_set stored (SetHitSink::count)
+    SKM_CTR_POOL_CHUNKS = 13,        // (nothing uses 11 and 12) chunks drawn from the distinct list's pool (k_skm_route, dl_chunk != 0)
+    SKM_CTR_COUNT
+};
+// the slots of other stages' counters that kernels here touch: BinGeom::ctr (kv_binned.h), KvRouteSink::ctr (kv_internal.h)
+enum { BIN_CTR_FAIL = 1, BIN_CTR_ADDED = 2, ROUTE_CTR_OVERFLOW = 1, ROUTE_CTR_DEST0 = 18 };
 
 // segment `seg` of coarse bucket c in seg1 / cnt1, counted in segments
 __device__ __forceinline__ uint64_t skm_seg1_slot(const SkmGeom &sg, uint32_t c, uint32_t seg)
@@ -129,9 +144,9 @@ __device__ __forceinline__ void skm_store_record(uint64_t *dst, uint64_t hdr, co
 
 __device__ __forceinline__ void skm_loose_push(const SkmGeom &sg, uint64_t hdr, const uint64_t *bw)
 {
-    const unsigned long long idx = atomicAdd(&sg.ctr[0], 1ull);
+    const unsigned long long idx = atomicAdd(&sg.ctr[SKM_CTR_LOOSE], 1ull);
     if (idx < sg.loose_cap) skm_store_record(sg.loose + idx * (uint64_t)sg.lrecw, hdr, bw, sg.nbw);
-    else sg.ctr[1] = 1;
+    else sg.ctr[SKM_CTR_FAIL] = 1;
 }
 
 // ---- S1 ------------------------------------------------------------------------------------------------
@@ -179,7 +194,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
     const int k = sg.k, m = sg.m, w = sg.w;
     const int lane = threadIdx.x & 63;
     for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_THREADS1) cur[c] = 0;
-    if (threadIdx.x == 0) sh.next_tile = (uint32_t)atomicAdd(&sg.ctr[2], 1ull) * SKM_TILES_PER_TICKET;
+    if (threadIdx.x == 0) sh.next_tile = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull) * SKM_TILES_PER_TICKET;
     uint64_t n_rec = 0;
     // Batches of equal-length reads (rd.uni_len): the layout of a tile is arithmetic, so the packed words of the NEXT
     // tile are requested while this one is processed (two registers per thread) and the per-tile chain of dependent loads
@@ -279,7 +294,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
         // the next ticket is fetched while this tile is processed (everybody has read the current one by now)
         if (threadIdx.x == 0) {
             if ((tile + 1u) % SKM_TILES_PER_TICKET) sh.next_tile = tile + 1u;       // same ticket
-            else sh.next_tile = taken + 1 < sg.quota1 ? (uint32_t)atomicAdd(&sg.ctr[2], 1ull) * SKM_TILES_PER_TICKET : 0xffffffffu;
+            else sh.next_tile = taken + 1 < sg.quota1 ? (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull) * SKM_TILES_PER_TICKET : 0xffffffffu;
         }
         const uint32_t NB = sh.bpre[nr];
         // P1: one thread per packed word: the order values of the m-mers starting at its 16 bases
@@ -409,7 +424,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_THREADS1) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
     n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63) == 0 && n_rec) atomicAdd(&sg.ctr[5], (unsigned long long)n_rec);
+    if ((threadIdx.x & 63) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
 }
 
 // ---- S1, batches of equal-length reads: a wave per group of reads -----------------------------------------------
@@ -472,7 +487,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
         if (mt == mt_end) {
             if (taken >= quota_mt) break;
             uint32_t t = 0;
-            if (lane == 0) t = (uint32_t)atomicAdd(&sg.ctr[2], 1ull);
+            if (lane == 0) t = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull);
             t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
             if ((uint64_t)t * per_ticket >= n_mt) break;
             mt = t * per_ticket;
@@ -596,7 +611,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < sg.C1; c += THREADS) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
     n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[5], (unsigned long long)n_rec);
+    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
 }
 
 // ---- S1, batches of equal-length reads: a LANE per read (round 5) ---------------------------------------------------
@@ -820,7 +835,7 @@ __global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_LANE_THREADS) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
     n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[5], (unsigned long long)n_rec);
+    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
 }
 
 // ---- S2 ------------------------------------------------------------------------------------------------
@@ -1174,13 +1189,13 @@ __device__ __forceinline__ void skm_walk_loose(const SkmGeom &sg, bool alone, co
     // (WANT_POS: pos0 is this occurrence's position already; else it is derived here from the owner's header, orientation included)
     const uint64_t posu = WANT_POS ? pos0 : skm_hdr_pos_of(skm_shfl64(hdr, owner), j0 + u);
     unsigned long long first = 0;
-    if (lane == 0) first = atomicAdd(&sg.ctr[0], (unsigned long long)__popcll(need));
+    if (lane == 0) first = atomicAdd(&sg.ctr[SKM_CTR_LOOSE], (unsigned long long)__popcll(need));
     first = skm_shfl64(first, 0);
     if (alone) {
         const unsigned long long idx = first + (unsigned long long)__popcll(need & ((1ull << lane) - 1ull));
         uint64_t one[3] = {kmer.w[0], KW == 2 ? kmer.w[KW - 1] : 0ull, 0ull};
         if (idx < sg.loose_cap) skm_store_record(sg.loose + idx * (uint64_t)recw, skm_header(posu, 1u, 0u), one, sg.nbw);
-        else sg.ctr[1] = 1;
+        else sg.ctr[SKM_CTR_FAIL] = 1;
     }
 }
 
@@ -1347,7 +1362,7 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
     // while the current bucket is processed
     skm_table_clear(tb);
     for (uint32_t i = threadIdx.x; i < (PL ? TS / 2 : TS); i += SKM_THREADS3) cnt[i] = 0;
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[3], 1ull) * sg.bpt; abl_cur = 0; abl_b0 = 0; abl_prev = 0xffffffffu; dl_cur = 0; dl_b0 = 0; }
+    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt; abl_cur = 0; abl_b0 = 0; abl_prev = 0xffffffffu; dl_cur = 0; dl_b0 = 0; }
     // where the finished bucket's entries of the abundance list lie (nothing if the workgroup's stretch ran out)
     auto abl_close = [&]() {
         if (sg.abl_keys && abl_prev != 0xffffffffu) {
@@ -1357,7 +1372,7 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
         }
         if (sg.dl_keys && abl_prev != 0xffffffffu) {
             sg.dl_bstart[abl_prev] = blockIdx.x * sg.dl_cap_wg + dl_b0;
-            sg.dl_bcount[abl_prev] = dl_cur - dl_b0;                // (a stretch that ran out is reported through ctr[9]: the whole list is then dropped)
+            sg.dl_bcount[abl_prev] = dl_cur - dl_b0;                // (a stretch that ran out is reported through SKM_CTR_DL_RAN_OUT: the whole list is then dropped)
         }
     };
     for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
@@ -1369,16 +1384,16 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
             abl_close();
             abl_prev = b; abl_b0 = abl_cur; dl_b0 = dl_cur;
             if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
+            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
             else {
-                const unsigned long long ticket = atomicAdd(&sg.ctr[3], 1ull);
+                const unsigned long long ticket = atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull);
                 next_bucket = (uint32_t)ticket * sg.bpt;     // (a raised flag ends the pass: the caller redoes the batch)
                 // a batch that does not fit the LDS tables (low coverage per batch: nearly every k-mer distinct) is given up
                 // early: once 2 % of the buckets are done, more than 4 % of their k-mers outside the tables raise the flag
                 const unsigned long long done = ticket * sg.bpt;
                 if (done * 50ull >= sg.n_buckets) {
-                    const unsigned long long now = __hip_atomic_load(&sg.ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[6];
-                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[1] = 1;
+                    const unsigned long long now = __hip_atomic_load(&sg.ctr[SKM_CTR_LOOSE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[SKM_CTR_LOOSE_S12];
+                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[SKM_CTR_FAIL] = 1;
                 }
             }
         }
@@ -1486,14 +1501,14 @@ __global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_sk
     __syncthreads();
     if (threadIdx.x == 0) {
         abl_close();
-        if (sg.dl_keys && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[9], 1ull);
+        if (sg.dl_keys && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
     }
     for (uint32_t s = threadIdx.x; s < ns; s += SKM_THREADS3)
         g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
     n_added = wave_sum_u64(n_added);
     n_distinct = wave_sum_u64(n_distinct);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
-    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[7], (unsigned long long)n_distinct);
+    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[BIN_CTR_ADDED], (unsigned long long)n_added);
+    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[SKM_CTR_DISTINCT], (unsigned long long)n_distinct);
 }
 
 // loose records: every k-mer occurrence on its own, increments through the spill list (global atomics)
@@ -1502,10 +1517,10 @@ __global__ __launch_bounds__(256) void k_skm_loose_count(SkmGeom sg, const Sketc
                                                          const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
 {
     __shared__ uint32_t lut[256];
-    if (sg.ctr[1] != 0) return;                  // the pass was given up: the caller redoes the batch another way
+    if (sg.ctr[SKM_CTR_FAIL] != 0) return;                  // the pass was given up: the caller redoes the batch another way
     lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     __syncthreads();
-    unsigned long long n = sg.ctr[0];
+    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
     if (n > sg.loose_cap) n = sg.loose_cap;
     const int k = sg.k, recw = sg.lrecw;
     uint64_t n_added = 0;
@@ -1557,7 +1572,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_count(SkmGeom sg, const Sketc
         }
     }
     n_added = wave_sum_u64(n_added);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
+    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[BIN_CTR_ADDED], (unsigned long long)n_added);
 }
 
 // ---- S3': route (read-sharded multi-GPU count) ---------------------------------------------------------------
@@ -1575,12 +1590,12 @@ __device__ __attribute__((noinline)) void skm_route_overflow(SkmOverflowSink rs,
         const unsigned long long here = __ballot(true);
         const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)here) - 1u;
         unsigned long long o = 0;
-        if (lane == leader) o = atomicAdd(&rs.ctr[1], (unsigned long long)__popcll(here));
+        if (lane == leader) o = atomicAdd(&rs.ctr[ROUTE_CTR_OVERFLOW], (unsigned long long)__popcll(here));
         o = skm_shfl64(o, leader) + (unsigned long long)__popcll(here & ((1ull << lane) - 1ull));
         const bool fits = o < rs.ovf_cap;
         for (int dd = 0; dd < rs.ndest; ++dd) {
             const unsigned long long same = __ballot(fits && d == (uint32_t)dd);
-            if (same && lane == (uint32_t)__ffsll((long long)same) - 1u) atomicAdd(&rs.ctr[18 + dd], (unsigned long long)__popcll(same));
+            if (same && lane == (uint32_t)__ffsll((long long)same) - 1u) atomicAdd(&rs.ctr[ROUTE_CTR_DEST0 + dd], (unsigned long long)__popcll(same));
         }
         if (fits) {
             *(ulonglong2 *)(rs.ovf + 2 * o) = make_ulonglong2(h, count);
@@ -1618,14 +1633,14 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashP
     skm_table_clear(tb);
     for (uint32_t i = threadIdx.x; i < TS; i += SKM_THREADS3) cnt[i] = 0;
     if (threadIdx.x == 0) {
-        next_bucket = (uint32_t)atomicAdd(&sg.ctr[3], 1ull) * sg.bpt; dl_cur = 0; dl_b0 = 0; dl_prev = 0xffffffffu;
+        next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt; dl_cur = 0; dl_b0 = 0; dl_prev = 0xffffffffu;
         dl_org = sg.dl_chunk ? 0u : blockIdx.x * sg.dl_cap_wg; dl_lim = sg.dl_chunk ? 0u : sg.dl_cap_wg;
     }
     auto dl_close = [&]() {
         if (sg.dl_keys && dl_prev != 0xffffffffu) {
             sg.dl_bstart[dl_prev] = dl_org + dl_b0;
-            sg.dl_bcount[dl_prev] = dl_cur - dl_b0;              // (a stretch that ran out is reported through ctr[9]: the whole list is then dropped)
-            if (sg.dl_chunk && dl_cur > dl_lim) atomicAdd(&sg.ctr[9], 1ull);
+            sg.dl_bcount[dl_prev] = dl_cur - dl_b0;              // (a stretch that ran out is reported through SKM_CTR_DL_RAN_OUT: the whole list is then dropped)
+            if (sg.dl_chunk && dl_cur > dl_lim) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
         }
     };
     // passes a bucket is combined in (see below), from its record count
@@ -1654,16 +1669,16 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashP
                 // worth of entries: a chunk that may not hold this bucket's is left as it is and the next one drawn.
                 const uint32_t need = passes_of(b) * (uint32_t)TS;
                 if (dl_cur + need > dl_lim) {
-                    const unsigned long long c = atomicAdd(&sg.ctr[13], 1ull);
+                    const unsigned long long c = atomicAdd(&sg.ctr[SKM_CTR_POOL_CHUNKS], 1ull);
                     if (c < sg.dl_nchunks && need <= sg.dl_chunk) { dl_org = (uint32_t)c * sg.dl_chunk; dl_lim = sg.dl_chunk; }
-                    else { dl_org = 0; dl_lim = 0; atomicAdd(&sg.ctr[9], 1ull); }          // the pool is empty (or the bucket beyond any chunk): no list
+                    else { dl_org = 0; dl_lim = 0; atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull); }          // the pool is empty (or the bucket beyond any chunk): no list
                     dl_cur = 0;
                 }
             }
             dl_prev = b; dl_b0 = dl_cur;
             if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[3], 1ull) * sg.bpt;
+            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
+            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt;
         }
         // A sample too big for the bucket geometry (255 x 4096 buckets: beyond 8.5 G k-mers a bucket holds more distinct k-mers than the
         // table has slots) is combined in passes: pass p walks the whole bucket and takes the k-mers whose hash says p -- the walk is paid
@@ -1712,12 +1727,12 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashP
     __syncthreads();
     if (threadIdx.x == 0) {
         dl_close();
-        if (sg.dl_keys && !sg.dl_chunk && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[9], 1ull);
+        if (sg.dl_keys && !sg.dl_chunk && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
     }
     if (threadIdx.x < (uint32_t)rs.ndest)
         rs.seg_count[(uint64_t)threadIdx.x * rs.nwg + blockIdx.x] = (uint32_t)min((uint64_t)cur[threadIdx.x], rs.seg_cap);
     n_distinct = wave_sum_u64(n_distinct);
-    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[7], (unsigned long long)n_distinct);
+    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[SKM_CTR_DISTINCT], (unsigned long long)n_distinct);
 }
 
 // loose records: one item of count 1 per k-mer occurrence, through the overflow list
@@ -1729,12 +1744,12 @@ __global__ __launch_bounds__(256) void k_skm_loose_route(SkmGeom sg, HashParams 
     __shared__ uint32_t dcount[SKM_ROUTE_MAX_DEST];      // items of this workgroup per destination
     __shared__ uint32_t wg_items, wg_cur;
     __shared__ unsigned long long wg_base;
-    if (sg.ctr[1] != 0) return;
+    if (sg.ctr[SKM_CTR_FAIL] != 0) return;
     lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     if (threadIdx.x < SKM_ROUTE_MAX_DEST) { lo[threadIdx.x] = rs.bs * (uint64_t)threadIdx.x; dcount[threadIdx.x] = 0; }
     if (threadIdx.x == 0) { wg_items = 0; wg_cur = 0; }
     __syncthreads();
-    unsigned long long n = sg.ctr[0];
+    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
     if (n > sg.loose_cap) n = sg.loose_cap;
     const int k = sg.k, recw = sg.lrecw;
     // Every item here goes to the sink's overflow list.  Its slots are reserved ONCE per workgroup (the k-mers of the workgroup's records
@@ -1748,7 +1763,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_route(SkmGeom sg, HashParams 
         if (mine) atomicAdd(&wg_items, mine);
     }
     __syncthreads();
-    if (threadIdx.x == 0) wg_base = wg_items ? atomicAdd(&rs.ctr[1], (unsigned long long)wg_items) : 0ull;
+    if (threadIdx.x == 0) wg_base = wg_items ? atomicAdd(&rs.ctr[ROUTE_CTR_OVERFLOW], (unsigned long long)wg_items) : 0ull;
     __syncthreads();
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t *rec = sg.loose + i * (uint64_t)recw;
@@ -1772,7 +1787,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_route(SkmGeom sg, HashParams 
         }
     }
     __syncthreads();
-    if (threadIdx.x < (uint32_t)rs.ndest && dcount[threadIdx.x]) atomicAdd(&rs.ctr[18 + threadIdx.x], (unsigned long long)dcount[threadIdx.x]);
+    if (threadIdx.x < (uint32_t)rs.ndest && dcount[threadIdx.x]) atomicAdd(&rs.ctr[ROUTE_CTR_DEST0 + threadIdx.x], (unsigned long long)dcount[threadIdx.x]);
 }
 
 // ---- S6: novel ------------------------------------------------------------------------------------------
@@ -1798,7 +1813,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
     if (threadIdx.x < 256) lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     load_descs(ns, p);
     const int k = sg.k;
-    if (threadIdx.x == 0) next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt;
+    if (threadIdx.x == 0) next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
     for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
         __syncthreads();
         const uint32_t b = next_bucket;
@@ -1808,17 +1823,17 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, Reads
         __syncthreads();
         if (threadIdx.x == 0) {
             if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
+            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
             else {
-                const unsigned long long ticket = atomicAdd(&sg.ctr[4], 1ull);
+                const unsigned long long ticket = atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull);
                 next_bucket = (uint32_t)ticket * sg.bpt;
                 // the count pass's early exit, for a scan that cut the batch itself: once 2 % of the buckets are done, more than
                 // 4 % of their k-mers outside the tables (a batch of low coverage: nearly every k-mer distinct) raise the flag --
                 // the caller then scans tile by tile, and remembers -- instead of pushing the whole batch through the loose list
                 const unsigned long long done = ticket * sg.bpt;
                 if (done * 50ull >= sg.n_buckets) {
-                    const unsigned long long now = __hip_atomic_load(&sg.ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[6];
-                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[1] = 1;
+                    const unsigned long long now = __hip_atomic_load(&sg.ctr[SKM_CTR_LOOSE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[SKM_CTR_LOOSE_S12];
+                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[SKM_CTR_FAIL] = 1;
                 }
             }
             any_hit = 0;
@@ -1905,7 +1920,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
     uint32_t *scratch = dyn;
     load_descs(ns, p);
     skm_table_clear(itb);
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt; n_int = 0; n_cand = 0; }
+    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt; n_int = 0; n_cand = 0; }
     auto mark_pass = [&](uint32_t b) {
         skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
             if (skm_cacheable<KW>(c) && skm_table_find(itb, c) >= 0) skm_mark(p, rd, pos, sg.stride);
@@ -1924,8 +1939,8 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
         __syncthreads();
         if (threadIdx.x == 0) {
             if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt;
+            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
+            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
             n_cand = 0;
         }
         // the first list entries are requested before the controls' lists are worked in: they arrive meanwhile
@@ -1954,13 +1969,13 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
             }
         }
         __syncthreads();
-        for (uint32_t base = 0; base < en; base += E * SKM_THREADS3) {
-            if (base) request(base);
+        for (uint32_t e0 = 0; e0 < en; e0 += E * SKM_THREADS3) {
+            if (e0) request(e0);
             bool live[E];
             uint32_t v[E];
 #pragma unroll
             for (uint32_t u = 0; u < E; ++u) {
-                live[u] = base + u * SKM_THREADS3 + threadIdx.x < en && skm_table_find(rtb, c[u]) < 0 && band_pass(p, h[u]);
+                live[u] = e0 + u * SKM_THREADS3 + threadIdx.x < en && skm_table_find(rtb, c[u]) < 0 && band_pass(p, h[u]);
                 if (p.case0_bits) {
                     const uint64_t bin = fastmod(h[u], ns.d[0].size, ns.d[0].magic);
                     const __attribute__((address_space(1))) uint32_t *bits = (const __attribute__((address_space(1))) uint32_t *)p.case0_bits;
@@ -1971,7 +1986,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
             }
 #pragma unroll
             for (uint32_t u = 0; u < E; ++u)
-                if (live[u] && (int)v[u] >= p.case_min) cand[atomicAdd(&n_cand, 1u)] = (uint16_t)(base + u * SKM_THREADS3 + threadIdx.x);
+                if (live[u] && (int)v[u] >= p.case_min) cand[atomicAdd(&n_cand, 1u)] = (uint16_t)(e0 + u * SKM_THREADS3 + threadIdx.x);
         }
         __syncthreads();
         const uint32_t nc = n_cand;
@@ -1984,7 +1999,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, 
                 if (KW == 2) c.w[KW - 1] = sg.dl_keys[(uint64_t)(e0 + i) * KW + (KW - 1)];
                 const uint64_t h = sg.dl_hash[e0 + i];
                 if (novel_test_wide(ns, p, h)) {
-                    if (skm_table_insert(itb, c) < 0) sg.ctr[1] = 1;          // (cannot happen below half full; the caller then redoes the scan the other way)
+                    if (skm_table_insert(itb, c) < 0) sg.ctr[SKM_CTR_FAIL] = 1;          // (cannot happen below half full; the caller then redoes the scan the other way)
                     atomicAdd(&n_int, 1u);
                     if (p.ab_keys) (void)ab_claim(p, h, p.ncase + p.nctrl);      // a place for its abundances (k_ab_fill), for the kernel that reports the hits
                 }
@@ -2030,7 +2045,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_novel(SkmGeom sg, ReadsDev rd
     lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     load_descs(ns, p);
     __syncthreads();
-    unsigned long long n = sg.ctr[0];
+    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
     if (n > sg.loose_cap) n = sg.loose_cap;
     const int k = sg.k, recw = sg.lrecw;
     const uint32_t lane = threadIdx.x & 63u;
@@ -2103,7 +2118,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, No
     extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
     uint32_t *scratch = dyn;
     skm_table_clear(itb);
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt; n_int = 0; n_hit = 0; }
+    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt; n_int = 0; n_hit = 0; }
     for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
         __syncthreads();
         const uint32_t b = next_bucket;
@@ -2112,7 +2127,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, No
         if (threadIdx.x == 0) {
             if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
             else if (taken + 1 >= sg.quota3) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[4], 1ull) * sg.bpt;
+            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
         }
         const uint32_t e0 = sg.dl_bstart[b], en = sg.dl_bcount[b];
         for (uint32_t i = threadIdx.x; i < en; i += SKM_THREADS3) {
@@ -2123,7 +2138,7 @@ __global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, No
             c.w[0] = sg.dl_keys[(uint64_t)(e0 + i) * KW];
             if (KW == 2) c.w[KW - 1] = sg.dl_keys[(uint64_t)(e0 + i) * KW + (KW - 1)];
             const int at = skm_table_insert(itb, c);
-            if (at < 0) { sg.ctr[1] = 1; continue; }            // more members than the table takes: the caller scans the other way
+            if (at < 0) { sg.ctr[SKM_CTR_FAIL] = 1; continue; }            // more members than the table takes: the caller scans the other way
             islot[at] = (uint32_t)slot;
             atomicAdd(&n_int, 1u);
         }
@@ -2157,7 +2172,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_set_hits(SkmGeom sg, NovelPar
     __shared__ uint32_t lut[256];
     lut[threadIdx.x] = skm_ascii4(threadIdx.x);
     __syncthreads();
-    unsigned long long n = sg.ctr[0];
+    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
     if (n > sg.loose_cap) n = sg.loose_cap;
     const int k = sg.k, recw = sg.lrecw;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -2180,7 +2195,7 @@ __global__ __launch_bounds__(256) void k_skm_loose_set_hits(SkmGeom sg, NovelPar
 
 __global__ void k_skm_forward_flag(const unsigned long long *skm_ctr, unsigned long long *bin_ctr)
 {
-    if (skm_ctr[1] != 0) bin_ctr[1] = 1;
+    if (skm_ctr[SKM_CTR_FAIL] != 0) bin_ctr[BIN_CTR_FAIL] = 1;
 }
 
 // hits per tile = set bits of the tile's range of the mask (what k_novel_mark counts while it marks)
@@ -2208,6 +2223,47 @@ __global__ __launch_bounds__(64) void k_tile_hits(ReadsDev rd, NovelParams p)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------
+// Bump pointer over an arena, every part rounded up to 256 bytes.  Without a base it only adds up: a layout written once as a function
+// of an SkmCarve gives the total for KvArena::need and then the pointers, and the two cannot drift apart.
+struct SkmCarve {
+    unsigned char *base;
+    size_t total = 0;
+    explicit SkmCarve(void *arena = nullptr) : base((unsigned char *)arena) {}
+    template <typename T> T *take(size_t bytes) { T *p = (T *)base; bytes = kv_round_up(bytes, 256); total += bytes; if (base) base += bytes; return p; }
+};
+
+// the parts of a list the count pass writes: `entries` keys of kw words, a V beside each, first entry and entry count of every bucket
+template <typename V> size_t skm_list_lay(SkmCarve c, uint64_t entries, int kw, uint32_t n_buckets, uint64_t **keys, V **vals, uint32_t **bstart, uint32_t **bcount)
+{
+    *keys = c.take<uint64_t>(entries * 8 * kw); *vals = c.take<V>(entries * sizeof(V));
+    *bstart = c.take<uint32_t>((uint64_t)n_buckets * 4); *bcount = c.take<uint32_t>((uint64_t)n_buckets * 4);
+    return c.total;
+}
+// (the two bucket arrays lie one behind the other)
+hipError_t skm_list_zero(uint32_t *bstart, uint32_t *bcount, hipStream_t st) { return hipMemsetAsync(bstart, 0, (size_t)((unsigned char *)bcount - (unsigned char *)bstart) * 2, st); }
+
+// The distinct list as the host holds it; SkmGeom::dl_* is the copy a kernel receives while the list is attached.
+struct SkmDistinctList {
+    uint64_t *keys = nullptr, *hash = nullptr;
+    uint32_t *bstart = nullptr, *bcount = nullptr;
+    uint32_t cap_wg = 0, chunk = 0, nchunks = 0;
+    static size_t bytes(uint64_t entries, int kw, uint32_t n_buckets) { SkmDistinctList l; return skm_list_lay(SkmCarve(), entries, kw, n_buckets, &l.keys, &l.hash, &l.bstart, &l.bcount); }
+    // room for `entries` k-mers in `arena`, the bucket arrays zeroed; KV_ERR_CAPACITY: the arena cannot grow to it
+    int carve(KvArena &arena, uint64_t entries, int kw, uint32_t n_buckets, uint32_t cap_wg_, uint32_t chunk_, uint32_t nchunks_, hipStream_t st)
+    {
+        if (arena.need(bytes(entries, kw, n_buckets)) != hipSuccess) return KV_ERR_CAPACITY;
+        skm_list_lay(SkmCarve(arena.p), entries, kw, n_buckets, &keys, &hash, &bstart, &bcount);
+        cap_wg = cap_wg_; chunk = chunk_; nchunks = nchunks_;
+        KV_HIP(skm_list_zero(bstart, bcount, st));
+        return KV_OK;
+    }
+    void attach(SkmGeom &g) const { g.dl_keys = keys; g.dl_hash = hash; g.dl_bstart = bstart; g.dl_bcount = bcount; g.dl_cap_wg = cap_wg; g.dl_chunk = chunk; g.dl_nchunks = nchunks; }
+    static void detach(SkmGeom &g) { g.dl_keys = nullptr; g.dl_hash = nullptr; g.dl_bstart = nullptr; g.dl_bcount = nullptr; }
+};
+// the abundance list a sketch keeps (KvAbundList, which owns its memory) goes to the kernels the same way
+void skm_abl_attach(const KvAbundList &al, SkmGeom &g) { g.abl_keys = al.keys; g.abl_cnts = al.cnts; g.abl_bstart = al.bstart; g.abl_bcount = al.bcount; g.abl_cap_wg = (uint32_t)al.cap_wg; }
+void skm_abl_detach(SkmGeom &g) { g.abl_keys = nullptr; g.abl_cnts = nullptr; g.abl_bstart = nullptr; g.abl_bcount = nullptr; }
+
 // The bucketed form of the last batch consumed on a stream stays in that stream's arena, so a scan of the same
 // batch (the case sample: count, then novel) does not cut its reads again.
 struct SkmIndex {
@@ -2221,14 +2277,17 @@ struct SkmIndex {
     KvArena dl;
     size_t dl_refused = SIZE_MAX;    // the smallest list kv_skm_mex_route asked for and did not get since the arena was last empty (a refused
                                      // allocation of tens of gigabytes takes a third of a second, and the arena is given up for the attempt)
-    uint64_t *dl_keys = nullptr, *dl_hash = nullptr;
-    uint32_t *dl_bstart = nullptr, *dl_bcount = nullptr;
-    uint32_t dl_cap_wg = 0;
+    SkmDistinctList list;
     bool dl_valid = false;
     bool mex_scan_ready = false;     // the arena holds an owner's combined buckets with their distinct list (kv_skm_mex_route, keep_scan): kv_skm_mex_scan_set
     uint64_t builds = 0;             // batches bucketed on this stream so far
     KvArena bits;                    // NovelParams::case0_bits of the scan in flight
     std::mutex mu;
+    // what a later call on the stream may reuse (valid, mex_scan_ready, dl_valid): a function that writes over one of them drops it first
+    enum { BATCH = 1, MEX_SCAN = 2, LIST = 4, ALL = 7 };
+    void drop(int what) { valid &= !(what & BATCH); mex_scan_ready &= !(what & MEX_SCAN); dl_valid &= !(what & LIST); }
+    // nothing to reuse, and the bucket and list arenas go back to the device
+    void give_back() { drop(ALL); arena.release(); dl.release(); list = SkmDistinctList(); }
 };
 std::map<hipStream_t, SkmIndex> g_skm;
 std::mutex g_skm_mu;
@@ -2249,9 +2308,8 @@ void kv_skm_scratch_release()
     for (auto &kv : g_skm) {
         SkmIndex &idx = kv.second;
         std::lock_guard<std::mutex> ilk(idx.mu);
-        idx.valid = false; idx.dl_valid = false; idx.mex_scan_ready = false;
-        idx.dl_keys = nullptr; idx.dl_hash = nullptr; idx.dl_bstart = nullptr; idx.dl_bcount = nullptr;
-        idx.arena.release(); idx.dl.release(); idx.bits.release();
+        idx.give_back();
+        idx.bits.release();
     }
 }
 namespace {
@@ -2267,13 +2325,39 @@ inline uint32_t skm_nwg3(const SkmGeom &g)
 // device-wide, measured: a sample's 64 k buckets one per ticket took k_skm_count from 3.1 to 6.9 ms, two per ticket to 3.7 -- and a big
 // ticket leaves a tail (16: +0.08 ms, 32: +0.13).  8 for a whole sample; fewer where the buckets are few (a rank's share of the exchange:
 // 7 936 buckets for 768 workgroups -- tickets of 8 give a quarter of them two and the rest one), down to 2.
-static void skm_pick_bpt(SkmGeom &g)
+// A workgroup takes at most quota3 buckets: one and a half even shares, in whole tickets.
+static void skm_plan_tickets(SkmGeom &g)
 {
     g.bpt = SKM_BUCKETS_PER_TICKET;
     while (g.bpt > 2u && g.n_buckets / g.bpt < 4u * 768u) g.bpt /= 2u;
+    const uint32_t nwg3 = skm_nwg3(g);
+    const uint64_t avg = (g.n_buckets + nwg3 - 1) / nwg3;
+    g.quota3 = (uint32_t)kv_round_up(avg + avg / 2 + 1, g.bpt);
 }
 
 inline uint32_t pow2_ceil(uint64_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+
+// nfine fine buckets as C1 coarse buckets of F2 = 2^fbits each.  At most 255 x 4096 buckets (a bucket id travels as 20 bits through
+// S1): 8.5 G k-mers at 8192 per bucket; bigger batches get bigger buckets, which only costs deduplication efficiency
+static void skm_bucket_grid(uint64_t nfine, uint32_t *C1, uint32_t *F2, uint32_t *fbits)
+{
+    *F2 = std::min<uint32_t>(512u, pow2_ceil((uint64_t)std::ceil(std::sqrt((double)nfine))));
+    if (nfine > 255ull * *F2) *F2 = std::min<uint32_t>(SKM_MAX_F2, pow2_ceil((nfine + 254) / 255));
+    *fbits = 0;
+    while ((1u << *fbits) < *F2) ++*fbits;
+    *C1 = (uint32_t)std::min<uint64_t>(255, std::max<uint64_t>(1, (nfine + *F2 - 1) / *F2));
+}
+
+// records: one run per ~ (w + 1) / 2 k-mers, one more per read, a few cuts at ncap
+static double skm_rec_est(uint64_t n_kmers, double n_reads, int w) { return (double)n_kmers * 2.2 / (double)(w + 1) + n_reads + 1024.0; }
+// records per private segment for a mean of `mean`: `slack` times that and eight standard deviations
+static uint32_t skm_seg_cap(double mean, double slack, uint64_t floor) { return (uint32_t)kv_round_up((uint64_t)(mean * slack + 8.0 * std::sqrt(mean)) + floor, 16); }
+// loose records: segment overflow (whole records) and occurrences that missed a full LDS table (one k-mer each)
+static uint64_t skm_loose_cap(double rec_est, uint64_t n_kmers) { return (uint64_t)(rec_est / 8.0) + n_kmers / 16 + (1u << 20); }
+// words of record-start bits per wave in the bucket walk
+static uint32_t skm_sbw(int ncap) { return ((64u * (uint32_t)ncap) >> 5) + 2u; }
+// 16-byte records without positions (kv_skm_device.h): shorter records, fewer k-mers in each
+static void skm_make_compact(SkmGeom &g) { g.compact = 1u; g.recw = 2; g.ncap = std::min(g.ncap, SKM_C_BASES + 1 - g.k); g.sbw = skm_sbw(g.ncap); }
 
 int skm_minimizer_len(int k) { return k >= 24 ? 12 : k / 2; }
 
@@ -2360,13 +2444,9 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
         return;
     }
     const size_t lds = ((size_t)g.np_max / 16 + KV_TILE_MAX_READS + 8 + (size_t)g.np_max + 96) * 4 + (((size_t)g.np_max + 96 + 1) & ~(size_t)1) * 2;
-    if (g.w > 16) {
-        kv_ensure_dynamic_lds((const void *)k_skm_emit<16>, lds);
-        hipLaunchKernelGGL(k_skm_emit<16>, dim3(g.nwg1), dim3(SKM_THREADS1), lds, st, reads_dev(reads), reads->n_tiles, g);
-    } else {
-        kv_ensure_dynamic_lds((const void *)k_skm_emit<8>, lds);
-        hipLaunchKernelGGL(k_skm_emit<8>, dim3(g.nwg1), dim3(SKM_THREADS1), lds, st, reads_dev(reads), reads->n_tiles, g);
-    }
+    void (*kernel)(ReadsDev, uint32_t, SkmGeom) = g.w > 16 ? k_skm_emit<16> : k_skm_emit<8>;
+    kv_ensure_dynamic_lds((const void *)kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(SKM_THREADS1), lds, st, reads_dev(reads), reads->n_tiles, g);
 }
 
 void skm_launch_split(const SkmGeom &g, hipStream_t st)
@@ -2377,21 +2457,25 @@ void skm_launch_split(const SkmGeom &g, hipStream_t st)
     const bool sorted = s2 ? strcmp(s2, "sorted") == 0 && g.F2 <= SKM_S2_MAXF : g.F2 <= SKM_S2_MAXF;
     if (sorted) {
         const size_t lds = (size_t)SKM_S2_CHUNK * g.recw * 8;
-        if (g.recw == 2) {
-            kv_ensure_dynamic_lds((const void *)k_skm_split_sorted<2>, lds);
-            hipLaunchKernelGGL(k_skm_split_sorted<2>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
-        } else if (g.recw == 3) {
-            kv_ensure_dynamic_lds((const void *)k_skm_split_sorted<3>, lds);
-            hipLaunchKernelGGL(k_skm_split_sorted<3>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
-        } else {
-            kv_ensure_dynamic_lds((const void *)k_skm_split_sorted<4>, lds);
-            hipLaunchKernelGGL(k_skm_split_sorted<4>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
-        }
+        void (*kernel)(SkmGeom) = g.recw == 2 ? k_skm_split_sorted<2> : k_skm_split_sorted<3>;
+        if (g.recw > 3) kernel = k_skm_split_sorted<4>;
+        kv_ensure_dynamic_lds((const void *)kernel, lds);
+        hipLaunchKernelGGL(kernel, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
     } else {
         if (g.recw == 2) hipLaunchKernelGGL(k_skm_split<true>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), 0, st, g);
         else hipLaunchKernelGGL(k_skm_split<false>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), 0, st, g);
     }
 }
+
+// a loose-list kernel, grid-stride over the list: its instance for one-word or two-word keys
+template <typename... A>
+void skm_launch_loose(void (*one)(SkmGeom, A...), void (*two)(SkmGeom, A...), hipStream_t st, const SkmGeom &g, typename std::common_type<A>::type... args)
+{
+    hipLaunchKernelGGL(g.kw == 1 ? one : two, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, args...);
+}
+
+// occurrences the bucket kernels sent through the loose list (they missed a full LDS table), from a host copy of the counters
+double skm_outside_tables(const unsigned long long *c) { return (double)(c[SKM_CTR_LOOSE] > c[SKM_CTR_LOOSE_S12] ? c[SKM_CTR_LOOSE] - c[SKM_CTR_LOOSE_S12] : 0); }
 
 // Exclusive prefix of n counts, off[n] = total -- n is the number of exchange segments, a couple of hundred thousand: chunks of 1024
 // scanned side by side (k_mex_scan_chunks), the chunk totals by one workgroup (k_mex_scan_parts), the bases added (k_mex_scan_add).
@@ -2423,8 +2507,8 @@ __global__ __launch_bounds__(1024) void k_mex_scan_parts(uint64_t *part, uint64_
     if (threadIdx.x == 0) carry_sh = 0;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t base = 0; base < n_parts; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
+    for (uint64_t first = 0; first < n_parts; first += 1024) {
+        const uint64_t i = first + threadIdx.x;
         const uint64_t v = i < n_parts ? part[i] : 0ull;
         uint64_t incl = v;
 #pragma unroll
@@ -2489,7 +2573,7 @@ void skm_geom_k(SkmGeom &g, int k)
     g.recw = 1 + g.nbw;
     g.lrecw = g.recw;
     g.ncap = 32 * g.nbw - k + 1;
-    g.sbw = ((64u * (uint32_t)g.ncap) >> 5) + 2u;
+    g.sbw = skm_sbw(g.ncap);
     g.bpt = SKM_BUCKETS_PER_TICKET;
 }
 
@@ -2506,15 +2590,12 @@ __global__ void k_mex_sum_kmers(const uint64_t *seg, const uint32_t *cnt, const 
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(out, mine);
 }
 
-
 // cut `reads` into super-k-mers and bucket them (S1 + S2); idx.mu held by the caller
 // distinct_frac: the share of distinct k-mers the caller expects (0: sequencing coverage of a whole sample, ~0.3)
 int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hipStream_t st, double distinct_frac = 0.0, bool want_pos = true)
 {
     SkmGeom &g = idx.g;
-    idx.valid = false;
-    idx.mex_scan_ready = false;
-    idx.dl_valid = false;
+    idx.drop(SkmIndex::ALL);
     idx.builds += 1;
     skm_geom_k(g, k);
     g.force_loose = kv_knob("KV_SKM_FORCE_LOOSE") ? 1u : 0u;
@@ -2539,21 +2620,12 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
         if (g_skm_pref_k == k && g_skm_pref_nfine && nfine * 4 >= g_skm_pref_nfine * 3 && nfine * 4 <= g_skm_pref_nfine * 5) nfine = g_skm_pref_nfine;
         else { g_skm_pref_k = k; g_skm_pref_nfine = nfine; }
     }
-    // at most 255 x 4096 buckets (a bucket id travels as 20 bits through S1): 8.5 G k-mers at 8192 per bucket; bigger
-    // batches get bigger buckets, which only costs deduplication efficiency
-    g.F2 = std::min<uint32_t>(512u, pow2_ceil((uint64_t)std::ceil(std::sqrt((double)nfine))));
-    if (nfine > 255ull * g.F2) g.F2 = std::min<uint32_t>(SKM_MAX_F2, pow2_ceil((nfine + 254) / 255));
-    g.fbits = 0;
-    while ((1u << g.fbits) < g.F2) ++g.fbits;
-    g.C1 = (uint32_t)std::min<uint64_t>(255, std::max<uint64_t>(1, (nfine + g.F2 - 1) / g.F2));
+    skm_bucket_grid(nfine, &g.C1, &g.F2, &g.fbits);
     g.n_buckets = g.C1 * g.F2;
     // 16-byte records without positions (kv_skm_device.h) when nobody will ask where a k-mer was: the count of a sample that is not
     // scanned from this very batch.  The lane-per-read S1 writes them, the sorted S2 moves them, k_skm_count reads them
-    {
-        const char *s2 = kv_knob("KV_SKM_S2");
-        g.compact = (!want_pos && g.kw == 1 && k + 1 <= SKM_C_BASES && skm_lane_fits(g, reads) && g.F2 <= SKM_S2_MAXF && !(s2 && strcmp(s2, "sorted") != 0)) ? 1u : 0u;
-        if (g.compact) { g.recw = 2; g.ncap = std::min(g.ncap, SKM_C_BASES + 1 - k); }
-    }
+    const char *s2 = kv_knob("KV_SKM_S2");
+    if (!want_pos && g.kw == 1 && k + 1 <= SKM_C_BASES && skm_lane_fits(g, reads) && g.F2 <= SKM_S2_MAXF && !(s2 && strcmp(s2, "sorted") != 0)) skm_make_compact(g);
     const int cus = kv_device_cus();
     // at least one whole ticket per workgroup: the per-writer capacities below assume even shares
     g.nwg1 = (uint32_t)std::min<uint64_t>((std::max<uint32_t>(reads->n_tiles, 1u) + SKM_TILES_PER_TICKET - 1) / SKM_TILES_PER_TICKET,
@@ -2565,66 +2637,53 @@ int skm_build(SkmIndex &idx, const kv_reads *reads, int k, uint64_t n_kmers, hip
         int ch_unused = 16;
         if (skm_wave_threads() == 1024 && skm_wave_plan(g, reads, &ch_unused)) g.nwg1 = std::min<uint32_t>(g.nwg1, (uint32_t)cus);
     }
-    {
-        const uint64_t avg = (reads->n_tiles + g.nwg1 - 1) / g.nwg1;
-        g.quota1 = (uint32_t)std::min<uint64_t>(kv_round_up(avg + avg / 2 + 1, SKM_TILES_PER_TICKET), 0xfffffff0ull);
-    }
+    const uint64_t avg1 = (reads->n_tiles + g.nwg1 - 1) / g.nwg1;
+    g.quota1 = (uint32_t)std::min<uint64_t>(kv_round_up(avg1 + avg1 / 2 + 1, SKM_TILES_PER_TICKET), 0xfffffff0ull);
     g.nwg2 = std::max<uint32_t>(1u, std::min<uint32_t>(16u, 1024u / g.C1));
     g.nwg2 = std::min<uint32_t>(g.nwg2, g.nwg1);
     g.np_max = std::max<uint32_t>(reads->tile_max_bases, 64u);
-    const uint64_t min_stride = reads->max_len >= (uint32_t)k ? reads->max_len - (uint32_t)k + 1 : 1;
-    g.stride = min_stride;
-    // records: one run per ~ (w + 1) / 2 k-mers, one more per read, a few cuts at ncap
-    const double rec_est = (double)n_kmers * 2.2 / (double)(g.w + 1) + (double)reads->n_reads + 1024.0;
-    const double m1 = rec_est / ((double)g.C1 * g.nwg1), m2 = rec_est / ((double)g.n_buckets * g.nwg2);
-    g.cap1 = (uint32_t)kv_round_up((uint64_t)(m1 * 1.5 + 8.0 * std::sqrt(m1)) + 64, 16);
-    g.cap2 = (uint32_t)kv_round_up((uint64_t)(m2 * 1.3 + 8.0 * std::sqrt(m2)) + 32, 16);
-    // loose records: segment overflow (whole records) and occurrences that missed a full LDS table (one k-mer each)
-    g.loose_cap = (uint64_t)(rec_est / 8.0) + n_kmers / 16 + (1u << 20);
+    g.stride = reads->max_len >= (uint32_t)k ? reads->max_len - (uint32_t)k + 1 : 1;
+    const double rec_est = skm_rec_est(n_kmers, (double)reads->n_reads, g.w);
+    g.cap1 = skm_seg_cap(rec_est / ((double)g.C1 * g.nwg1), 1.5, 64);
+    g.cap2 = skm_seg_cap(rec_est / ((double)g.n_buckets * g.nwg2), 1.3, 32);
+    g.loose_cap = skm_loose_cap(rec_est, n_kmers);
     if (const char *pct = kv_knob("KV_SKM_CAP_PCT")) {       // tests: undersized segments push records through the loose list
         g.cap1 = std::max<uint32_t>(16u, (uint32_t)((uint64_t)g.cap1 * (uint64_t)atoi(pct) / 100));
         g.cap2 = std::max<uint32_t>(16u, (uint32_t)((uint64_t)g.cap2 * (uint64_t)atoi(pct) / 100));
     }
     if (const char *lc = kv_knob("KV_SKM_LOOSE_CAP")) g.loose_cap = strtoull(lc, nullptr, 10);
-    const size_t rb = (size_t)g.recw * 8;
-    const size_t b_seg1 = kv_round_up((uint64_t)g.C1 * g.nwg1 * g.cap1 * rb, 256), b_cnt1 = kv_round_up((uint64_t)g.C1 * g.nwg1 * 4, 256);
-    const size_t b_seg2 = kv_round_up((uint64_t)g.n_buckets * g.nwg2 * g.cap2 * rb, 256), b_cnt2 = kv_round_up((uint64_t)g.n_buckets * g.nwg2 * 4, 256);
-    const size_t b_loose = kv_round_up(g.loose_cap * (size_t)g.lrecw * 8, 256), b_ctr = 256;
+    const size_t rb = (size_t)g.recw * 8, b_ctr = 256;
+    auto lay = [&](SkmCarve c) {
+        g.seg1 = c.take<uint64_t>((uint64_t)g.C1 * g.nwg1 * g.cap1 * rb);
+        g.cnt1 = c.take<uint32_t>((uint64_t)g.C1 * g.nwg1 * 4);
+        g.seg2 = c.take<uint64_t>((uint64_t)g.n_buckets * g.nwg2 * g.cap2 * rb);
+        g.cnt2 = c.take<uint32_t>((uint64_t)g.n_buckets * g.nwg2 * 4);
+        g.loose = c.take<uint64_t>(g.loose_cap * (size_t)g.lrecw * 8);
+        g.ctr = c.take<unsigned long long>(b_ctr);
+        return c.total;
+    };
+    const size_t b_all = lay(SkmCarve());
     // (no memory for the buckets -- three samples cut side by side in batches of tens of millions of reads -- is a CAPACITY answer: the batch
     // takes the plain partition, or the tile scan, as it does when a buffer runs over)
-    if (idx.arena.need(b_seg1 + b_cnt1 + b_seg2 + b_cnt2 + b_loose + b_ctr) != hipSuccess) {
+    if (idx.arena.need(b_all) != hipSuccess) {
         (void)hipGetLastError();
-        idx.valid = false; idx.mex_scan_ready = false; idx.dl_valid = false;
-        kv_set_error("no device memory for the super-k-mer buckets (%.1f GB)", (double)(b_seg1 + b_cnt1 + b_seg2 + b_cnt2 + b_loose + b_ctr) / 1e9);
+        kv_set_error("no device memory for the super-k-mer buckets (%.1f GB)", (double)b_all / 1e9);
         return KV_ERR_CAPACITY;
     }
-    unsigned char *base = (unsigned char *)idx.arena.p;
-    g.seg1 = (uint64_t *)base; base += b_seg1;
-    g.cnt1 = (uint32_t *)base; base += b_cnt1;
+    lay(SkmCarve(idx.arena.p));
     g.seg1_wmajor = 1u;
-    g.seg2 = (uint64_t *)base; base += b_seg2;
-    g.cnt2 = (uint32_t *)base; base += b_cnt2;
-    g.loose = (uint64_t *)base; base += b_loose;
-    g.ctr = (unsigned long long *)base;
     KV_HIP(hipMemsetAsync(g.ctr, 0, b_ctr, st));
-    g.sbw = ((64u * (uint32_t)g.ncap) >> 5) + 2u;
     g.bucket_kmers = std::max<uint64_t>(1, n_kmers / g.n_buckets);
     skm_launch_emit(g, reads, st);
     skm_launch_split(g, st);
     KV_HIP(hipGetLastError());
-    KV_HIP(hipMemcpyAsync(&g.ctr[6], &g.ctr[0], 8, hipMemcpyDeviceToDevice, st));   // loose records S1/S2 left behind
-    skm_pick_bpt(g);
-    const uint32_t nwg3 = skm_nwg3(g);
-    {
-        const uint64_t avg = (g.n_buckets + nwg3 - 1) / nwg3;
-        g.quota3 = (uint32_t)kv_round_up(avg + avg / 2 + 1, g.bpt);
-    }
+    KV_HIP(hipMemcpyAsync(&g.ctr[SKM_CTR_LOOSE_S12], &g.ctr[SKM_CTR_LOOSE], 8, hipMemcpyDeviceToDevice, st));   // loose records S1/S2 left behind
+    skm_plan_tickets(g);
     idx.reads_uid = reads->uid;
     idx.k = k;
     idx.valid = true;
     return KV_OK;
 }
-
 
 }  // namespace
 
@@ -2670,10 +2729,7 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
     auto no_memory = [&](int rc) {
         s->skm_off = true;
         s->skm_off_kmers = n_kmers;
-        idx.valid = false; idx.mex_scan_ready = false; idx.dl_valid = false;
-        idx.arena.release();
-        idx.dl.release();
-        idx.dl_keys = nullptr; idx.dl_hash = nullptr; idx.dl_bstart = nullptr; idx.dl_bcount = nullptr;
+        idx.give_back();
         if (kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] no memory for the bucketed count of this batch: the plain partition, and the stream's bucket buffers are given back\n");
         return rc;
     };
@@ -2702,9 +2758,7 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         if (!al.valid && !s->scan_hint) {            // (a case sample's list would never be asked for: it is scanned, not scanned against)
             const uint64_t cap_total = std::min<uint64_t>(std::max<uint64_t>(n_kmers / 8, 1u << 16), 0xfffffff0ull);
             const uint64_t cap_wg = std::max<uint64_t>(64, cap_total / nwg3);
-            const size_t b_keys = kv_round_up(cap_wg * nwg3 * 8 * sg.kw, 256), b_cnts = kv_round_up(cap_wg * nwg3, 256);
-            const size_t b_idx = kv_round_up((uint64_t)sg.n_buckets * 4, 256);
-            const size_t need = b_keys + b_cnts + 2 * b_idx;
+            const size_t need = skm_list_lay(SkmCarve(), cap_wg * nwg3, sg.kw, sg.n_buckets, &al.keys, &al.cnts, &al.bstart, &al.bcount);
             if (al.bytes < need) {
                 if (al.mem) (void)hipFree(al.mem);
                 al.mem = nullptr; al.bytes = 0;
@@ -2712,22 +2766,18 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
                 else (void)hipGetLastError();              // no room: no list, nothing else changes
             }
             if (al.mem) {
-                unsigned char *base = (unsigned char *)al.mem;
-                al.keys = (uint64_t *)base; base += b_keys;
-                al.cnts = (uint8_t *)base; base += b_cnts;
-                al.bstart = (uint32_t *)base; base += b_idx;
-                al.bcount = (uint32_t *)base;
-                KV_HIP(hipMemsetAsync(al.bstart, 0, 2 * b_idx, st));
+                skm_list_lay(SkmCarve(al.mem), cap_wg * nwg3, sg.kw, sg.n_buckets, &al.keys, &al.cnts, &al.bstart, &al.bcount);
+                KV_HIP(skm_list_zero(al.bstart, al.bcount, st));
                 al.k = k; al.m = sg.m; al.kw = sg.kw; al.C1 = sg.C1; al.F2 = sg.F2; al.fbits = sg.fbits; al.n_buckets = sg.n_buckets;
                 al.nwg = nwg3; al.cap_wg = cap_wg; al.cap_total = cap_wg * nwg3;
-                sg.abl_keys = al.keys; sg.abl_cnts = al.cnts; sg.abl_bstart = al.bstart; sg.abl_bcount = al.bcount; sg.abl_cap_wg = (uint32_t)cap_wg;
+                skm_abl_attach(al, sg);
                 abl_new = true;
             }
         }
     }
     // distinct list (kv_sketch_scan_hint): the batch is a case sample's and will be scanned next.  A workgroup takes up to
     // quota3 of the buckets, so its stretch holds one and a half average shares of the distinct k-mers the batch is expected
-    // to have (what the previous batch showed, or 30 %); a stretch that runs out drops the list (ctr[9]), nothing else.
+    // to have (what the previous batch showed, or 30 %); a stretch that runs out drops the list (SKM_CTR_DL_RAN_OUT), nothing else.
     // The first batch a stream ever buckets gets no list unless the room is there already: allocating a gigabyte or two costs
     // tens of milliseconds, more than the list saves once -- a one-shot `kevlar novel` is exactly that case -- while a process
     // that counts and scans sample after sample pays it once (KV_SKM_DL=1: always, =0: never).
@@ -2736,22 +2786,11 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
     if (s->scan_hint && !(dl_env && atoi(dl_env) == 0)) {
         const double frac = std::min(1.0, std::max(0.3, s->skm_distinct * 1.15));
         const uint64_t cap_wg = std::min<uint64_t>((uint64_t)((double)n_kmers * frac * 1.6 / nwg3) + 4096, 0xfffffff0ull / nwg3);
-        const size_t b_keys = kv_round_up(cap_wg * nwg3 * 8 * sg.kw, 256), b_hash = kv_round_up(cap_wg * nwg3 * 8, 256);
-        const size_t b_idx = kv_round_up((uint64_t)sg.n_buckets * 4, 256);
-        const bool worth = (dl_env && atoi(dl_env) == 1) || s->scan_steady || idx.builds > 1 || idx.dl.bytes >= b_keys + b_hash + 2 * b_idx;
-        if (worth && idx.dl.need(b_keys + b_hash + 2 * b_idx) == hipSuccess) {
-            unsigned char *base = (unsigned char *)idx.dl.p;
-            idx.dl_keys = (uint64_t *)base; base += b_keys;
-            idx.dl_hash = (uint64_t *)base; base += b_hash;
-            idx.dl_bstart = (uint32_t *)base; base += b_idx;
-            idx.dl_bcount = (uint32_t *)base;
-            idx.dl_cap_wg = (uint32_t)cap_wg;
-            KV_HIP(hipMemsetAsync(idx.dl_bstart, 0, 2 * b_idx, st));
-            sg.dl_keys = idx.dl_keys; sg.dl_hash = idx.dl_hash; sg.dl_bstart = idx.dl_bstart; sg.dl_bcount = idx.dl_bcount; sg.dl_cap_wg = idx.dl_cap_wg;
-            dl_new = true;
-        } else {
-            (void)hipGetLastError();                    // no room: no list
-        }
+        const bool worth = (dl_env && atoi(dl_env) == 1) || s->scan_steady || idx.builds > 1 || idx.dl.bytes >= SkmDistinctList::bytes(cap_wg * nwg3, sg.kw, sg.n_buckets);
+        const int lrc = worth ? idx.list.carve(idx.dl, cap_wg * nwg3, sg.kw, sg.n_buckets, (uint32_t)cap_wg, 0, 0, st) : KV_ERR_CAPACITY;
+        if (lrc != KV_OK && lrc != KV_ERR_CAPACITY) return lrc;
+        if (lrc == KV_OK) { idx.list.attach(sg); dl_new = true; }
+        else (void)hipGetLastError();                   // no room: no list
     }
     {
         KvProfScope prof("k_skm_count");
@@ -2774,28 +2813,27 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
     }
     {
         KvProfScope prof("k_skm_loose_count");
-        if (sg.kw == 1) hipLaunchKernelGGL(k_skm_loose_count<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
-        else hipLaunchKernelGGL(k_skm_loose_count<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
+        skm_launch_loose(k_skm_loose_count<1>, k_skm_loose_count<2>, st, sg, s->d_desc, d_mask, filter, plan.g);
     }
     KV_HIP(hipGetLastError());
     // a lost record (loose list overflow) must stop the apply stage, which looks at the partition's own flag
     hipLaunchKernelGGL(k_skm_forward_flag, dim3(1), dim3(1), 0, st, sg.ctr, plan.g.ctr);
     KV_HIP(hipGetLastError());
-    sg.abl_keys = nullptr; sg.abl_cnts = nullptr; sg.abl_bstart = nullptr; sg.abl_bcount = nullptr;
-    sg.dl_keys = nullptr; sg.dl_hash = nullptr; sg.dl_bstart = nullptr; sg.dl_bcount = nullptr;
+    skm_abl_detach(sg);
+    SkmDistinctList::detach(sg);
     const int rc = kv_bin_finish(s, plan, true, 0, n_added);     // synchronises the stream
     if (abl_new) s->abl.valid = rc == KV_OK;
     {
         // what the batch looked like: if most k-mers are distinct (low coverage per batch) cutting and bucketing the
         // reads buys nothing, and if many occurrences missed the LDS tables the buckets were too full; either way
         // the next batches into this sketch take the one-item-per-k-mer partition (until the sketch is cleared)
-        unsigned long long sc[10] = {0};
+        unsigned long long sc[SKM_CTR_DL_RAN_OUT + 1] = {0};
         const bool got = hipMemcpy(sc, sg.ctr, sizeof(sc), hipMemcpyDeviceToHost) == hipSuccess;
-        idx.dl_valid = dl_new && got && rc == KV_OK && sc[9] == 0;
-        if (dl_new && kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] distinct list: %s (%llu workgroups ran out of %u entries)\n", idx.dl_valid ? "kept" : "dropped", sc[9], idx.dl_cap_wg);
+        idx.dl_valid = dl_new && got && rc == KV_OK && sc[SKM_CTR_DL_RAN_OUT] == 0;
+        if (dl_new && kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] distinct list: %s (%llu workgroups ran out of %u entries)\n", idx.dl_valid ? "kept" : "dropped", sc[SKM_CTR_DL_RAN_OUT], idx.list.cap_wg);
         if (got && n_kmers) {
-            const double alone = (double)(sc[0] > sc[6] ? sc[0] - sc[6] : 0) / (double)n_kmers;
-            const double distinct = (double)sc[7] / (double)n_kmers + alone;
+            const double alone = skm_outside_tables(sc) / (double)n_kmers;
+            const double distinct = (double)sc[SKM_CTR_DISTINCT] / (double)n_kmers + alone;
             s->skm_off = rc != KV_OK || alone > 0.03 || distinct > 0.45;
             // (what the batch itself showed -- or buffers sized for sequencing coverage running over, which is how a batch without repeats ends:
             // its figures are then those of an aborted count -- not an error of another kind)
@@ -2804,19 +2842,18 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
             { std::lock_guard<std::mutex> glk(g_skm_mu); g_skm_last_distinct = distinct; }
             if (kv_knob("KV_SKM_VERBOSE"))
                 fprintf(stderr, "[kv_skm] batch of %llu k-mers: %.1f%% distinct, %.2f%% outside the LDS tables, %llu of %llu records (%d bytes each) outside their segments%s\n",
-                        (unsigned long long)n_kmers, 100 * distinct, 100 * alone, sc[6], sc[5], 8 * sg.recw,
+                        (unsigned long long)n_kmers, 100 * distinct, 100 * alone, sc[SKM_CTR_LOOSE_S12], sc[SKM_CTR_RECORDS], 8 * sg.recw,
                         s->skm_off ? " -> next batches take the plain partition" : "");
         }
     }
     if (rc != KV_OK) {
-        idx.valid = false;
-        idx.mex_scan_ready = false;
+        idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
         if (kv_knob("KV_SKM_VERBOSE")) {
-            unsigned long long sc[8] = {0}, bc[4] = {0};
+            unsigned long long sc[SKM_CTR_DISTINCT + 1] = {0}, bc[4] = {0};
             (void)hipMemcpy(sc, sg.ctr, sizeof(sc), hipMemcpyDeviceToHost);
             (void)hipMemcpy(bc, plan.g.ctr, sizeof(bc), hipMemcpyDeviceToHost);
             fprintf(stderr, "[kv_skm] count fell back: rc %d, loose %llu of %llu (flag %llu), records %llu, spill %llu of %llu (flag %llu); C1 %u F2 %u nwg1 %u nwg2 %u cap1 %u cap2 %u\n",
-                    rc, sc[0], (unsigned long long)sg.loose_cap, sc[1], sc[5], bc[0], (unsigned long long)plan.g.spill_cap, bc[1],
+                    rc, sc[SKM_CTR_LOOSE], (unsigned long long)sg.loose_cap, sc[SKM_CTR_FAIL], sc[SKM_CTR_RECORDS], bc[0], (unsigned long long)plan.g.spill_cap, bc[1],
                     sg.C1, sg.F2, sg.nwg1, sg.nwg2, sg.cap1, sg.cap2);
         }
     }
@@ -2825,10 +2862,7 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         // nothing to combine: the gigabytes the attempt took (records twice over with their slack: 30 GB per stream for a 37.5 M-read
         // batch of config 4, which is what kept batches of twice the size from fitting beside the resident reads) go back now instead of
         // waiting for kv_scratch_trim.
-        idx.valid = false; idx.mex_scan_ready = false; idx.dl_valid = false;
-        idx.arena.release();
-        idx.dl.release();
-        idx.dl_keys = nullptr; idx.dl_hash = nullptr; idx.dl_bstart = nullptr; idx.dl_bcount = nullptr;
+        idx.give_back();
         if (kv_knob("KV_SKM_VERBOSE")) fprintf(stderr, "[kv_skm] the stream's bucket buffers are given back\n");
     }
     return rc;
@@ -2880,12 +2914,12 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     // the count pass of this very batch left key + hash of every distinct k-mer (kv_sketch_scan_hint): scan from that list
     const bool from_list = reuse && idx->dl_valid && !p.set_keys && !(kv_knob("KV_SKM_DL") && atoi(kv_knob("KV_SKM_DL")) == 0);
     if (reuse) {
-        // records that did not fit their S1/S2 segment are the first ctr[6] entries of the loose list; the entries the
+        // records that did not fit their S1/S2 segment are the first SKM_CTR_LOOSE_S12 entries of the loose list; the entries the
         // count pass added behind them (single occurrences that missed its LDS tables) are re-created by the scan's
         // own pass 0, so the list is cut back to what S1/S2 left -- unless the scan goes by the distinct list, which does
         // not hold those k-mers: then they stay, and k_skm_loose_novel evaluates them
-        if (!from_list) KV_HIP(hipMemcpyAsync(&sg.ctr[0], &sg.ctr[6], 8, hipMemcpyDeviceToDevice, st));
-        KV_HIP(hipMemsetAsync(&sg.ctr[4], 0, 8, st));
+        if (!from_list) KV_HIP(hipMemcpyAsync(&sg.ctr[SKM_CTR_LOOSE], &sg.ctr[SKM_CTR_LOOSE_S12], 8, hipMemcpyDeviceToDevice, st));
+        KV_HIP(hipMemsetAsync(&sg.ctr[SKM_CTR_TICKET_SCAN], 0, 8, st));
     }
     const uint32_t nwg3 = skm_nwg3(sg);
     const ReadsDev rd = reads_dev(reads);
@@ -2910,8 +2944,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     if (from_list && p.host_case0 && !(kv_knob("KV_NOVEL_BITS") && atoi(kv_knob("KV_NOVEL_BITS")) == 0)) {
         const kv_sketch *c0 = (const kv_sketch *)p.host_case0;
         if (c0->h.storage == ST_BYTE && !c0->lazy_zero && idx->bits.need(kv_round_up(((c0->h.size[0] + 31) >> 5) * 4, 256)) == hipSuccess) {
-            KvProfScope prof("k_case_bits");
-            hipLaunchKernelGGL(k_case_bits, dim3(4096), dim3(256), 0, st, (const uint8_t *)c0->h.tab[0], (uint64_t)c0->h.size[0], p.case_min, (uint32_t *)idx->bits.p);
+            kv_case_bits_launch((const uint8_t *)c0->h.tab[0], (uint64_t)c0->h.size[0], p.case_min, (uint32_t *)idx->bits.p, st);
             pl.case0_bits = (const uint32_t *)idx->bits.p;
         } else {
             (void)hipGetLastError();
@@ -2919,7 +2952,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     }
     if (from_list) {
         KvProfScope prof("k_skm_novel_list");
-        sg.dl_keys = idx->dl_keys; sg.dl_hash = idx->dl_hash; sg.dl_bstart = idx->dl_bstart; sg.dl_bcount = idx->dl_bcount; sg.dl_cap_wg = idx->dl_cap_wg;
+        idx->list.attach(sg);
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
         void (*kernel)(SkmGeom, ReadsDev, NovelParams, SkmAblSet) =
             sg.kw == 1 ? k_skm_novel_list<1, 2048> : k_skm_novel_list<2, 1024>;
@@ -2930,7 +2963,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
             if (hipMemcpyAsync(&claimed, p.ab_count, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
                 fprintf(stderr, "[kv_skm] scan: %u interesting k-mers hold a slot for their abundances (the list takes %u)\n", claimed, p.ab_list_cap);
         }
-        sg.dl_keys = nullptr; sg.dl_hash = nullptr; sg.dl_bstart = nullptr; sg.dl_bcount = nullptr;
+        SkmDistinctList::detach(sg);
     } else {
         KvProfScope prof("k_skm_novel");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
@@ -2939,25 +2972,22 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     }
     {
         KvProfScope prof("k_skm_loose_novel");
-        if (sg.kw == 1) hipLaunchKernelGGL(k_skm_loose_novel<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, rd, p);
-        else hipLaunchKernelGGL(k_skm_loose_novel<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, rd, p);
+        skm_launch_loose(k_skm_loose_novel<1>, k_skm_loose_novel<2>, st, sg, rd, p);
     }
-    {
-        KvProfScope prof("k_tile_hits");
-        hipLaunchKernelGGL(k_tile_hits, dim3(reads->n_tiles), dim3(64), 0, st, rd, p);
-    }
+    kv_tile_hits_launch(reads, p, st);
     KV_HIP(hipGetLastError());
-    unsigned long long sctr[2] = {0, 0};
+    unsigned long long sctr[SKM_CTR_FAIL + 1] = {0, 0};
     KV_HIP(hipMemcpyAsync(sctr, sg.ctr, sizeof(sctr), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
-    idx->valid = false;     // one scan per build: the loose list now holds this scan's entries
-    idx->dl_valid = false;
-    if (sctr[1] != 0) {
-        kv_set_error("super-k-mer scan: loose record list overflow (%llu records)", sctr[0]);
+    idx->drop(SkmIndex::BATCH | SkmIndex::LIST);     // one scan per build: the loose list now holds this scan's entries
+    if (sctr[SKM_CTR_FAIL] != 0) {
+        kv_set_error("super-k-mer scan: loose record list overflow (%llu records)", sctr[SKM_CTR_LOOSE]);
         return KV_ERR_CAPACITY;
     }
     return KV_OK;
 }
+
+static void skm_launch_route(void (*kernel)(SkmGeom, HashParams, KvRouteSink), const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st);
 
 int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, int ndest,
                           int (*alloc)(void *ctx, uint32_t nwg, KvRouteSink *sink), void *ctx)
@@ -2972,37 +3002,37 @@ int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, in
     KvRouteSink rs;
     memset(&rs, 0, sizeof(rs));
     { const int rc = alloc(ctx, nwg3, &rs); if (rc != KV_OK) return rc; }
-    const HashParams hp = make_hash_params(ksize, HF_MURMUR);
-    {
-        KvProfScope prof("k_skm_route");
-        const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
-        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
-        else hipLaunchKernelGGL((k_skm_route<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, hp, rs);
-    }
-    {
-        KvProfScope prof("k_skm_loose_route");
-        if (sg.kw == 1) hipLaunchKernelGGL(k_skm_loose_route<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, hp, rs);
-        else hipLaunchKernelGGL(k_skm_loose_route<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, hp, rs);
-    }
+    skm_launch_route(sg.kw == 1 ? k_skm_route<1, 4096> : k_skm_route<2, 2048>, sg, ksize, rs, st);
     KV_HIP(hipGetLastError());
-    unsigned long long sctr[8] = {0};
+    unsigned long long sctr[SKM_CTR_DISTINCT + 1] = {0};
     KV_HIP(hipMemcpyAsync(sctr, sg.ctr, sizeof(sctr), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     // the next shard routed on this stream (same sample or a sibling: same coverage) gets buckets sized for what this one held
-    const double alone = (double)(sctr[0] > sctr[6] ? sctr[0] - sctr[6] : 0) / (double)n_kmers;
-    idx.distinct_hint = std::min(1.0, (double)sctr[7] / (double)n_kmers + alone);
+    const double alone = skm_outside_tables(sctr) / (double)n_kmers;
+    idx.distinct_hint = std::min(1.0, (double)sctr[SKM_CTR_DISTINCT] / (double)n_kmers + alone);
     if (kv_knob("KV_SKM_VERBOSE"))
         fprintf(stderr, "[kv_skm] routed %llu k-mers: %.1f%% distinct, %.2f%% outside the LDS tables, %u buckets\n",
                 (unsigned long long)n_kmers, 100 * idx.distinct_hint, 100 * alone, sg.n_buckets);
-    if (sctr[1] != 0) {
-        idx.valid = false;
-        idx.mex_scan_ready = false;
-        kv_set_error("super-k-mer route: loose record list overflow (%llu records)", sctr[0]);
+    if (sctr[SKM_CTR_FAIL] != 0) {
+        idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
+        kv_set_error("super-k-mer route: loose record list overflow (%llu records)", sctr[SKM_CTR_LOOSE]);
         return KV_ERR_CAPACITY;
     }
     return KV_OK;
 }
 
+// the buckets' distinct k-mers through `kernel`, the instance of k_skm_route for the geometry, then the loose list's
+static void skm_launch_route(void (*kernel)(SkmGeom, HashParams, KvRouteSink), const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st)
+{
+    const HashParams hp = make_hash_params(k, HF_MURMUR);
+    {
+        KvProfScope prof("k_skm_route");
+        const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(g.sbw)) * 4;
+        hipLaunchKernelGGL(kernel, dim3(skm_nwg3(g)), dim3(SKM_THREADS3), lds, st, g, hp, rs);
+    }
+    KvProfScope prof("k_skm_loose_route");
+    skm_launch_loose(k_skm_loose_route<1>, k_skm_loose_route<2>, st, g, hp, rs);
+}
 
 // ---- minimizer-sharded exchange (kevlar_amd/shardrun.py) ------------------------------------------------
 // N ranks each hold 1/N of a sample's reads.  Deduplicating a shard on its own finds little to combine at 1/8 of the
@@ -3021,13 +3051,10 @@ int kv_skm_mex_plan(int ksize, uint64_t n_reads_global, uint32_t read_len, int n
     const uint32_t table_slots = g.kw == 1 ? 4096u : 2048u;
     const uint64_t target = g.kw == 1 ? 2ull * table_slots : table_slots + table_slots / 2;       // a whole sample at sequencing coverage (~0.2 distinct)
     const uint64_t nfine = std::max<uint64_t>(1, (n_kmers + target - 1) / target);
-    uint32_t F2 = std::min<uint32_t>(512u, pow2_ceil((uint64_t)std::ceil(std::sqrt((double)nfine))));
-    if (nfine > 255ull * F2) F2 = std::min<uint32_t>(SKM_MAX_F2, pow2_ceil((nfine + 254) / 255));
-    uint32_t C1 = (uint32_t)std::min<uint64_t>(255, std::max<uint64_t>(1, (nfine + F2 - 1) / F2));
+    uint32_t C1, F2, fbits;
+    skm_bucket_grid(nfine, &C1, &F2, &fbits);
     C1 = (uint32_t)kv_round_up(C1, (uint64_t)ndest);
     if (C1 > 255u) C1 = 255u / (uint32_t)ndest * (uint32_t)ndest;
-    uint32_t fbits = 0;
-    while ((1u << fbits) < F2) ++fbits;
     const uint64_t shard_reads = (n_reads_global + ndest - 1) / ndest;
     const uint64_t tiles = (shard_reads + KV_TILE_MAX_READS - 1) / KV_TILE_MAX_READS;
     // Writers per shard; every one owns a segment of every coarse bucket.  One per CU, 1024 threads each: a shard is an N-th of a
@@ -3036,9 +3063,8 @@ int kv_skm_mex_plan(int ksize, uint64_t n_reads_global, uint32_t read_len, int n
     // 7.73 / 23.10 with 256 of 1024).
     const uint64_t nwg1_max = 256;
     const uint32_t nwg1 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tiles + SKM_TILES_PER_TICKET - 1) / SKM_TILES_PER_TICKET, nwg1_max));
-    const double rec_est = (double)(shard_reads * nk_read) * 2.2 / (double)(g.w + 1) + (double)shard_reads + 1024.0;
-    const double m1 = rec_est / ((double)C1 * nwg1);
-    const uint32_t cap1 = (uint32_t)kv_round_up((uint64_t)(m1 * 2.0 + 8.0 * std::sqrt(m1)) + 64, 16);
+    const double rec_est = skm_rec_est(shard_reads * nk_read, (double)shard_reads, g.w);
+    const uint32_t cap1 = skm_seg_cap(rec_est / ((double)C1 * nwg1), 2.0, 64);
     plan->ksize = ksize; plan->ndest = ndest; plan->C1 = C1; plan->F2 = F2; plan->fbits = fbits; plan->nwg1 = nwg1; plan->cap1 = cap1;
     plan->recw = (uint32_t)g.recw; plan->m = (uint32_t)g.m;
     plan->seg_words = (uint64_t)C1 * nwg1 * cap1 * g.recw;
@@ -3064,10 +3090,13 @@ int kv_skm_mex_plan_short(kv_mex_plan *plan)
     plan->recw = 2u;
     return KV_OK;
 }
-// what the plan's flags mean for the geometry
-static void skm_mex_apply_flags(SkmGeom &g, const kv_mex_plan *plan)
+// what a plan fixes of the geometry, for C1 of its coarse buckets: all of them where a shard is cut, the owner's share where they are combined
+static void skm_geom_plan(SkmGeom &g, const kv_mex_plan *plan, uint32_t C1)
 {
-    if (plan->flags & 1u) { g.compact = 1u; g.recw = 2; g.ncap = std::min(g.ncap, SKM_C_BASES + 1 - g.k); g.sbw = ((64u * (uint32_t)g.ncap) >> 5) + 2u; }
+    skm_geom_k(g, plan->ksize);
+    if (plan->flags & 1u) skm_make_compact(g);
+    g.C1 = C1; g.F2 = plan->F2; g.fbits = plan->fbits; g.n_buckets = C1 * g.F2;
+    g.nwg1 = plan->nwg1; g.cap1 = plan->cap1; g.stride = plan->read_len - (uint32_t)plan->ksize + 1u;
 }
 
 // S1 of one shard into the caller's buffers ([C1][nwg1][cap1] records, [C1][nwg1] counts: what the plan says).
@@ -3079,16 +3108,11 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
     hipStream_t st = kv_stream();
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
-    idx.valid = false;
-    idx.mex_scan_ready = false;
+    idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
     SkmGeom &g = idx.g;
-    skm_geom_k(g, plan->ksize);
-    skm_mex_apply_flags(g, plan);
-    g.C1 = plan->C1; g.F2 = plan->F2; g.fbits = plan->fbits; g.n_buckets = g.C1 * g.F2;
-    g.nwg1 = plan->nwg1; g.cap1 = plan->cap1;
+    skm_geom_plan(g, plan, plan->C1);
     g.quota1 = 0xfffffff0u;                                   // tiles are dealt dynamically; the plan's capacity has the slack
     g.np_max = std::max<uint32_t>(reads->tile_max_bases, 64u);
-    g.stride = plan->read_len - (uint32_t)plan->ksize + 1u;
     KV_REQUIRE(reads->max_len <= plan->read_len, KV_ERR_ARG, "kv_mex_emit: a read of %u bases in a plan for %u", reads->max_len, plan->read_len);
     // (a rank whose shard holds no read -- fewer reads than ranks -- still takes part: it sends empty segments)
     KV_REQUIRE(reads->n_tiles == 0 || (reads->tile_max_bases > 0 && reads->tile_max_bases <= 8192u), KV_ERR_ARG, "kv_mex_emit: reads too long for the super-k-mer front end");
@@ -3097,20 +3121,23 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
     // k-mer under one key whichever shard it came from)
     g.seg1 = d_seg; g.cnt1 = d_cnt;
     g.loose_cap = 1u << 16;
-    const size_t b_loose = kv_round_up(g.loose_cap * (size_t)g.lrecw * 8, 256), b_ctr = 256;
+    const size_t b_ctr = 256;
     const uint64_t n_seg = plan->cnt_entries;
     // (a shard without reads cuts nothing and fits any plan)
     KV_REQUIRE(!g.compact || reads->n_tiles == 0 || skm_lane_fits(g, reads), KV_ERR_NOTIMPL, "kv_mex_emit: 16-byte records need a shard of equal-length reads (the lane-per-read cut)");
-    const size_t b_off = d_out ? mex_scan_bytes(n_seg) : 0;
-    KV_HIP(idx.arena.need(b_loose + b_ctr + b_off));
-    g.loose = (uint64_t *)idx.arena.p;
-    g.ctr = (unsigned long long *)((unsigned char *)idx.arena.p + b_loose);
-    uint64_t *d_off = d_out ? (uint64_t *)((unsigned char *)idx.arena.p + b_loose + b_ctr) : nullptr;
+    uint64_t *d_off = nullptr;
+    auto lay = [&](SkmCarve c) {
+        g.loose = c.take<uint64_t>(g.loose_cap * (size_t)g.lrecw * 8);
+        g.ctr = c.take<unsigned long long>(b_ctr);
+        if (d_out) d_off = c.take<uint64_t>(mex_scan_bytes(n_seg));
+        return c.total;
+    };
+    KV_HIP(idx.arena.need(lay(SkmCarve())));
+    lay(SkmCarve(idx.arena.p));
     KV_HIP(hipMemsetAsync(g.ctr, 0, b_ctr, st));
     // a workgroup that takes no tile still writes its counts; workgroups beyond the grid never run: zero them
     KV_HIP(hipMemsetAsync(d_cnt, 0, plan->cnt_entries * 4, st));
     if (reads->n_tiles) {
-        g.nwg1 = plan->nwg1;
         tl_s1_threads = plan->nwg1 <= 256u ? 1024u : 0u;
         skm_launch_emit(g, reads, st);
         tl_s1_threads = 0;
@@ -3125,7 +3152,7 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
     }
     KvReadback rb;
     hipError_t rb_err = hipSuccess;
-    const unsigned long long *ctr = rb.add(g.ctr, 2, st, &rb_err);
+    const unsigned long long *ctr = rb.add(g.ctr, SKM_CTR_FAIL + 1, st, &rb_err);
     std::vector<const uint64_t *> bounds(plan->ndest + 1, nullptr);
     if (d_out)
         for (int d = 0; d <= plan->ndest; ++d) bounds[d] = rb.add(d_off + (uint64_t)plan->c_lo[d] * plan->nwg1, 1, st, &rb_err);
@@ -3137,7 +3164,7 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
     }
     // records that miss their segment have nowhere to travel in: the plan's capacity is twice the expected fill, so this
     // means a pathological input (one minimizer everywhere); no silent change of layout
-    KV_REQUIRE(ctr[0] == 0 && ctr[1] == 0, KV_ERR_CAPACITY, "kv_mex_emit: %llu records did not fit their exchange segment", ctr[0]);
+    KV_REQUIRE(ctr[SKM_CTR_LOOSE] == 0 && ctr[SKM_CTR_FAIL] == 0, KV_ERR_CAPACITY, "kv_mex_emit: %llu records did not fit their exchange segment", ctr[SKM_CTR_LOOSE]);
     // a later scan of this shard against the set of interesting k-mers buckets the shard on its own: 1 / ndest of the coverage
     // leaves more of its k-mers distinct than the sample's ~20 % (measured: 30 / 33 / 49 % at 1/2, 1/4, 1/8 of 30x)
     { std::lock_guard<std::mutex> glk(g_skm_mu); g_skm_last_distinct = std::min(0.9, 0.2 * std::sqrt((double)plan->ndest)); }
@@ -3153,17 +3180,13 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
     hipStream_t st = kv_stream();
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
-    idx.valid = false;
-    idx.mex_scan_ready = false;
+    idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
     SkmGeom &g = idx.g;
-    skm_geom_k(g, plan->ksize);
-    skm_mex_apply_flags(g, plan);
-    KV_REQUIRE(!(g.compact && keep_scan), KV_ERR_ARG, "kv_mex_route: the sample the scan is answered from needs records with positions (not a short-record plan)");
     const uint32_t Cl = plan->c_lo[my_dest + 1] - plan->c_lo[my_dest];
-    g.C1 = Cl; g.F2 = plan->F2; g.fbits = plan->fbits; g.n_buckets = Cl * g.F2;
-    g.nwg1 = plan->nwg1; g.cap1 = plan->cap1; g.n_src = (uint32_t)n_src;
+    skm_geom_plan(g, plan, Cl);
+    KV_REQUIRE(!(g.compact && keep_scan), KV_ERR_ARG, "kv_mex_route: the sample the scan is answered from needs records with positions (not a short-record plan)");
+    g.n_src = (uint32_t)n_src;
     g.seg1 = const_cast<uint64_t *>(d_recv_seg); g.cnt1 = const_cast<uint32_t *>(d_recv_cnt);
-    g.stride = plan->read_len - (uint32_t)plan->ksize + 1u;
     if (Cl == 0) { *n_kmers_in = 0; KvRouteSink rs; memset(&rs, 0, sizeof(rs)); return alloc(ctx, 1, &rs); }
     const uint32_t nseg = g.nwg1 * g.n_src;
     g.nwg2 = std::max<uint32_t>(std::max<uint32_t>(1u, std::min<uint32_t>(16u, 1024u / Cl)), (nseg + 767u) / 768u);
@@ -3171,24 +3194,24 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
     KV_REQUIRE((nseg + g.nwg2 - 1) / g.nwg2 <= 768u, KV_ERR_ARG, "kv_mex_route: %u segments per bucket", nseg);
     // this rank's share of the sample: its buckets hold 1 / ndest of the k-mers, give or take the hash's evenness
     const uint64_t n_kmers_exp = plan->n_kmers_global / (uint64_t)plan->ndest + 1;
-    const double rec_est = (double)n_kmers_exp * 2.2 / (double)(g.w + 1) + (double)plan->n_reads_global / plan->ndest + 1024.0;
-    const double m2 = rec_est / ((double)g.n_buckets * g.nwg2);
+    const double rec_est = skm_rec_est(n_kmers_exp, (double)plan->n_reads_global / plan->ndest, g.w);
     // (a geometry at its limit -- 4096 fine buckets per coarse one: a handful of distinct 12-base minimizers per bucket -- has buckets of
     // very different sizes: at 248 x 4096 buckets a tenth of the records missed segments of 2 x the even share)
     const double slack2 = plan->F2 > SKM_S2_MAXF ? 3.0 : 1.4;
-    g.cap2 = (uint32_t)kv_round_up((uint64_t)(m2 * slack2 + 8.0 * std::sqrt(m2)) + 32, 16);
-    g.loose_cap = (uint64_t)(rec_est / 8.0) + n_kmers_exp / 16 + (1u << 20);
-    const size_t rb = (size_t)g.recw * 8;
-    const size_t b_seg2 = kv_round_up((uint64_t)g.n_buckets * g.nwg2 * g.cap2 * rb, 256), b_cnt2 = kv_round_up((uint64_t)g.n_buckets * g.nwg2 * 4, 256);
-    const size_t b_loose = kv_round_up(g.loose_cap * (size_t)g.lrecw * 8, 256), b_ctr = 256;
-    const size_t b_off = compact ? mex_scan_bytes((uint64_t)Cl * nseg) : 0;
-    KV_HIP(idx.arena.need(b_seg2 + b_cnt2 + b_loose + b_off + b_ctr));
-    unsigned char *base = (unsigned char *)idx.arena.p;
-    g.seg2 = (uint64_t *)base; base += b_seg2;
-    g.cnt2 = (uint32_t *)base; base += b_cnt2;
-    g.loose = (uint64_t *)base; base += b_loose;
-    uint64_t *d_off = compact ? (uint64_t *)base : nullptr; base += b_off;
-    g.ctr = (unsigned long long *)base;
+    g.cap2 = skm_seg_cap(rec_est / ((double)g.n_buckets * g.nwg2), slack2, 32);
+    g.loose_cap = skm_loose_cap(rec_est, n_kmers_exp);
+    const size_t rb = (size_t)g.recw * 8, b_ctr = 256;
+    uint64_t *d_off = nullptr;
+    auto lay = [&](SkmCarve c) {
+        g.seg2 = c.take<uint64_t>((uint64_t)g.n_buckets * g.nwg2 * g.cap2 * rb);
+        g.cnt2 = c.take<uint32_t>((uint64_t)g.n_buckets * g.nwg2 * 4);
+        g.loose = c.take<uint64_t>(g.loose_cap * (size_t)g.lrecw * 8);
+        if (compact) d_off = c.take<uint64_t>(mex_scan_bytes((uint64_t)Cl * nseg));
+        g.ctr = c.take<unsigned long long>(b_ctr);
+        return c.total;
+    };
+    KV_HIP(idx.arena.need(lay(SkmCarve())));
+    lay(SkmCarve(idx.arena.p));
     KV_HIP(hipMemsetAsync(g.ctr, 0, b_ctr, st));
     g.bucket_kmers = std::max<uint64_t>(1, n_kmers_exp / g.n_buckets);
     {
@@ -3207,28 +3230,23 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
         g.seg1_off = d_off;
     }
     // how many k-mer occurrences arrived (the caller's buffer must hold a pair for each in the worst case)
-    hipLaunchKernelGGL(k_mex_sum_kmers, dim3(1024), dim3(256), 0, st, g.seg1, g.cnt1, g.seg1_off, (uint64_t)Cl * nseg, g.cap1, (uint32_t)g.recw, &g.ctr[8]);
+    hipLaunchKernelGGL(k_mex_sum_kmers, dim3(1024), dim3(256), 0, st, g.seg1, g.cnt1, g.seg1_off, (uint64_t)Cl * nseg, g.cap1, (uint32_t)g.recw, &g.ctr[SKM_CTR_ARRIVED]);
     skm_launch_split(g, st);
     KV_HIP(hipGetLastError());
-    KV_HIP(hipMemcpyAsync(&g.ctr[6], &g.ctr[0], 8, hipMemcpyDeviceToDevice, st));
-    skm_pick_bpt(g);
+    KV_HIP(hipMemcpyAsync(&g.ctr[SKM_CTR_LOOSE_S12], &g.ctr[SKM_CTR_LOOSE], 8, hipMemcpyDeviceToDevice, st));
+    skm_plan_tickets(g);
     const uint32_t nwg3 = skm_nwg3(g);
-    {
-        const uint64_t avg = (g.n_buckets + nwg3 - 1) / nwg3;
-        g.quota3 = (uint32_t)kv_round_up(avg + avg / 2 + 1, g.bpt);
-    }
     KvRouteSink rs;
     memset(&rs, 0, sizeof(rs));
     { const int rc = alloc(ctx, nwg3, &rs); if (rc != KV_OK) return rc; }
-    const HashParams hp = make_hash_params(plan->ksize, HF_MURMUR);
     // keep_scan (the case sample): key + hash of every distinct k-mer stay, bucket by bucket, and the buckets themselves stay where
     // they are -- this rank will answer the scan for its buckets (kv_skm_mex_scan_set).  A stretch holds one and a half average shares
-    // of 0.45 distinct k-mers per occurrence; one that runs out drops the list (ctr[9]) and the scan goes the other way.
+    // of 0.45 distinct k-mers per occurrence; one that runs out drops the list (SKM_CTR_DL_RAN_OUT) and the scan goes the other way.
     bool dl_new = false;
     const char *dl_why = "not asked for";
     // Room: 0.72 entries per occurrence in one stretch per workgroup covers a shard's 4-15 x with slack for uneven shares.  An owner of
     // config 4 holds 7.9 G occurrences at 30 x, a fifth of them distinct, and 16 bytes for each of 0.72 x 7.9 G entries is memory it does
-    // not have: half of that next, and last a POOL with room for 0.22 -- chunks the workgroups draw one after the other (ctr[13]), so that
+    // not have: half of that next, and last a POOL with room for 0.22 -- chunks the workgroups draw one after the other (SKM_CTR_POOL_CHUNKS), so that
     // what one workgroup needs beyond its even share comes out of what another leaves (a quarter more than the even share per workgroup
     // was not enough there: 12-base minimizers make a million buckets far from even).  KV_MEX_DL_POOL=1 (tests): the pool at once.
     static const double dl_room[3] = {0.72, 0.36, 0.22};
@@ -3246,9 +3264,7 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
             entries = nchunks * chunk;
             cap_wg = 0;
         }
-        const size_t b_keys = kv_round_up(entries * 8 * g.kw, 256), b_hash = kv_round_up(entries * 8, 256);
-        const size_t b_idx = kv_round_up((uint64_t)g.n_buckets * 4, 256);
-        const size_t b_all = b_keys + b_hash + 2 * b_idx;
+        const size_t b_all = SkmDistinctList::bytes(entries, g.kw, g.n_buckets);
         if (idx.dl.bytes == 0) idx.dl_refused = SIZE_MAX;
         if (b_all > idx.dl.bytes) {
             // not worth asking: refused before, or more than the device has left beside what the arena itself would give back
@@ -3258,16 +3274,10 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
                 continue;
             }
         }
-        if (idx.dl.need(b_all) == hipSuccess) {
-            unsigned char *dbase = (unsigned char *)idx.dl.p;
-            idx.dl_keys = (uint64_t *)dbase; dbase += b_keys;
-            idx.dl_hash = (uint64_t *)dbase; dbase += b_hash;
-            idx.dl_bstart = (uint32_t *)dbase; dbase += b_idx;
-            idx.dl_bcount = (uint32_t *)dbase;
-            idx.dl_cap_wg = (uint32_t)cap_wg;
-            KV_HIP(hipMemsetAsync(idx.dl_bstart, 0, 2 * b_idx, st));
-            g.dl_keys = idx.dl_keys; g.dl_hash = idx.dl_hash; g.dl_bstart = idx.dl_bstart; g.dl_bcount = idx.dl_bcount; g.dl_cap_wg = idx.dl_cap_wg;
-            g.dl_chunk = (uint32_t)chunk; g.dl_nchunks = (uint32_t)nchunks;
+        const int lrc = idx.list.carve(idx.dl, entries, g.kw, g.n_buckets, (uint32_t)cap_wg, (uint32_t)chunk, (uint32_t)nchunks, st);
+        if (lrc != KV_OK && lrc != KV_ERR_CAPACITY) return lrc;
+        if (lrc == KV_OK) {
+            idx.list.attach(g);      // (and stays attached: kv_skm_mex_scan_set works on a copy of this geometry)
             dl_new = true;
             dl_why = attempt == 0 ? "kept" : attempt == 1 ? "kept (room for 0.36 entries per occurrence)" : "kept (a pool of chunks the workgroups draw from)";
         } else {
@@ -3276,50 +3286,38 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
             idx.dl_refused = std::min(idx.dl_refused, b_all);
         }
     }
-    {
-        KvProfScope prof("k_skm_route");
-        const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(g.sbw)) * 4;
-        if (g.compact) hipLaunchKernelGGL((k_skm_route<1, 4096, true>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-        else if (g.kw == 1) hipLaunchKernelGGL((k_skm_route<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-        else hipLaunchKernelGGL((k_skm_route<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, g, hp, rs);
-    }
-    {
-        KvProfScope prof("k_skm_loose_route");
-        if (g.kw == 1) hipLaunchKernelGGL(k_skm_loose_route<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, hp, rs);
-        else hipLaunchKernelGGL(k_skm_loose_route<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, hp, rs);
-    }
+    skm_launch_route(g.compact ? k_skm_route<1, 4096, true> : g.kw == 1 ? k_skm_route<1, 4096> : k_skm_route<2, 2048>, g, plan->ksize, rs, st);
     KV_HIP(hipGetLastError());
     // the packing of the pairs (the caller's `after`) is queued behind the route kernels and everything is waited for once: its
     // kernels bound what they write by the output's capacity, so what the counters say can be judged afterwards
     if (after) { const int rc = after(ctx); if (rc != KV_OK) return rc; }
     KvReadback back;
     hipError_t rb_err = hipSuccess;
-    const unsigned long long *sctr = back.add(g.ctr, 14, st, &rb_err);
+    const unsigned long long *sctr = back.add(g.ctr, SKM_CTR_COUNT, st, &rb_err);
     KV_HIP(rb_err);
     KV_HIP(back.wait(st));
-    const unsigned long long arrived = sctr[8];
+    const unsigned long long arrived = sctr[SKM_CTR_ARRIVED];
     *n_kmers_in = arrived;
-    idx.mex_scan_ready = dl_new && sctr[9] == 0 && sctr[1] == 0;
+    idx.mex_scan_ready = dl_new && sctr[SKM_CTR_DL_RAN_OUT] == 0 && sctr[SKM_CTR_FAIL] == 0;
     idx.k = plan->ksize;
     if (kv_knob("KV_SKM_VERBOSE"))
         fprintf(stderr, "[kv_skm] exchange owner: %llu k-mers arrived in %u buckets (%u passes, segments of %u records), %.1f%% distinct, %.2f%% outside the LDS tables, "
                         "%llu records outside their bucket's segments\n",
-                arrived, g.n_buckets, g.passes, g.cap2, arrived ? 100.0 * (double)sctr[7] / (double)arrived : 0.0,
-                arrived ? 100.0 * (double)(sctr[0] > sctr[6] ? sctr[0] - sctr[6] : 0) / (double)arrived : 0.0, sctr[6]);
+                arrived, g.n_buckets, g.passes, g.cap2, arrived ? 100.0 * (double)sctr[SKM_CTR_DISTINCT] / (double)arrived : 0.0,
+                arrived ? 100.0 * skm_outside_tables(sctr) / (double)arrived : 0.0, sctr[SKM_CTR_LOOSE_S12]);
     if (keep_scan && kv_knob("KV_SKM_VERBOSE")) {
         fprintf(stderr, "[kv_skm] exchange owner: the distinct list its scan answers from: %s\n",
-                !dl_new ? dl_why : sctr[9] != 0 ? (g.dl_chunk ? "dropped (the pool of chunks ran out)" : "dropped (a workgroup's stretch ran out)")
-                                 : sctr[1] != 0 ? "dropped (loose list overflow)" : dl_why);
+                !dl_new ? dl_why : sctr[SKM_CTR_DL_RAN_OUT] != 0 ? (g.dl_chunk ? "dropped (the pool of chunks ran out)" : "dropped (a workgroup's stretch ran out)")
+                                 : sctr[SKM_CTR_FAIL] != 0 ? "dropped (loose list overflow)" : dl_why);
         if (dl_new && g.dl_chunk)
-            fprintf(stderr, "[kv_skm] exchange owner: %llu of %u chunks of %u entries drawn for %llu distinct k-mers\n", sctr[13], g.dl_nchunks, g.dl_chunk, sctr[7]);
+            fprintf(stderr, "[kv_skm] exchange owner: %llu of %u chunks of %u entries drawn for %llu distinct k-mers\n", sctr[SKM_CTR_POOL_CHUNKS], g.dl_nchunks, g.dl_chunk, sctr[SKM_CTR_DISTINCT]);
     }
-    if (sctr[1] != 0) {
-        kv_set_error("kv_mex_route: loose record list overflow (%llu records)", sctr[0]);
+    if (sctr[SKM_CTR_FAIL] != 0) {
+        kv_set_error("kv_mex_route: loose record list overflow (%llu records)", sctr[SKM_CTR_LOOSE]);
         return KV_ERR_CAPACITY;
     }
     return KV_OK;
 }
-
 
 // The hits of this rank's minimizer buckets against the gathered set of interesting hashes (p.set_*): see k_skm_set_hits.  Needs the
 // state kv_skm_mex_route(keep_scan) left on this stream; KV_ERR_CAPACITY when it is not there (or a bucket holds more members than its
@@ -3334,33 +3332,32 @@ int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8
         return KV_ERR_CAPACITY;
     }
     SkmGeom sg = idx.g;
-    sg.dl_keys = idx.dl_keys; sg.dl_hash = idx.dl_hash; sg.dl_bstart = idx.dl_bstart; sg.dl_bcount = idx.dl_bcount; sg.dl_cap_wg = idx.dl_cap_wg;
-    KV_HIP(hipMemsetAsync(&sg.ctr[4], 0, 8, st));
-    KV_HIP(hipMemsetAsync(&sg.ctr[10], 0, 8, st));
+    idx.list.attach(sg);
+    KV_HIP(hipMemsetAsync(&sg.ctr[SKM_CTR_TICKET_SCAN], 0, 8, st));
+    KV_HIP(hipMemsetAsync(&sg.ctr[SKM_CTR_SET_HITS], 0, 8, st));
     SetHitSink out;
-    out.tags = (unsigned long long *)d_tags; out.abund = d_abund; out.count = &sg.ctr[10]; out.cap = cap;
+    out.tags = (unsigned long long *)d_tags; out.abund = d_abund; out.count = &sg.ctr[SKM_CTR_SET_HITS]; out.cap = cap;
     const uint32_t nwg3 = skm_nwg3(sg);
     {
         KvProfScope prof("k_skm_set_hits");
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
         if (sg.kw == 1) hipLaunchKernelGGL((k_skm_set_hits<1, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
         else hipLaunchKernelGGL((k_skm_set_hits<2, 1024>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
-        if (sg.kw == 1) hipLaunchKernelGGL(k_skm_loose_set_hits<1>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, p, out);
-        else hipLaunchKernelGGL(k_skm_loose_set_hits<2>, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, sg, p, out);
+        skm_launch_loose(k_skm_loose_set_hits<1>, k_skm_loose_set_hits<2>, st, sg, p, out);
     }
     KV_HIP(hipGetLastError());
     KvReadback back;
     hipError_t rb_err = hipSuccess;
-    const unsigned long long *c = back.add(sg.ctr, 11, st, &rb_err);
+    const unsigned long long *c = back.add(sg.ctr, SKM_CTR_SET_HITS + 1, st, &rb_err);
     KV_HIP(rb_err);
     KV_HIP(back.wait(st));
-    if (c[1] != 0) {
-        idx.mex_scan_ready = false;
+    if (c[SKM_CTR_FAIL] != 0) {
+        idx.drop(SkmIndex::MEX_SCAN);
         kv_set_error("kv_mex_scan_set: a bucket holds more members of the set than its table takes");
         return KV_ERR_CAPACITY;
     }
-    KV_REQUIRE(c[10] <= cap, KV_ERR_CAPACITY, "kv_mex_scan_set: %llu hits exceed the buffer of %llu", c[10], (unsigned long long)cap);
-    *n_hits = c[10];
+    KV_REQUIRE(c[SKM_CTR_SET_HITS] <= cap, KV_ERR_CAPACITY, "kv_mex_scan_set: %llu hits exceed the buffer of %llu", c[SKM_CTR_SET_HITS], (unsigned long long)cap);
+    *n_hits = c[SKM_CTR_SET_HITS];
     return KV_OK;
 }
 
@@ -3374,7 +3371,7 @@ int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32
     const uint64_t n_seg = plan->cnt_entries;
     // the offsets go where the stream's bucketed batch lies: whatever that was -- a batch a scan could reuse, an owner's combined
     // buckets kept for kv_skm_mex_scan_set, a distinct list -- is gone after this call
-    idx.valid = false; idx.mex_scan_ready = false; idx.dl_valid = false;
+    idx.drop(SkmIndex::ALL);
     KV_HIP(idx.arena.need(mex_scan_bytes(n_seg)));
     uint64_t *d_off = (uint64_t *)idx.arena.p;
     mex_scan_launch(d_cnt, n_seg, plan->cap1, d_off, st);

@@ -375,6 +375,37 @@ def test_skm_scan_from_the_distinct_list_matches_oracle(hk, ok, skm, k):
     assert launches('k_skm_emit') == 3
 
 
+def test_exchange_packing_on_the_stream_drops_what_a_scan_could_have_reused(hk, ok, skm):
+    """kv_mex_pack writes its segment offsets where the stream's bucketed batch lies.  After it neither the case sample's buckets nor its
+    distinct list may be reused: the scan that follows cuts the reads again, walks the buckets, and finds the oracle's hits."""
+    import torch
+    os.environ['KV_SKM_BUCKET_KMERS'] = '2048'
+    k = 31
+    reads = trio_reads(100000, 20000, 41)
+    names = ('proband', 'mother', 'father')
+    os.environ['KV_SKM_DL'] = '1'
+    dev = {n: hk.Counttable(k, 1.5e6, 4) for n in names}
+    ref = {n: ok.Counttable(k, 1.5e6, 4) for n in names}
+    dev['proband'].expect_scan()
+    batches = {n: hk.ReadBatch(reads[n]) for n in names}
+    for n in ('mother', 'father', 'proband'):                   # the case sample last: its buckets and its list are the stream's state
+        dev[n].consume_batch(batches[n])
+        bases, offs = ok.concat_reads(reads[n])
+        ok.consume_reads(ref[n], bases, offs, len(reads[n]))
+    assert launches('k_skm_emit') == 3
+    plan = hk.mex_plan(hk.Counttable, k, 1000, 100, 2)          # a shard nobody cut: every exchange segment empty
+    seg = torch.zeros(int(plan.seg_words), dtype=torch.int64, device='cuda')
+    cnt = torch.zeros(int(plan.cnt_entries), dtype=torch.int32, device='cuda')
+    out = torch.zeros(64, dtype=torch.int64, device='cuda')
+    assert hk.mex_pack(plan, seg.data_ptr(), cnt.data_ptr(), out.data_ptr()) == [0, 0]
+    r, o, a, _ = hk.novel_scan([dev['proband']], [dev['mother'], dev['father']], batches['proband'], 6, 1)
+    assert launches('k_skm_emit') == 4 and launches('k_skm_novel') == 1 and launches('k_skm_novel_list') == 0
+    bases, offs = ok.concat_reads(reads['proband'])
+    hits, _ = ok.novel_scan([ref['proband']], [ref['mother'], ref['father']], bases, offs, len(reads['proband']), k, 6, 1, 0, 0, 0, 0)
+    assert len(hits) > 50
+    assert [(int(r[i]), int(o[i]), tuple(int(x) for x in a[i])) for i in range(len(r))] == hits
+
+
 @pytest.mark.parametrize('kind,case_min,ctrl_max', [('SmallCounttable', 6, 1), ('Nodetable', 1, 0)])
 def test_skm_scan_from_the_distinct_list_nibble_and_bit_counters(hk, ok, skm, kind, case_min, ctrl_max):
     """four-bit counters saturate at 15, one-bit ones at 1: the controls' abundance lists reject by min(count, what a counter holds)"""

@@ -894,6 +894,599 @@ def test_exchange_plans_are_host_arithmetic_every_rank_repeats():
     assert lib.kv_mex_plan_make(0, 12, 1000, 100, 8, ctypes.byref(p)) != 0          # k below the super-k-mer front end's range
 
 
+# kv_mex_plan_make over k x reads x read length x destinations, as the library answered before its bucket planner was written once:
+# ((k, reads, read length, ndest), (C1, F2, fbits, nwg1, cap1, recw, m, seg_words, cnt_entries, c_lo[0..ndest], flags),
+#  what kv_mex_plan_short returns for it, (recw, seg_words, flags) after that call)
+_MEX_PLANS = (
+    ((16,1,16,1),(1,1,0,1,2384,3,8,7152,1,(0,1),0),-5,(3,7152,0)),
+    ((16,1,16,2),(2,1,0,1,1280,3,8,7680,2,(0,1,2),0),-5,(3,7680,0)),
+    ((16,1,16,3),(3,1,0,1,896,3,8,8064,3,(0,1,2,3),0),-5,(3,8064,0)),
+    ((16,1,16,8),(8,1,0,1,416,3,8,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((16,1,100,1),(1,1,0,1,2416,3,8,7248,1,(0,1),0),-5,(3,7248,0)),
+    ((16,1,100,2),(2,1,0,1,1296,3,8,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((16,1,100,3),(3,1,0,1,912,3,8,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((16,1,100,8),(8,1,0,1,416,3,8,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((16,1,150,1),(1,1,0,1,2448,3,8,7344,1,(0,1),0),-5,(3,7344,0)),
+    ((16,1,150,2),(2,1,0,1,1312,3,8,7872,2,(0,1,2),0),-5,(3,7872,0)),
+    ((16,1,150,3),(3,1,0,1,928,3,8,8352,3,(0,1,2,3),0),-5,(3,8352,0)),
+    ((16,1,150,8),(8,1,0,1,432,3,8,10368,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,10368,0)),
+    ((16,1,251,1),(1,1,0,1,2480,3,8,7440,1,(0,1),0),-5,(3,7440,0)),
+    ((16,1,251,2),(2,1,0,1,1328,3,8,7968,2,(0,1,2),0),-5,(3,7968,0)),
+    ((16,1,251,3),(3,1,0,1,944,3,8,8496,3,(0,1,2,3),0),-5,(3,8496,0)),
+    ((16,1,251,8),(8,1,0,1,432,3,8,10368,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,10368,0)),
+    ((16,1000,16,1),(1,1,0,2,2576,3,8,15456,2,(0,1),0),-5,(3,15456,0)),
+    ((16,1000,16,2),(2,1,0,1,1936,3,8,11616,2,(0,1,2),0),-5,(3,11616,0)),
+    ((16,1000,16,3),(3,1,0,1,1200,3,8,10800,3,(0,1,2,3),0),-5,(3,10800,0)),
+    ((16,1000,16,8),(8,1,0,1,464,3,8,11136,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,11136,0)),
+    ((16,1000,100,1),(3,4,2,2,7456,3,8,134208,6,(0,3),0),-5,(3,134208,0)),
+    ((16,1000,100,2),(4,4,2,1,5920,3,8,71040,4,(0,2,4),0),-5,(3,71040,0)),
+    ((16,1000,100,3),(3,4,2,1,5536,3,8,49824,3,(0,1,2,3),0),-5,(3,49824,0)),
+    ((16,1000,100,8),(8,4,2,1,1104,3,8,26496,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,26496,0)),
+    ((16,1000,150,1),(3,8,3,2,11232,3,8,202176,6,(0,3),0),-5,(3,202176,0)),
+    ((16,1000,150,2),(4,8,3,1,8768,3,8,105216,4,(0,2,4),0),-5,(3,105216,0)),
+    ((16,1000,150,3),(3,8,3,1,8080,3,8,72720,3,(0,1,2,3),0),-5,(3,72720,0)),
+    ((16,1000,150,8),(8,8,3,1,1488,3,8,35712,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,35712,0)),
+    ((16,1000,251,1),(4,8,3,2,14208,3,8,340992,8,(0,4),0),-5,(3,340992,0)),
+    ((16,1000,251,2),(4,8,3,1,14480,3,8,173760,4,(0,2,4),0),-5,(3,173760,0)),
+    ((16,1000,251,3),(6,8,3,1,6752,3,8,121536,6,(0,2,4,6),0),-5,(3,121536,0)),
+    ((16,1000,251,8),(8,8,3,1,2224,3,8,53376,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,53376,0)),
+    ((16,2000000,16,1),(16,16,4,256,1456,3,8,17891328,4096,(0,16),0),-5,(3,17891328,0)),
+    ((16,2000000,16,2),(16,16,4,256,800,3,8,9830400,4096,(0,8,16),0),-5,(3,9830400,0)),
+    ((16,2000000,16,3),(18,16,4,256,528,3,8,7299072,4608,(0,6,12,18),0),-5,(3,7299072,0)),
+    ((16,2000000,16,8),(16,16,4,256,288,3,8,3538944,4096,(0,2,4,6,8,10,12,14,16),0),-5,(3,3538944,0)),
+    ((16,2000000,100,1),(82,256,8,256,4176,3,8,262987776,20992,(0,82),0),-5,(3,262987776,0)),
+    ((16,2000000,100,2),(82,256,8,256,2192,3,8,138043392,20992,(0,41,82),0),-5,(3,138043392,0)),
+    ((16,2000000,100,3),(84,256,8,256,1488,3,8,95993856,21504,(0,28,56,84),0),-5,(3,95993856,0)),
+    ((16,2000000,100,8),(88,256,8,256,624,3,8,42172416,22528,(0,11,22,33,44,55,66,77,88),0),-5,(3,42172416,0)),
+    ((16,2000000,150,1),(129,256,8,256,4128,3,8,408969216,33024,(0,129),0),-5,(3,408969216,0)),
+    ((16,2000000,150,2),(130,256,8,256,2160,3,8,215654400,33280,(0,65,130),0),-5,(3,215654400,0)),
+    ((16,2000000,150,3),(129,256,8,256,1504,3,8,149004288,33024,(0,43,86,129),0),-5,(3,149004288,0)),
+    ((16,2000000,150,8),(136,256,8,256,624,3,8,65175552,34816,(0,17,34,51,68,85,102,119,136),0),-5,(3,65175552,0)),
+    ((16,2000000,251,1),(226,256,8,256,4064,3,8,705380352,57856,(0,226),0),-5,(3,705380352,0)),
+    ((16,2000000,251,2),(226,256,8,256,2144,3,8,372129792,57856,(0,113,226),0),-5,(3,372129792,0)),
+    ((16,2000000,251,3),(228,256,8,256,1472,3,8,257753088,58368,(0,76,152,228),0),-5,(3,257753088,0)),
+    ((16,2000000,251,8),(232,256,8,256,640,3,8,114032640,59392,(0,29,58,87,116,145,174,203,232),0),-5,(3,114032640,0)),
+    ((16,7500000,16,1),(29,32,5,256,2816,3,8,62717952,7424,(0,29),0),-5,(3,62717952,0)),
+    ((16,7500000,16,2),(30,32,5,256,1456,3,8,33546240,7680,(0,15,30),0),-5,(3,33546240,0)),
+    ((16,7500000,16,3),(30,32,5,256,1024,3,8,23592960,7680,(0,10,20,30),0),-5,(3,23592960,0)),
+    ((16,7500000,16,8),(32,32,5,256,448,3,8,11010048,8192,(0,4,8,12,16,20,24,28,32),0),-5,(3,11010048,0)),
+    ((16,7500000,100,1),(152,512,9,256,8160,3,8,952565760,38912,(0,152),0),-5,(3,952565760,0)),
+    ((16,7500000,100,2),(152,512,9,256,4224,3,8,493092864,38912,(0,76,152),0),-5,(3,493092864,0)),
+    ((16,7500000,100,3),(153,512,9,256,2864,3,8,336531456,39168,(0,51,102,153),0),-5,(3,336531456,0)),
+    ((16,7500000,100,8),(152,512,9,256,1200,3,8,140083200,38912,(0,19,38,57,76,95,114,133,152),0),-5,(3,140083200,0)),
+    ((16,7500000,150,1),(242,512,9,256,7984,3,8,1483874304,61952,(0,242),0),-5,(3,1483874304,0)),
+    ((16,7500000,150,2),(242,512,9,256,4128,3,8,767213568,61952,(0,121,242),0),-5,(3,767213568,0)),
+    ((16,7500000,150,3),(243,512,9,256,2816,3,8,525533184,62208,(0,81,162,243),0),-5,(3,525533184,0)),
+    ((16,7500000,150,8),(248,512,9,256,1152,3,8,219414528,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,219414528,0)),
+    ((16,7500000,251,1),(212,1024,10,256,15376,3,8,2503458816,54272,(0,212),0),-5,(3,2503458816,0)),
+    ((16,7500000,251,2),(212,1024,10,256,7872,3,8,1281687552,54272,(0,106,212),0),-5,(3,1281687552,0)),
+    ((16,7500000,251,3),(213,1024,10,256,5312,3,8,868958208,54528,(0,71,142,213),0),-5,(3,868958208,0)),
+    ((16,7500000,251,8),(216,1024,10,256,2112,3,8,350355456,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,350355456,0)),
+    ((16,900000000,16,1),(215,512,9,256,41104,3,8,6787092480,55040,(0,215),0),-5,(3,6787092480,0)),
+    ((16,900000000,16,2),(216,512,9,256,20720,3,8,3437199360,55296,(0,108,216),0),-5,(3,3437199360,0)),
+    ((16,900000000,16,3),(216,512,9,256,13952,3,8,2314469376,55296,(0,72,144,216),0),-5,(3,2314469376,0)),
+    ((16,900000000,16,8),(216,512,9,256,5440,3,8,902430720,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,902430720,0)),
+    ((16,900000000,100,1),(255,4096,12,256,547440,3,8,107210649600,65280,(0,255),0),-5,(3,107210649600,0)),
+    ((16,900000000,100,2),(254,4096,12,256,275696,3,8,53780570112,65024,(0,127,254),0),-5,(3,53780570112,0)),
+    ((16,900000000,100,3),(255,4096,12,256,183552,3,8,35946823680,65280,(0,85,170,255),0),-5,(3,35946823680,0)),
+    ((16,900000000,100,8),(248,4096,12,256,71376,3,8,13594558464,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,13594558464,0)),
+    ((16,900000000,150,1),(255,4096,12,256,851776,3,8,166811811840,65280,(0,255),0),-5,(3,166811811840,0)),
+    ((16,900000000,150,2),(254,4096,12,256,428672,3,8,83621904384,65024,(0,127,254),0),-5,(3,83621904384,0)),
+    ((16,900000000,150,3),(255,4096,12,256,285248,3,8,55862968320,65280,(0,85,170,255),0),-5,(3,55862968320,0)),
+    ((16,900000000,150,8),(248,4096,12,256,110736,3,8,21091221504,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,21091221504,0)),
+    ((16,900000000,251,1),(255,4096,12,256,1466096,3,8,287120240640,65280,(0,255),0),-5,(3,287120240640,0)),
+    ((16,900000000,251,2),(254,4096,12,256,737376,3,8,143841411072,65024,(0,127,254),0),-5,(3,143841411072,0)),
+    ((16,900000000,251,3),(255,4096,12,256,490416,3,8,96043069440,65280,(0,85,170,255),0),-5,(3,96043069440,0)),
+    ((16,900000000,251,8),(248,4096,12,256,190064,3,8,36200349696,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,36200349696,0)),
+    ((25,1,25,1),(1,1,0,1,2384,3,12,7152,1,(0,1),0),-5,(3,7152,0)),
+    ((25,1,25,2),(2,1,0,1,1280,3,12,7680,2,(0,1,2),0),-5,(3,7680,0)),
+    ((25,1,25,3),(3,1,0,1,896,3,12,8064,3,(0,1,2,3),0),-5,(3,8064,0)),
+    ((25,1,25,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((25,1,100,1),(1,1,0,1,2400,3,12,7200,1,(0,1),0),-5,(3,7200,0)),
+    ((25,1,100,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((25,1,100,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((25,1,100,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((25,1,150,1),(1,1,0,1,2416,3,12,7248,1,(0,1),0),-5,(3,7248,0)),
+    ((25,1,150,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((25,1,150,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((25,1,150,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((25,1,251,1),(1,1,0,1,2448,3,12,7344,1,(0,1),0),-5,(3,7344,0)),
+    ((25,1,251,2),(2,1,0,1,1312,3,12,7872,2,(0,1,2),0),-5,(3,7872,0)),
+    ((25,1,251,3),(3,1,0,1,928,3,12,8352,3,(0,1,2,3),0),-5,(3,8352,0)),
+    ((25,1,251,8),(8,1,0,1,432,3,12,10368,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,10368,0)),
+    ((25,1000,25,1),(1,1,0,2,2512,3,12,15072,2,(0,1),0),-5,(3,15072,0)),
+    ((25,1000,25,2),(2,1,0,1,1888,3,12,11328,2,(0,1,2),0),-5,(3,11328,0)),
+    ((25,1000,25,3),(3,1,0,1,1184,3,12,10656,3,(0,1,2,3),0),-5,(3,10656,0)),
+    ((25,1000,25,8),(8,1,0,1,464,3,12,11136,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,11136,0)),
+    ((25,1000,100,1),(3,4,2,2,4832,3,12,86976,6,(0,3),0),-5,(3,86976,0)),
+    ((25,1000,100,2),(4,4,2,1,3952,3,12,47424,4,(0,2,4),0),-5,(3,47424,0)),
+    ((25,1000,100,3),(3,4,2,1,3792,3,12,34128,3,(0,1,2,3),0),-5,(3,34128,0)),
+    ((25,1000,100,8),(8,4,2,1,848,3,12,20352,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,20352,0)),
+    ((25,1000,150,1),(4,4,2,2,5600,3,12,134400,8,(0,4),0),-5,(3,134400,0)),
+    ((25,1000,150,2),(4,4,2,1,5872,3,12,70464,4,(0,2,4),0),-5,(3,70464,0)),
+    ((25,1000,150,3),(6,4,2,1,2864,3,12,51552,6,(0,2,4,6),0),-5,(3,51552,0)),
+    ((25,1000,150,8),(8,4,2,1,1104,3,12,26496,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,26496,0)),
+    ((25,1000,251,1),(4,8,3,2,9424,3,12,226176,8,(0,4),0),-5,(3,226176,0)),
+    ((25,1000,251,2),(4,8,3,1,9696,3,12,116352,4,(0,2,4),0),-5,(3,116352,0)),
+    ((25,1000,251,3),(6,8,3,1,4592,3,12,82656,6,(0,2,4,6),0),-5,(3,82656,0)),
+    ((25,1000,251,8),(8,8,3,1,1600,3,12,38400,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,38400,0)),
+    ((25,2000000,25,1),(16,16,4,256,1376,3,12,16908288,4096,(0,16),0),-5,(3,16908288,0)),
+    ((25,2000000,25,2),(16,16,4,256,768,3,12,9437184,4096,(0,8,16),0),-5,(3,9437184,0)),
+    ((25,2000000,25,3),(18,16,4,256,512,3,12,7077888,4608,(0,6,12,18),0),-5,(3,7077888,0)),
+    ((25,2000000,25,8),(16,16,4,256,272,3,12,3342336,4096,(0,2,4,6,8,10,12,14,16),0),-5,(3,3342336,0)),
+    ((25,2000000,100,1),(73,256,8,256,2960,3,12,165949440,18688,(0,73),0),-5,(3,165949440,0)),
+    ((25,2000000,100,2),(74,256,8,256,1552,3,12,88203264,18944,(0,37,74),0),-5,(3,88203264,0)),
+    ((25,2000000,100,3),(75,256,8,256,1072,3,12,61747200,19200,(0,25,50,75),0),-5,(3,61747200,0)),
+    ((25,2000000,100,8),(80,256,8,256,464,3,12,28508160,20480,(0,10,20,30,40,50,60,70,80),0),-5,(3,28508160,0)),
+    ((25,2000000,150,1),(121,256,8,256,2864,3,12,266145792,30976,(0,121),0),-5,(3,266145792,0)),
+    ((25,2000000,150,2),(122,256,8,256,1520,3,12,142417920,31232,(0,61,122),0),-5,(3,142417920,0)),
+    ((25,2000000,150,3),(123,256,8,256,1056,3,12,99753984,31488,(0,41,82,123),0),-5,(3,99753984,0)),
+    ((25,2000000,150,8),(128,256,8,256,464,3,12,45613056,32768,(0,16,32,48,64,80,96,112,128),0),-5,(3,45613056,0)),
+    ((25,2000000,251,1),(217,256,8,256,2816,3,12,469303296,55552,(0,217),0),-5,(3,469303296,0)),
+    ((25,2000000,251,2),(218,256,8,256,1504,3,12,251805696,55808,(0,109,218),0),-5,(3,251805696,0)),
+    ((25,2000000,251,3),(219,256,8,256,1056,3,12,177610752,56064,(0,73,146,219),0),-5,(3,177610752,0)),
+    ((25,2000000,251,8),(224,256,8,256,464,3,12,79822848,57344,(0,28,56,84,112,140,168,196,224),0),-5,(3,79822848,0)),
+    ((25,7500000,25,1),(29,32,5,256,2656,3,12,59154432,7424,(0,29),0),-5,(3,59154432,0)),
+    ((25,7500000,25,2),(30,32,5,256,1376,3,12,31703040,7680,(0,15,30),0),-5,(3,31703040,0)),
+    ((25,7500000,25,3),(30,32,5,256,976,3,12,22487040,7680,(0,10,20,30),0),-5,(3,22487040,0)),
+    ((25,7500000,25,8),(32,32,5,256,432,3,12,10616832,8192,(0,4,8,12,16,20,24,28,32),0),-5,(3,10616832,0)),
+    ((25,7500000,100,1),(136,512,9,256,5712,3,12,596606976,34816,(0,136),0),-5,(3,596606976,0)),
+    ((25,7500000,100,2),(136,512,9,256,2976,3,12,310837248,34816,(0,68,136),0),-5,(3,310837248,0)),
+    ((25,7500000,100,3),(138,512,9,256,2032,3,12,215359488,35328,(0,46,92,138),0),-5,(3,215359488,0)),
+    ((25,7500000,100,8),(136,512,9,256,864,3,12,90243072,34816,(0,17,34,51,68,85,102,119,136),0),-5,(3,90243072,0)),
+    ((25,7500000,150,1),(226,512,9,256,5520,3,12,958095360,57856,(0,226),0),-5,(3,958095360,0)),
+    ((25,7500000,150,2),(226,512,9,256,2880,3,12,499875840,57856,(0,113,226),0),-5,(3,499875840,0)),
+    ((25,7500000,150,3),(228,512,9,256,1968,3,12,344604672,58368,(0,76,152,228),0),-5,(3,344604672,0)),
+    ((25,7500000,150,8),(232,512,9,256,832,3,12,148242432,59392,(0,29,58,87,116,145,174,203,232),0),-5,(3,148242432,0)),
+    ((25,7500000,251,1),(203,1024,10,256,10528,3,12,1641357312,51968,(0,203),0),-5,(3,1641357312,0)),
+    ((25,7500000,251,2),(204,1024,10,256,5392,3,12,844775424,52224,(0,102,204),0),-5,(3,844775424,0)),
+    ((25,7500000,251,3),(204,1024,10,256,3680,3,12,576552960,52224,(0,68,136,204),0),-5,(3,576552960,0)),
+    ((25,7500000,251,8),(208,1024,10,256,1472,3,12,235143168,53248,(0,26,52,78,104,130,156,182,208),0),-5,(3,235143168,0)),
+    ((25,900000000,25,1),(215,512,9,256,38672,3,12,6385520640,55040,(0,215),0),-5,(3,6385520640,0)),
+    ((25,900000000,25,2),(216,512,9,256,19504,3,12,3235479552,55296,(0,108,216),0),-5,(3,3235479552,0)),
+    ((25,900000000,25,3),(216,512,9,256,13152,3,12,2181758976,55296,(0,72,144,216),0),-5,(3,2181758976,0)),
+    ((25,900000000,25,8),(216,512,9,256,5120,3,12,849346560,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,849346560,0)),
+    ((25,900000000,100,1),(255,4096,12,256,338272,3,12,66247188480,65280,(0,255),0),-5,(3,66247188480,0)),
+    ((25,900000000,100,2),(254,4096,12,256,170512,3,12,33262116864,65024,(0,127,254),0),-5,(3,33262116864,0)),
+    ((25,900000000,100,3),(255,4096,12,256,113600,3,12,22247424000,65280,(0,85,170,255),0),-5,(3,22247424000,0)),
+    ((25,900000000,100,8),(248,4096,12,256,44288,3,12,8435269632,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,8435269632,0)),
+    ((25,900000000,150,1),(255,4096,12,256,541344,3,12,106016808960,65280,(0,255),0),-5,(3,106016808960,0)),
+    ((25,900000000,150,2),(254,4096,12,256,272624,3,12,53181308928,65024,(0,127,254),0),-5,(3,53181308928,0)),
+    ((25,900000000,150,3),(255,4096,12,256,181504,3,12,35545743360,65280,(0,85,170,255),0),-5,(3,35545743360,0)),
+    ((25,900000000,150,8),(248,4096,12,256,70592,3,12,13445234688,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,13445234688,0)),
+    ((25,900000000,251,1),(255,4096,12,256,951168,3,12,186276741120,65280,(0,255),0),-5,(3,186276741120,0)),
+    ((25,900000000,251,2),(254,4096,12,256,478624,3,12,93366140928,65024,(0,127,254),0),-5,(3,93366140928,0)),
+    ((25,900000000,251,3),(255,4096,12,256,318448,3,12,62364856320,65280,(0,85,170,255),0),-5,(3,62364856320,0)),
+    ((25,900000000,251,8),(248,4096,12,256,123584,3,12,23538302976,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,23538302976,0)),
+    ((31,1,31,1),(1,1,0,1,2384,3,12,7152,1,(0,1),0),0,(2,4768,1)),
+    ((31,1,31,2),(2,1,0,1,1280,3,12,7680,2,(0,1,2),0),0,(2,5120,1)),
+    ((31,1,31,3),(3,1,0,1,896,3,12,8064,3,(0,1,2,3),0),0,(2,5376,1)),
+    ((31,1,31,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),0,(2,6656,1)),
+    ((31,1,100,1),(1,1,0,1,2400,3,12,7200,1,(0,1),0),0,(2,4800,1)),
+    ((31,1,100,2),(2,1,0,1,1280,3,12,7680,2,(0,1,2),0),0,(2,5120,1)),
+    ((31,1,100,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),0,(2,5472,1)),
+    ((31,1,100,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),0,(2,6656,1)),
+    ((31,1,150,1),(1,1,0,1,2400,3,12,7200,1,(0,1),0),0,(2,4800,1)),
+    ((31,1,150,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),0,(2,5184,1)),
+    ((31,1,150,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),0,(2,5472,1)),
+    ((31,1,150,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),0,(2,6656,1)),
+    ((31,1,251,1),(1,1,0,1,2432,3,12,7296,1,(0,1),0),-5,(3,7296,0)),
+    ((31,1,251,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((31,1,251,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((31,1,251,8),(8,1,0,1,432,3,12,10368,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,10368,0)),
+    ((31,1000,31,1),(1,1,0,2,2464,3,12,14784,2,(0,1),0),0,(2,9856,1)),
+    ((31,1000,31,2),(2,1,0,1,1872,3,12,11232,2,(0,1,2),0),0,(2,7488,1)),
+    ((31,1000,31,3),(3,1,0,1,1168,3,12,10512,3,(0,1,2,3),0),0,(2,7008,1)),
+    ((31,1000,31,8),(8,1,0,1,464,3,12,11136,8,(0,1,2,3,4,5,6,7,8),0),0,(2,7424,1)),
+    ((31,1000,100,1),(3,4,2,2,3504,3,12,63072,6,(0,3),0),0,(2,42048,1)),
+    ((31,1000,100,2),(4,4,2,1,2960,3,12,35520,4,(0,2,4),0),0,(2,23680,1)),
+    ((31,1000,100,3),(3,4,2,1,2896,3,12,26064,3,(0,1,2,3),0),0,(2,17376,1)),
+    ((31,1000,100,8),(8,4,2,1,720,3,12,17280,8,(0,1,2,3,4,5,6,7,8),0),0,(2,11520,1)),
+    ((31,1000,150,1),(4,4,2,2,4064,3,12,97536,8,(0,4),0),0,(2,65024,1)),
+    ((31,1000,150,2),(4,4,2,1,4336,3,12,52032,4,(0,2,4),0),0,(2,34688,1)),
+    ((31,1000,150,3),(6,4,2,1,2160,3,12,38880,6,(0,2,4,6),0),0,(2,25920,1)),
+    ((31,1000,150,8),(8,4,2,1,896,3,12,21504,8,(0,1,2,3,4,5,6,7,8),0),0,(2,14336,1)),
+    ((31,1000,251,1),(4,8,3,2,6816,3,12,163584,8,(0,4),0),-5,(3,163584,0)),
+    ((31,1000,251,2),(4,8,3,1,7072,3,12,84864,4,(0,2,4),0),-5,(3,84864,0)),
+    ((31,1000,251,3),(6,8,3,1,3408,3,12,61344,6,(0,2,4,6),0),-5,(3,61344,0)),
+    ((31,1000,251,8),(8,8,3,1,1264,3,12,30336,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,30336,0)),
+    ((31,2000000,31,1),(16,16,4,256,1344,3,12,16515072,4096,(0,16),0),0,(2,11010048,1)),
+    ((31,2000000,31,2),(16,16,4,256,736,3,12,9043968,4096,(0,8,16),0),0,(2,6029312,1)),
+    ((31,2000000,31,3),(18,16,4,256,496,3,12,6856704,4608,(0,6,12,18),0),0,(2,4571136,1)),
+    ((31,2000000,31,8),(16,16,4,256,272,3,12,3342336,4096,(0,2,4,6,8,10,12,14,16),0),0,(2,2228224,1)),
+    ((31,2000000,100,1),(67,256,8,256,2256,3,12,116084736,17152,(0,67),0),0,(2,77389824,1)),
+    ((31,2000000,100,2),(68,256,8,256,1200,3,12,62668800,17408,(0,34,68),0),0,(2,41779200,1)),
+    ((31,2000000,100,3),(69,256,8,256,848,3,12,44937216,17664,(0,23,46,69),0),0,(2,29958144,1)),
+    ((31,2000000,100,8),(72,256,8,256,384,3,12,21233664,18432,(0,9,18,27,36,45,54,63,72),0),0,(2,14155776,1)),
+    ((31,2000000,150,1),(115,256,8,256,2160,3,12,190771200,29440,(0,115),0),0,(2,127180800,1)),
+    ((31,2000000,150,2),(116,256,8,256,1152,3,12,102629376,29696,(0,58,116),0),0,(2,68419584,1)),
+    ((31,2000000,150,3),(117,256,8,256,816,3,12,73322496,29952,(0,39,78,117),0),0,(2,48881664,1)),
+    ((31,2000000,150,8),(120,256,8,256,384,3,12,35389440,30720,(0,15,30,45,60,75,90,105,120),0),0,(2,23592960,1)),
+    ((31,2000000,251,1),(211,256,8,256,2096,3,12,339652608,54016,(0,211),0),-5,(3,339652608,0)),
+    ((31,2000000,251,2),(212,256,8,256,1136,3,12,184958976,54272,(0,106,212),0),-5,(3,184958976,0)),
+    ((31,2000000,251,3),(213,256,8,256,800,3,12,130867200,54528,(0,71,142,213),0),-5,(3,130867200,0)),
+    ((31,2000000,251,8),(216,256,8,256,368,3,12,61046784,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,61046784,0)),
+    ((31,7500000,31,1),(29,32,5,256,2576,3,12,57372672,7424,(0,29),0),0,(2,38248448,1)),
+    ((31,7500000,31,2),(30,32,5,256,1328,3,12,30597120,7680,(0,15,30),0),0,(2,20398080,1)),
+    ((31,7500000,31,3),(30,32,5,256,944,3,12,21749760,7680,(0,10,20,30),0),0,(2,14499840,1)),
+    ((31,7500000,31,8),(32,32,5,256,416,3,12,10223616,8192,(0,4,8,12,16,20,24,28,32),0),0,(2,6815744,1)),
+    ((31,7500000,100,1),(251,256,8,256,2272,3,12,437968896,64256,(0,251),0),0,(2,291979264,1)),
+    ((31,7500000,100,2),(252,256,8,256,1216,3,12,235339776,64512,(0,126,252),0),0,(2,156893184,1)),
+    ((31,7500000,100,3),(252,256,8,256,864,3,12,167215104,64512,(0,84,168,252),0),0,(2,111476736,1)),
+    ((31,7500000,100,8),(248,256,8,256,400,3,12,76185600,63488,(0,31,62,93,124,155,186,217,248),0),0,(2,50790400,1)),
+    ((31,7500000,150,1),(215,512,9,256,4112,3,12,678973440,55040,(0,215),0),0,(2,452648960,1)),
+    ((31,7500000,150,2),(216,512,9,256,2160,3,12,358318080,55296,(0,108,216),0),0,(2,238878720,1)),
+    ((31,7500000,150,3),(216,512,9,256,1504,3,12,249495552,55296,(0,72,144,216),0),0,(2,166330368,1)),
+    ((31,7500000,150,8),(216,512,9,256,656,3,12,108822528,55296,(0,27,54,81,108,135,162,189,216),0),0,(2,72548352,1)),
+    ((31,7500000,251,1),(198,1024,10,256,7696,3,12,1170284544,50688,(0,198),0),-5,(3,1170284544,0)),
+    ((31,7500000,251,2),(198,1024,10,256,3984,3,12,605822976,50688,(0,99,198),0),-5,(3,605822976,0)),
+    ((31,7500000,251,3),(198,1024,10,256,2736,3,12,416047104,50688,(0,66,132,198),0),-5,(3,416047104,0)),
+    ((31,7500000,251,8),(200,1024,10,256,1120,3,12,172032000,51200,(0,25,50,75,100,125,150,175,200),0),-5,(3,172032000,0)),
+    ((31,900000000,31,1),(215,512,9,256,37280,3,12,6155673600,55040,(0,215),0),0,(2,4103782400,1)),
+    ((31,900000000,31,2),(216,512,9,256,18816,3,12,3121348608,55296,(0,108,216),0),0,(2,2080899072,1)),
+    ((31,900000000,31,3),(216,512,9,256,12672,3,12,2102132736,55296,(0,72,144,216),0),0,(2,1401421824,1)),
+    ((31,900000000,31,8),(216,512,9,256,4944,3,12,820150272,55296,(0,27,54,81,108,135,162,189,216),0),0,(2,546766848,1)),
+    ((31,900000000,100,1),(255,4096,12,256,232560,3,12,45544550400,65280,(0,255),0),0,(2,30363033600,1)),
+    ((31,900000000,100,2),(254,4096,12,256,117328,3,12,22887407616,65024,(0,127,254),0),0,(2,15258271744,1)),
+    ((31,900000000,100,3),(255,4096,12,256,78224,3,12,15319388160,65280,(0,85,170,255),0),0,(2,10212925440,1)),
+    ((31,900000000,100,8),(248,4096,12,256,30576,3,12,5823627264,63488,(0,31,62,93,124,155,186,217,248),0),0,(2,3882418176,1)),
+    ((31,900000000,150,1),(255,4096,12,256,377744,3,12,73977384960,65280,(0,255),0),0,(2,49318256640,1)),
+    ((31,900000000,150,2),(254,4096,12,256,190368,3,12,37135466496,65024,(0,127,254),0),0,(2,24756977664,1)),
+    ((31,900000000,150,3),(255,4096,12,256,126800,3,12,24832512000,65280,(0,85,170,255),0),0,(2,16555008000,1)),
+    ((31,900000000,150,8),(248,4096,12,256,49408,3,12,9410445312,63488,(0,31,62,93,124,155,186,217,248),0),0,(2,6273630208,1)),
+    ((31,900000000,251,1),(255,4096,12,256,670656,3,12,131341271040,65280,(0,255),0),-5,(3,131341271040,0)),
+    ((31,900000000,251,2),(254,4096,12,256,337632,3,12,65862549504,65024,(0,127,254),0),-5,(3,65862549504,0)),
+    ((31,900000000,251,3),(255,4096,12,256,224720,3,12,44009164800,65280,(0,85,170,255),0),-5,(3,44009164800,0)),
+    ((31,900000000,251,8),(248,4096,12,256,87328,3,12,16632840192,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,16632840192,0)),
+    ((32,1,32,1),(1,1,0,1,2384,3,12,7152,1,(0,1),0),-5,(3,7152,0)),
+    ((32,1,32,2),(2,1,0,1,1280,3,12,7680,2,(0,1,2),0),-5,(3,7680,0)),
+    ((32,1,32,3),(3,1,0,1,896,3,12,8064,3,(0,1,2,3),0),-5,(3,8064,0)),
+    ((32,1,32,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((32,1,100,1),(1,1,0,1,2384,3,12,7152,1,(0,1),0),-5,(3,7152,0)),
+    ((32,1,100,2),(2,1,0,1,1280,3,12,7680,2,(0,1,2),0),-5,(3,7680,0)),
+    ((32,1,100,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((32,1,100,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((32,1,150,1),(1,1,0,1,2400,3,12,7200,1,(0,1),0),-5,(3,7200,0)),
+    ((32,1,150,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((32,1,150,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((32,1,150,8),(8,1,0,1,416,3,12,9984,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,9984,0)),
+    ((32,1,251,1),(1,1,0,1,2416,3,12,7248,1,(0,1),0),-5,(3,7248,0)),
+    ((32,1,251,2),(2,1,0,1,1296,3,12,7776,2,(0,1,2),0),-5,(3,7776,0)),
+    ((32,1,251,3),(3,1,0,1,912,3,12,8208,3,(0,1,2,3),0),-5,(3,8208,0)),
+    ((32,1,251,8),(8,1,0,1,432,3,12,10368,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,10368,0)),
+    ((32,1000,32,1),(1,1,0,2,2448,3,12,14688,2,(0,1),0),-5,(3,14688,0)),
+    ((32,1000,32,2),(2,1,0,1,1872,3,12,11232,2,(0,1,2),0),-5,(3,11232,0)),
+    ((32,1000,32,3),(3,1,0,1,1168,3,12,10512,3,(0,1,2,3),0),-5,(3,10512,0)),
+    ((32,1000,32,8),(8,1,0,1,464,3,12,11136,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,11136,0)),
+    ((32,1000,100,1),(3,4,2,2,3360,3,12,60480,6,(0,3),0),-5,(3,60480,0)),
+    ((32,1000,100,2),(4,4,2,1,2848,3,12,34176,4,(0,2,4),0),-5,(3,34176,0)),
+    ((32,1000,100,3),(3,4,2,1,2800,3,12,25200,3,(0,1,2,3),0),-5,(3,25200,0)),
+    ((32,1000,100,8),(8,4,2,1,704,3,12,16896,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,16896,0)),
+    ((32,1000,150,1),(4,4,2,2,3888,3,12,93312,8,(0,4),0),-5,(3,93312,0)),
+    ((32,1000,150,2),(4,4,2,1,4160,3,12,49920,4,(0,2,4),0),-5,(3,49920,0)),
+    ((32,1000,150,3),(6,4,2,1,2080,3,12,37440,6,(0,2,4,6),0),-5,(3,37440,0)),
+    ((32,1000,150,8),(8,4,2,1,880,3,12,21120,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,21120,0)),
+    ((32,1000,251,1),(4,8,3,2,6512,3,12,156288,8,(0,4),0),-5,(3,156288,0)),
+    ((32,1000,251,2),(4,8,3,1,6784,3,12,81408,4,(0,2,4),0),-5,(3,81408,0)),
+    ((32,1000,251,3),(6,8,3,1,3280,3,12,59040,6,(0,2,4,6),0),-5,(3,59040,0)),
+    ((32,1000,251,8),(8,8,3,1,1216,3,12,29184,8,(0,1,2,3,4,5,6,7,8),0),-5,(3,29184,0)),
+    ((32,2000000,32,1),(16,16,4,256,1328,3,12,16318464,4096,(0,16),0),-5,(3,16318464,0)),
+    ((32,2000000,32,2),(16,16,4,256,736,3,12,9043968,4096,(0,8,16),0),-5,(3,9043968,0)),
+    ((32,2000000,32,3),(18,16,4,256,496,3,12,6856704,4608,(0,6,12,18),0),-5,(3,6856704,0)),
+    ((32,2000000,32,8),(16,16,4,256,272,3,12,3342336,4096,(0,2,4,6,8,10,12,14,16),0),-5,(3,3342336,0)),
+    ((32,2000000,100,1),(66,256,8,256,2192,3,12,111108096,16896,(0,66),0),-5,(3,111108096,0)),
+    ((32,2000000,100,2),(66,256,8,256,1184,3,12,60014592,16896,(0,33,66),0),-5,(3,60014592,0)),
+    ((32,2000000,100,3),(66,256,8,256,832,3,12,42172416,16896,(0,22,44,66),0),-5,(3,42172416,0)),
+    ((32,2000000,100,8),(72,256,8,256,368,3,12,20348928,18432,(0,9,18,27,36,45,54,63,72),0),-5,(3,20348928,0)),
+    ((32,2000000,150,1),(114,256,8,256,2080,3,12,182108160,29184,(0,114),0),-5,(3,182108160,0)),
+    ((32,2000000,150,2),(114,256,8,256,1120,3,12,98058240,29184,(0,57,114),0),-5,(3,98058240,0)),
+    ((32,2000000,150,3),(114,256,8,256,800,3,12,70041600,29184,(0,38,76,114),0),-5,(3,70041600,0)),
+    ((32,2000000,150,8),(120,256,8,256,368,3,12,33914880,30720,(0,15,30,45,60,75,90,105,120),0),-5,(3,33914880,0)),
+    ((32,2000000,251,1),(210,256,8,256,2016,3,12,325140480,53760,(0,210),0),-5,(3,325140480,0)),
+    ((32,2000000,251,2),(210,256,8,256,1088,3,12,175472640,53760,(0,105,210),0),-5,(3,175472640,0)),
+    ((32,2000000,251,3),(210,256,8,256,784,3,12,126443520,53760,(0,70,140,210),0),-5,(3,126443520,0)),
+    ((32,2000000,251,8),(216,256,8,256,368,3,12,61046784,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,61046784,0)),
+    ((32,7500000,32,1),(29,32,5,256,2560,3,12,57016320,7424,(0,29),0),-5,(3,57016320,0)),
+    ((32,7500000,32,2),(30,32,5,256,1328,3,12,30597120,7680,(0,15,30),0),-5,(3,30597120,0)),
+    ((32,7500000,32,3),(30,32,5,256,944,3,12,21749760,7680,(0,10,20,30),0),-5,(3,21749760,0)),
+    ((32,7500000,32,8),(32,32,5,256,416,3,12,10223616,8192,(0,4,8,12,16,20,24,28,32),0),-5,(3,10223616,0)),
+    ((32,7500000,100,1),(247,256,8,256,2192,3,12,415813632,63232,(0,247),0),-5,(3,415813632,0)),
+    ((32,7500000,100,2),(248,256,8,256,1184,3,12,225509376,63488,(0,124,248),0),-5,(3,225509376,0)),
+    ((32,7500000,100,3),(249,256,8,256,832,3,12,159105024,63744,(0,83,166,249),0),-5,(3,159105024,0)),
+    ((32,7500000,100,8),(248,256,8,256,384,3,12,73138176,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,73138176,0)),
+    ((32,7500000,150,1),(213,512,9,256,3952,3,12,646483968,54528,(0,213),0),-5,(3,646483968,0)),
+    ((32,7500000,150,2),(214,512,9,256,2080,3,12,341852160,54784,(0,107,214),0),-5,(3,341852160,0)),
+    ((32,7500000,150,3),(213,512,9,256,1456,3,12,238178304,54528,(0,71,142,213),0),-5,(3,238178304,0)),
+    ((32,7500000,150,8),(216,512,9,256,624,3,12,103514112,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,103514112,0)),
+    ((32,7500000,251,1),(197,1024,10,256,7376,3,12,1115959296,50432,(0,197),0),-5,(3,1115959296,0)),
+    ((32,7500000,251,2),(198,1024,10,256,3808,3,12,579059712,50688,(0,99,198),0),-5,(3,579059712,0)),
+    ((32,7500000,251,3),(198,1024,10,256,2608,3,12,396582912,50688,(0,66,132,198),0),-5,(3,396582912,0)),
+    ((32,7500000,251,8),(200,1024,10,256,1072,3,12,164659200,51200,(0,25,50,75,100,125,150,175,200),0),-5,(3,164659200,0)),
+    ((32,900000000,32,1),(215,512,9,256,37120,3,12,6129254400,55040,(0,215),0),-5,(3,6129254400,0)),
+    ((32,900000000,32,2),(216,512,9,256,18736,3,12,3108077568,55296,(0,108,216),0),-5,(3,3108077568,0)),
+    ((32,900000000,32,3),(216,512,9,256,12624,3,12,2094170112,55296,(0,72,144,216),0),-5,(3,2094170112,0)),
+    ((32,900000000,32,8),(216,512,9,256,4928,3,12,817496064,55296,(0,27,54,81,108,135,162,189,216),0),-5,(3,817496064,0)),
+    ((32,900000000,100,1),(255,4096,12,256,220544,3,12,43191336960,65280,(0,255),0),-5,(3,43191336960,0)),
+    ((32,900000000,100,2),(254,4096,12,256,111280,3,12,21707612160,65024,(0,127,254),0),-5,(3,21707612160,0)),
+    ((32,900000000,100,3),(255,4096,12,256,74208,3,12,14532894720,65280,(0,85,170,255),0),-5,(3,14532894720,0)),
+    ((32,900000000,100,8),(248,4096,12,256,29008,3,12,5524979712,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,5524979712,0)),
+    ((32,900000000,150,1),(255,4096,12,256,359136,3,12,70333194240,65280,(0,255),0),-5,(3,70333194240,0)),
+    ((32,900000000,150,2),(254,4096,12,256,181008,3,12,35309592576,65024,(0,127,254),0),-5,(3,35309592576,0)),
+    ((32,900000000,150,3),(255,4096,12,256,120592,3,12,23616737280,65280,(0,85,170,255),0),-5,(3,23616737280,0)),
+    ((32,900000000,150,8),(248,4096,12,256,46992,3,12,8950284288,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,8950284288,0)),
+    ((32,900000000,251,1),(255,4096,12,256,638768,3,12,125096325120,65280,(0,255),0),-5,(3,125096325120,0)),
+    ((32,900000000,251,2),(254,4096,12,256,321600,3,12,62735155200,65024,(0,127,254),0),-5,(3,62735155200,0)),
+    ((32,900000000,251,3),(255,4096,12,256,214064,3,12,41922293760,65280,(0,85,170,255),0),-5,(3,41922293760,0)),
+    ((32,900000000,251,8),(248,4096,12,256,83200,3,12,15846604800,63488,(0,31,62,93,124,155,186,217,248),0),-5,(3,15846604800,0)),
+    ((33,1,33,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((33,1,33,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((33,1,33,3),(3,1,0,1,896,4,12,10752,3,(0,1,2,3),0),-5,(4,10752,0)),
+    ((33,1,33,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((33,1,100,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((33,1,100,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((33,1,100,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((33,1,100,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((33,1,150,1),(1,1,0,1,2400,4,12,9600,1,(0,1),0),-5,(4,9600,0)),
+    ((33,1,150,2),(2,1,0,1,1296,4,12,10368,2,(0,1,2),0),-5,(4,10368,0)),
+    ((33,1,150,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((33,1,150,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((33,1,251,1),(1,1,0,1,2416,4,12,9664,1,(0,1),0),-5,(4,9664,0)),
+    ((33,1,251,2),(2,1,0,1,1296,4,12,10368,2,(0,1,2),0),-5,(4,10368,0)),
+    ((33,1,251,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((33,1,251,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((33,1000,33,1),(1,1,0,2,2448,4,12,19584,2,(0,1),0),-5,(4,19584,0)),
+    ((33,1000,33,2),(2,1,0,1,1872,4,12,14976,2,(0,1,2),0),-5,(4,14976,0)),
+    ((33,1000,33,3),(3,1,0,1,1168,4,12,14016,3,(0,1,2,3),0),-5,(4,14016,0)),
+    ((33,1000,33,8),(8,1,0,1,464,4,12,14848,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,14848,0)),
+    ((33,1000,100,1),(3,8,3,2,3216,4,12,77184,6,(0,3),0),-5,(4,77184,0)),
+    ((33,1000,100,2),(4,8,3,1,2736,4,12,43776,4,(0,2,4),0),-5,(4,43776,0)),
+    ((33,1000,100,3),(3,8,3,1,2704,4,12,32448,3,(0,1,2,3),0),-5,(4,32448,0)),
+    ((33,1000,100,8),(8,8,3,1,688,4,12,22016,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,22016,0)),
+    ((33,1000,150,1),(5,8,3,2,3024,4,12,120960,10,(0,5),0),-5,(4,120960,0)),
+    ((33,1000,150,2),(6,8,3,1,2736,4,12,65664,6,(0,3,6),0),-5,(4,65664,0)),
+    ((33,1000,150,3),(6,8,3,1,2016,4,12,48384,6,(0,2,4,6),0),-5,(4,48384,0)),
+    ((33,1000,150,8),(8,8,3,1,848,4,12,27136,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,27136,0)),
+    ((33,1000,251,1),(5,16,4,2,5056,4,12,202240,10,(0,5),0),-5,(4,202240,0)),
+    ((33,1000,251,2),(6,16,4,1,4432,4,12,106368,6,(0,3,6),0),-5,(4,106368,0)),
+    ((33,1000,251,3),(6,16,4,1,3152,4,12,75648,6,(0,2,4,6),0),-5,(4,75648,0)),
+    ((33,1000,251,8),(8,16,4,1,1184,4,12,37888,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,37888,0)),
+    ((33,2000000,33,1),(21,32,5,256,1056,4,12,22708224,5376,(0,21),0),-5,(4,22708224,0)),
+    ((33,2000000,33,2),(22,32,5,256,576,4,12,12976128,5632,(0,11,22),0),-5,(4,12976128,0)),
+    ((33,2000000,33,3),(21,32,5,256,432,4,12,9289728,5376,(0,7,14,21),0),-5,(4,9289728,0)),
+    ((33,2000000,33,8),(24,32,5,256,208,4,12,5111808,6144,(0,3,6,9,12,15,18,21,24),0),-5,(4,5111808,0)),
+    ((33,2000000,100,1),(173,256,8,256,896,4,12,158728192,44288,(0,173),0),-5,(4,158728192,0)),
+    ((33,2000000,100,2),(174,256,8,256,512,4,12,91226112,44544,(0,87,174),0),-5,(4,91226112,0)),
+    ((33,2000000,100,3),(174,256,8,256,384,4,12,68419584,44544,(0,58,116,174),0),-5,(4,68419584,0)),
+    ((33,2000000,100,8),(176,256,8,256,208,4,12,37486592,45056,(0,22,44,66,88,110,132,154,176),0),-5,(4,37486592,0)),
+    ((33,2000000,150,1),(151,512,9,256,1552,4,12,239976448,38656,(0,151),0),-5,(4,239976448,0)),
+    ((33,2000000,150,2),(152,512,9,256,848,4,12,131989504,38912,(0,76,152),0),-5,(4,131989504,0)),
+    ((33,2000000,150,3),(153,512,9,256,608,4,12,95256576,39168,(0,51,102,153),0),-5,(4,95256576,0)),
+    ((33,2000000,150,8),(152,512,9,256,304,4,12,47316992,38912,(0,19,38,57,76,95,114,133,152),0),-5,(4,47316992,0)),
+    ((33,2000000,251,1),(140,1024,10,256,2800,4,12,401408000,35840,(0,140),0),-5,(4,401408000,0)),
+    ((33,2000000,251,2),(140,1024,10,256,1488,4,12,213319680,35840,(0,70,140),0),-5,(4,213319680,0)),
+    ((33,2000000,251,3),(141,1024,10,256,1040,4,12,150159360,36096,(0,47,94,141),0),-5,(4,150159360,0)),
+    ((33,2000000,251,8),(144,1024,10,256,464,4,12,68419584,36864,(0,18,36,54,72,90,108,126,144),0),-5,(4,68419584,0)),
+    ((33,7500000,33,1),(39,64,6,256,1952,4,12,77955072,9984,(0,39),0),-5,(4,77955072,0)),
+    ((33,7500000,33,2),(40,64,6,256,1040,4,12,42598400,10240,(0,20,40),0),-5,(4,42598400,0)),
+    ((33,7500000,33,3),(39,64,6,256,752,4,12,30031872,9984,(0,13,26,39),0),-5,(4,30031872,0)),
+    ((33,7500000,33,8),(40,64,6,256,352,4,12,14417920,10240,(0,5,10,15,20,25,30,35,40),0),-5,(4,14417920,0)),
+    ((33,7500000,100,1),(163,1024,10,256,3056,4,12,510083072,41728,(0,163),0),-5,(4,510083072,0)),
+    ((33,7500000,100,2),(164,1024,10,256,1616,4,12,271384576,41984,(0,82,164),0),-5,(4,271384576,0)),
+    ((33,7500000,100,3),(165,1024,10,256,1120,4,12,189235200,42240,(0,55,110,165),0),-5,(4,189235200,0)),
+    ((33,7500000,100,8),(168,1024,10,256,496,4,12,85327872,43008,(0,21,42,63,84,105,126,147,168),0),-5,(4,85327872,0)),
+    ((33,7500000,150,1),(141,2048,11,256,5584,4,12,806240256,36096,(0,141),0),-5,(4,806240256,0)),
+    ((33,7500000,150,2),(142,2048,11,256,2896,4,12,421101568,36352,(0,71,142),0),-5,(4,421101568,0)),
+    ((33,7500000,150,3),(141,2048,11,256,2000,4,12,288768000,36096,(0,47,94,141),0),-5,(4,288768000,0)),
+    ((33,7500000,150,8),(144,2048,11,256,832,4,12,122683392,36864,(0,18,36,54,72,90,108,126,144),0),-5,(4,122683392,0)),
+    ((33,7500000,251,1),(131,4096,12,256,10448,4,12,1401536512,33536,(0,131),0),-5,(4,1401536512,0)),
+    ((33,7500000,251,2),(132,4096,12,256,5344,4,12,722337792,33792,(0,66,132),0),-5,(4,722337792,0)),
+    ((33,7500000,251,3),(132,4096,12,256,3648,4,12,493092864,33792,(0,44,88,132),0),-5,(4,493092864,0)),
+    ((33,7500000,251,8),(136,4096,12,256,1440,4,12,200540160,34816,(0,17,34,51,68,85,102,119,136),0),-5,(4,200540160,0)),
+    ((33,900000000,33,1),(144,2048,11,256,54880,4,12,8092385280,36864,(0,144),0),-5,(4,8092385280,0)),
+    ((33,900000000,33,2),(144,2048,11,256,27744,4,12,4091019264,36864,(0,72,144),0),-5,(4,4091019264,0)),
+    ((33,900000000,33,3),(144,2048,11,256,18656,4,12,2750939136,36864,(0,48,96,144),0),-5,(4,2750939136,0)),
+    ((33,900000000,33,8),(144,2048,11,256,7216,4,12,1064042496,36864,(0,18,36,54,72,90,108,126,144),0),-5,(4,1064042496,0)),
+    ((33,900000000,100,1),(255,4096,12,256,209568,4,12,54722396160,65280,(0,255),0),-5,(4,54722396160,0)),
+    ((33,900000000,100,2),(254,4096,12,256,105760,4,12,27507752960,65024,(0,127,254),0),-5,(4,27507752960,0)),
+    ((33,900000000,100,3),(255,4096,12,256,70528,4,12,18416271360,65280,(0,85,170,255),0),-5,(4,18416271360,0)),
+    ((33,900000000,100,8),(248,4096,12,256,27584,4,12,7005011968,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,7005011968,0)),
+    ((33,900000000,150,1),(255,4096,12,256,342160,4,12,89344819200,65280,(0,255),0),-5,(4,89344819200,0)),
+    ((33,900000000,150,2),(254,4096,12,256,172464,4,12,44857196544,65024,(0,127,254),0),-5,(4,44857196544,0)),
+    ((33,900000000,150,3),(255,4096,12,256,114896,4,12,30001643520,65280,(0,85,170,255),0),-5,(4,30001643520,0)),
+    ((33,900000000,150,8),(248,4096,12,256,44800,4,12,11377049600,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,11377049600,0)),
+    ((33,900000000,251,1),(255,4096,12,256,609648,4,12,159191285760,65280,(0,255),0),-5,(4,159191285760,0)),
+    ((33,900000000,251,2),(254,4096,12,256,306976,4,12,79843229696,65024,(0,127,254),0),-5,(4,79843229696,0)),
+    ((33,900000000,251,3),(255,4096,12,256,204336,4,12,53356216320,65280,(0,85,170,255),0),-5,(4,53356216320,0)),
+    ((33,900000000,251,8),(248,4096,12,256,79424,4,12,20169883648,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,20169883648,0)),
+    ((51,1,51,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((51,1,51,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((51,1,51,3),(3,1,0,1,896,4,12,10752,3,(0,1,2,3),0),-5,(4,10752,0)),
+    ((51,1,51,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((51,1,100,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((51,1,100,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((51,1,100,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((51,1,100,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((51,1,150,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((51,1,150,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((51,1,150,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((51,1,150,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((51,1,251,1),(1,1,0,1,2400,4,12,9600,1,(0,1),0),-5,(4,9600,0)),
+    ((51,1,251,2),(2,1,0,1,1296,4,12,10368,2,(0,1,2),0),-5,(4,10368,0)),
+    ((51,1,251,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((51,1,251,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((51,1000,51,1),(1,1,0,2,2400,4,12,19200,2,(0,1),0),-5,(4,19200,0)),
+    ((51,1000,51,2),(2,1,0,1,1840,4,12,14720,2,(0,1,2),0),-5,(4,14720,0)),
+    ((51,1000,51,3),(3,1,0,1,1152,4,12,13824,3,(0,1,2,3),0),-5,(4,13824,0)),
+    ((51,1000,51,8),(8,1,0,1,464,4,12,14848,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,14848,0)),
+    ((51,1000,100,1),(3,8,3,2,1872,4,12,44928,6,(0,3),0),-5,(4,44928,0)),
+    ((51,1000,100,2),(4,8,3,1,1712,4,12,27392,4,(0,2,4),0),-5,(4,27392,0)),
+    ((51,1000,100,3),(3,8,3,1,1792,4,12,21504,3,(0,1,2,3),0),-5,(4,21504,0)),
+    ((51,1000,100,8),(8,8,3,1,544,4,12,17408,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,17408,0)),
+    ((51,1000,150,1),(5,8,3,2,1760,4,12,70400,10,(0,5),0),-5,(4,70400,0)),
+    ((51,1000,150,2),(6,8,3,1,1680,4,12,40320,6,(0,3,6),0),-5,(4,40320,0)),
+    ((51,1000,150,3),(6,8,3,1,1312,4,12,31488,6,(0,2,4,6),0),-5,(4,31488,0)),
+    ((51,1000,150,8),(8,8,3,1,640,4,12,20480,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,20480,0)),
+    ((51,1000,251,1),(5,16,4,2,2912,4,12,116480,10,(0,5),0),-5,(4,116480,0)),
+    ((51,1000,251,2),(6,16,4,1,2656,4,12,63744,6,(0,3,6),0),-5,(4,63744,0)),
+    ((51,1000,251,3),(6,16,4,1,1952,4,12,46848,6,(0,2,4,6),0),-5,(4,46848,0)),
+    ((51,1000,251,8),(8,16,4,1,832,4,12,26624,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,26624,0)),
+    ((51,2000000,51,1),(21,32,5,256,1008,4,12,21676032,5376,(0,21),0),-5,(4,21676032,0)),
+    ((51,2000000,51,2),(22,32,5,256,560,4,12,12615680,5632,(0,11,22),0),-5,(4,12615680,0)),
+    ((51,2000000,51,3),(21,32,5,256,432,4,12,9289728,5376,(0,7,14,21),0),-5,(4,9289728,0)),
+    ((51,2000000,51,8),(24,32,5,256,208,4,12,5111808,6144,(0,3,6,9,12,15,18,21,24),0),-5,(4,5111808,0)),
+    ((51,2000000,100,1),(128,256,8,256,640,4,12,83886080,32768,(0,128),0),-5,(4,83886080,0)),
+    ((51,2000000,100,2),(128,256,8,256,384,4,12,50331648,32768,(0,64,128),0),-5,(4,50331648,0)),
+    ((51,2000000,100,3),(129,256,8,256,288,4,12,38043648,33024,(0,43,86,129),0),-5,(4,38043648,0)),
+    ((51,2000000,100,8),(128,256,8,256,176,4,12,23068672,32768,(0,16,32,48,64,80,96,112,128),0),-5,(4,23068672,0)),
+    ((51,2000000,150,1),(255,256,8,256,576,4,12,150405120,65280,(0,255),0),-5,(4,150405120,0)),
+    ((51,2000000,150,2),(254,256,8,256,352,4,12,91553792,65024,(0,127,254),0),-5,(4,91553792,0)),
+    ((51,2000000,150,3),(255,256,8,256,272,4,12,71024640,65280,(0,85,170,255),0),-5,(4,71024640,0)),
+    ((51,2000000,150,8),(248,256,8,256,160,4,12,40632320,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,40632320,0)),
+    ((51,2000000,251,1),(128,1024,10,256,1728,4,12,226492416,32768,(0,128),0),-5,(4,226492416,0)),
+    ((51,2000000,251,2),(128,1024,10,256,944,4,12,123731968,32768,(0,64,128),0),-5,(4,123731968,0)),
+    ((51,2000000,251,3),(129,1024,10,256,672,4,12,88768512,33024,(0,43,86,129),0),-5,(4,88768512,0)),
+    ((51,2000000,251,8),(128,1024,10,256,320,4,12,41943040,32768,(0,16,32,48,64,80,96,112,128),0),-5,(4,41943040,0)),
+    ((51,7500000,51,1),(39,64,6,256,1872,4,12,74760192,9984,(0,39),0),-5,(4,74760192,0)),
+    ((51,7500000,51,2),(40,64,6,256,1008,4,12,41287680,10240,(0,20,40),0),-5,(4,41287680,0)),
+    ((51,7500000,51,3),(39,64,6,256,736,4,12,29392896,9984,(0,13,26,39),0),-5,(4,29392896,0)),
+    ((51,7500000,51,8),(40,64,6,256,336,4,12,13762560,10240,(0,5,10,15,20,25,30,35,40),0),-5,(4,13762560,0)),
+    ((51,7500000,100,1),(239,512,9,256,1136,4,12,278020096,61184,(0,239),0),-5,(4,278020096,0)),
+    ((51,7500000,100,2),(240,512,9,256,640,4,12,157286400,61440,(0,120,240),0),-5,(4,157286400,0)),
+    ((51,7500000,100,3),(240,512,9,256,464,4,12,114032640,61440,(0,80,160,240),0),-5,(4,114032640,0)),
+    ((51,7500000,100,8),(240,512,9,256,240,4,12,58982400,61440,(0,30,60,90,120,150,180,210,240),0),-5,(4,58982400,0)),
+    ((51,7500000,150,1),(239,1024,10,256,1856,4,12,454230016,61184,(0,239),0),-5,(4,454230016,0)),
+    ((51,7500000,150,2),(240,1024,10,256,1008,4,12,247726080,61440,(0,120,240),0),-5,(4,247726080,0)),
+    ((51,7500000,150,3),(240,1024,10,256,720,4,12,176947200,61440,(0,80,160,240),0),-5,(4,176947200,0)),
+    ((51,7500000,150,8),(240,1024,10,256,352,4,12,86507520,61440,(0,30,60,90,120,150,180,210,240),0),-5,(4,86507520,0)),
+    ((51,7500000,251,1),(240,2048,11,256,3248,4,12,798228480,61440,(0,240),0),-5,(4,798228480,0)),
+    ((51,7500000,251,2),(240,2048,11,256,1728,4,12,424673280,61440,(0,120,240),0),-5,(4,424673280,0)),
+    ((51,7500000,251,3),(240,2048,11,256,1200,4,12,294912000,61440,(0,80,160,240),0),-5,(4,294912000,0)),
+    ((51,7500000,251,8),(240,2048,11,256,544,4,12,133693440,61440,(0,30,60,90,120,150,180,210,240),0),-5,(4,133693440,0)),
+    ((51,900000000,51,1),(144,2048,11,256,52800,4,12,7785676800,36864,(0,144),0),-5,(4,7785676800,0)),
+    ((51,900000000,51,2),(144,2048,11,256,26704,4,12,3937665024,36864,(0,72,144),0),-5,(4,3937665024,0)),
+    ((51,900000000,51,3),(144,2048,11,256,17968,4,12,2649489408,36864,(0,48,96,144),0),-5,(4,2649489408,0)),
+    ((51,900000000,51,8),(144,2048,11,256,6960,4,12,1026293760,36864,(0,18,36,54,72,90,108,126,144),0),-5,(4,1026293760,0)),
+    ((51,900000000,100,1),(255,4096,12,256,103424,4,12,27006074880,65280,(0,255),0),-5,(4,27006074880,0)),
+    ((51,900000000,100,2),(254,4096,12,256,52320,4,12,13608222720,65024,(0,127,254),0),-5,(4,13608222720,0)),
+    ((51,900000000,100,3),(255,4096,12,256,34960,4,12,9128755200,65280,(0,85,170,255),0),-5,(4,9128755200,0)),
+    ((51,900000000,100,8),(248,4096,12,256,13776,4,12,3498442752,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,3498442752,0)),
+    ((51,900000000,150,1),(255,4096,12,256,177968,4,12,46471004160,65280,(0,255),0),-5,(4,46471004160,0)),
+    ((51,900000000,150,2),(254,4096,12,256,89856,4,12,23371186176,65024,(0,127,254),0),-5,(4,23371186176,0)),
+    ((51,900000000,150,3),(255,4096,12,256,59952,4,12,15654666240,65280,(0,85,170,255),0),-5,(4,15654666240,0)),
+    ((51,900000000,150,8),(248,4096,12,256,23488,4,12,5964824576,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,5964824576,0)),
+    ((51,900000000,251,1),(255,4096,12,256,328256,4,12,85714206720,65280,(0,255),0),-5,(4,85714206720,0)),
+    ((51,900000000,251,2),(254,4096,12,256,165472,4,12,43038605312,65024,(0,127,254),0),-5,(4,43038605312,0)),
+    ((51,900000000,251,3),(255,4096,12,256,110256,4,12,28790046720,65280,(0,85,170,255),0),-5,(4,28790046720,0)),
+    ((51,900000000,251,8),(248,4096,12,256,42992,4,12,10917904384,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,10917904384,0)),
+    ((64,1,64,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((64,1,64,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((64,1,64,3),(3,1,0,1,896,4,12,10752,3,(0,1,2,3),0),-5,(4,10752,0)),
+    ((64,1,64,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((64,1,100,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((64,1,100,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((64,1,100,3),(3,1,0,1,896,4,12,10752,3,(0,1,2,3),0),-5,(4,10752,0)),
+    ((64,1,100,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((64,1,150,1),(1,1,0,1,2384,4,12,9536,1,(0,1),0),-5,(4,9536,0)),
+    ((64,1,150,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((64,1,150,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((64,1,150,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((64,1,251,1),(1,1,0,1,2400,4,12,9600,1,(0,1),0),-5,(4,9600,0)),
+    ((64,1,251,2),(2,1,0,1,1280,4,12,10240,2,(0,1,2),0),-5,(4,10240,0)),
+    ((64,1,251,3),(3,1,0,1,912,4,12,10944,3,(0,1,2,3),0),-5,(4,10944,0)),
+    ((64,1,251,8),(8,1,0,1,416,4,12,13312,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,13312,0)),
+    ((64,1000,64,1),(1,1,0,2,2400,4,12,19200,2,(0,1),0),-5,(4,19200,0)),
+    ((64,1000,64,2),(2,1,0,1,1840,4,12,14720,2,(0,1,2),0),-5,(4,14720,0)),
+    ((64,1000,64,3),(3,1,0,1,1152,4,12,13824,3,(0,1,2,3),0),-5,(4,13824,0)),
+    ((64,1000,64,8),(8,1,0,1,448,4,12,14336,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,14336,0)),
+    ((64,1000,100,1),(4,4,2,2,1120,4,12,35840,8,(0,4),0),-5,(4,35840,0)),
+    ((64,1000,100,2),(4,4,2,1,1408,4,12,22528,4,(0,2,4),0),-5,(4,22528,0)),
+    ((64,1000,100,3),(6,4,2,1,832,4,12,19968,6,(0,2,4,6),0),-5,(4,19968,0)),
+    ((64,1000,100,8),(8,4,2,1,512,4,12,16384,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,16384,0)),
+    ((64,1000,150,1),(4,8,3,2,1680,4,12,53760,8,(0,4),0),-5,(4,53760,0)),
+    ((64,1000,150,2),(4,8,3,1,1952,4,12,31232,4,(0,2,4),0),-5,(4,31232,0)),
+    ((64,1000,150,3),(6,8,3,1,1088,4,12,26112,6,(0,2,4,6),0),-5,(4,26112,0)),
+    ((64,1000,150,8),(8,8,3,1,576,4,12,18432,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,18432,0)),
+    ((64,1000,251,1),(8,8,3,2,1472,4,12,94208,16,(0,8),0),-5,(4,94208,0)),
+    ((64,1000,251,2),(8,8,3,1,1616,4,12,51712,8,(0,4,8),0),-5,(4,51712,0)),
+    ((64,1000,251,3),(9,8,3,1,1104,4,12,39744,9,(0,3,6,9),0),-5,(4,39744,0)),
+    ((64,1000,251,8),(8,8,3,1,720,4,12,23040,8,(0,1,2,3,4,5,6,7,8),0),-5,(4,23040,0)),
+    ((64,2000000,64,1),(21,32,5,256,1008,4,12,21676032,5376,(0,21),0),-5,(4,21676032,0)),
+    ((64,2000000,64,2),(22,32,5,256,544,4,12,12255232,5632,(0,11,22),0),-5,(4,12255232,0)),
+    ((64,2000000,64,3),(21,32,5,256,416,4,12,8945664,5376,(0,7,14,21),0),-5,(4,8945664,0)),
+    ((64,2000000,64,8),(24,32,5,256,208,4,12,5111808,6144,(0,3,6,9,12,15,18,21,24),0),-5,(4,5111808,0)),
+    ((64,2000000,100,1),(95,256,8,256,592,4,12,57589760,24320,(0,95),0),-5,(4,57589760,0)),
+    ((64,2000000,100,2),(96,256,8,256,352,4,12,34603008,24576,(0,48,96),0),-5,(4,34603008,0)),
+    ((64,2000000,100,3),(96,256,8,256,272,4,12,26738688,24576,(0,32,64,96),0),-5,(4,26738688,0)),
+    ((64,2000000,100,8),(96,256,8,256,160,4,12,15728640,24576,(0,12,24,36,48,60,72,84,96),0),-5,(4,15728640,0)),
+    ((64,2000000,150,1),(222,256,8,256,496,4,12,112754688,56832,(0,222),0),-5,(4,112754688,0)),
+    ((64,2000000,150,2),(222,256,8,256,304,4,12,69107712,56832,(0,111,222),0),-5,(4,69107712,0)),
+    ((64,2000000,150,3),(222,256,8,256,240,4,12,54558720,56832,(0,74,148,222),0),-5,(4,54558720,0)),
+    ((64,2000000,150,8),(224,256,8,256,144,4,12,33030144,57344,(0,28,56,84,112,140,168,196,224),0),-5,(4,33030144,0)),
+    ((64,2000000,251,1),(240,512,9,256,768,4,12,188743680,61440,(0,240),0),-5,(4,188743680,0)),
+    ((64,2000000,251,2),(240,512,9,256,448,4,12,110100480,61440,(0,120,240),0),-5,(4,110100480,0)),
+    ((64,2000000,251,3),(240,512,9,256,336,4,12,82575360,61440,(0,80,160,240),0),-5,(4,82575360,0)),
+    ((64,2000000,251,8),(240,512,9,256,192,4,12,47185920,61440,(0,30,60,90,120,150,180,210,240),0),-5,(4,47185920,0)),
+    ((64,7500000,64,1),(39,64,6,256,1856,4,12,74121216,9984,(0,39),0),-5,(4,74121216,0)),
+    ((64,7500000,64,2),(40,64,6,256,992,4,12,40632320,10240,(0,20,40),0),-5,(4,40632320,0)),
+    ((64,7500000,64,3),(39,64,6,256,720,4,12,28753920,9984,(0,13,26,39),0),-5,(4,28753920,0)),
+    ((64,7500000,64,8),(40,64,6,256,336,4,12,13762560,10240,(0,5,10,15,20,25,30,35,40),0),-5,(4,13762560,0)),
+    ((64,7500000,100,1),(177,512,9,256,1072,4,12,194297856,45312,(0,177),0),-5,(4,194297856,0)),
+    ((64,7500000,100,2),(178,512,9,256,592,4,12,107905024,45568,(0,89,178),0),-5,(4,107905024,0)),
+    ((64,7500000,100,3),(177,512,9,256,448,4,12,81199104,45312,(0,59,118,177),0),-5,(4,81199104,0)),
+    ((64,7500000,100,8),(184,512,9,256,224,4,12,42205184,47104,(0,23,46,69,92,115,138,161,184),0),-5,(4,42205184,0)),
+    ((64,7500000,150,1),(208,1024,10,256,1552,4,12,330563584,53248,(0,208),0),-5,(4,330563584,0)),
+    ((64,7500000,150,2),(208,1024,10,256,848,4,12,180617216,53248,(0,104,208),0),-5,(4,180617216,0)),
+    ((64,7500000,150,3),(210,1024,10,256,608,4,12,130744320,53760,(0,70,140,210),0),-5,(4,130744320,0)),
+    ((64,7500000,150,8),(208,1024,10,256,304,4,12,64749568,53248,(0,26,52,78,104,130,156,182,208),0),-5,(4,64749568,0)),
+    ((64,7500000,251,1),(225,2048,11,256,2592,4,12,597196800,57600,(0,225),0),-5,(4,597196800,0)),
+    ((64,7500000,251,2),(226,2048,11,256,1376,4,12,318439424,57856,(0,113,226),0),-5,(4,318439424,0)),
+    ((64,7500000,251,3),(225,2048,11,256,976,4,12,224870400,57600,(0,75,150,225),0),-5,(4,224870400,0)),
+    ((64,7500000,251,8),(232,2048,11,256,432,4,12,102629376,59392,(0,29,58,87,116,145,174,203,232),0),-5,(4,102629376,0)),
+    ((64,900000000,64,1),(144,2048,11,256,52160,4,12,7691304960,36864,(0,144),0),-5,(4,7691304960,0)),
+    ((64,900000000,64,2),(144,2048,11,256,26384,4,12,3890479104,36864,(0,72,144),0),-5,(4,3890479104,0)),
+    ((64,900000000,64,3),(144,2048,11,256,17744,4,12,2616459264,36864,(0,48,96,144),0),-5,(4,2616459264,0)),
+    ((64,900000000,64,8),(144,2048,11,256,6880,4,12,1014497280,36864,(0,18,36,54,72,90,108,126,144),0),-5,(4,1014497280,0)),
+    ((64,900000000,100,1),(255,4096,12,256,70704,4,12,18462228480,65280,(0,255),0),-5,(4,18462228480,0)),
+    ((64,900000000,100,2),(254,4096,12,256,35824,4,12,9317679104,65024,(0,127,254),0),-5,(4,9317679104,0)),
+    ((64,900000000,100,3),(255,4096,12,256,23968,4,12,6258524160,65280,(0,85,170,255),0),-5,(4,6258524160,0)),
+    ((64,900000000,100,8),(248,4096,12,256,9488,4,12,2409496576,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,2409496576,0)),
+    ((64,900000000,150,1),(255,4096,12,256,127376,4,12,33260421120,65280,(0,255),0),-5,(4,33260421120,0)),
+    ((64,900000000,150,2),(254,4096,12,256,64384,4,12,16746020864,65024,(0,127,254),0),-5,(4,16746020864,0)),
+    ((64,900000000,150,3),(255,4096,12,256,42992,4,12,11226071040,65280,(0,85,170,255),0),-5,(4,11226071040,0)),
+    ((64,900000000,150,8),(248,4096,12,256,16896,4,12,4290772992,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,4290772992,0)),
+    ((64,900000000,251,1),(255,4096,12,256,241600,4,12,63086592000,65280,(0,255),0),-5,(4,63086592000,0)),
+    ((64,900000000,251,2),(254,4096,12,256,121888,4,12,31702581248,65024,(0,127,254),0),-5,(4,31702581248,0)),
+    ((64,900000000,251,3),(255,4096,12,256,81248,4,12,21215477760,65280,(0,85,170,255),0),-5,(4,21215477760,0)),
+    ((64,900000000,251,8),(248,4096,12,256,31744,4,12,8061452288,63488,(0,31,62,93,124,155,186,217,248),0),-5,(4,8061452288,0)),
+)
+
+
+def test_exchange_plans_are_the_recorded_ones_field_by_field():
+    """The planner's arithmetic (fine buckets -> C1 x F2, records per segment, writers) is pinned against a recorded table: k on both
+    sides of the one-word key, one read to 900 M, reads of exactly k bases to 251, 1 to 8 destinations; the short form where the
+    shape has one, KV_ERR_NOTIMPL and an untouched plan where it has not."""
+    import ctypes
+    from kevlar_amd import _lib
+    lib = _lib.load()
+    names = ('C1', 'F2', 'fbits', 'nwg1', 'cap1', 'recw', 'm', 'seg_words', 'cnt_entries')
+    assert len(_MEX_PLANS) == 7 * 5 * 4 * 4
+    for (k, n_reads, read_len, ndest), want, short_rc, (short_recw, short_seg_words, short_flags) in _MEX_PLANS:
+        case = 'k {} reads {} length {} ndest {}'.format(k, n_reads, read_len, ndest)
+        p = _lib.MexPlan()
+        assert lib.kv_mex_plan_make(0, k, n_reads, read_len, ndest, ctypes.byref(p)) == 0, case
+        for name, value in zip(names, want):
+            assert int(getattr(p, name)) == value, (case, name)
+        assert tuple(int(p.c_lo[d]) for d in range(ndest + 1)) == want[9], case
+        assert int(p.flags) == want[10], case
+        assert lib.kv_mex_plan_short(ctypes.byref(p)) == short_rc, case
+        assert short_rc in (0, _lib.KV_ERR_NOTIMPL), case
+        assert (int(p.recw), int(p.seg_words), int(p.flags)) == (short_recw, short_seg_words, short_flags), case
+        for name, value in zip(names, want):                      # the short form keeps everything else
+            if name not in ('recw', 'seg_words'):
+                assert int(getattr(p, name)) == value, (case, name, 'short')
+        assert tuple(int(p.c_lo[d]) for d in range(ndest + 1)) == want[9], case
+
+
 def test_every_environment_switch_is_in_the_one_registry_of_two_classes(monkeypatch):
     """kevlar_amd/csrc/kv_knobs.h: the library and its wrapper look at the environment through ONE table (kv_host.hip).  No source
     calls getenv() beside the registry; every name a source asks for is registered with a class and a description; a TUNING switch is
