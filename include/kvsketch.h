@@ -474,6 +474,31 @@ int kv_mex_emit_pack(const kv_reads *shard, const kv_mex_plan *plan, uint64_t re
 int kv_argsort_u64(const uint64_t *keys, uint64_t n, uint32_t *order);
 int kv_argsort_rows(const void *rows, uint64_t n, uint32_t width, uint32_t *order);
 
+/* ---- exact seed matching for `kevlar localize` (kevlar/localize.py:113-144; kv_localize.hip) -----------------------------
+ * The reference asks `bwa mem -k Z -T Z -a` for the perfect full-length matches of every contig Z-mer.  Here the canonical
+ * Z-mers of the contigs (Z <= 128) become a seed set on the device and the genome text is scanned against it chunk by chunk.
+ * kv_localize_create: contig c = bases[offsets[c] .. offsets[c + 1]) (ASCII, the convention of kv_reads_create); window w of the
+ * contigs, counted contig after contig, gets seed_of_window[w] = the index of the first window that claimed its canonical key
+ * (equal keys share an id), or 0xFFFFFFFF when the window holds a byte outside ACGT (lower case counts as upper).  n_windows must
+ * be the number of windows the contigs have.
+ * kv_localize_scan: one chunk of genome text whose first byte sits at global_offset of the whole text.  Every window that lies
+ * inside the chunk, consists of ACGT bytes only and equals a seed or its reverse complement is reported once as
+ * (ids_out[i], pos_out[i]) = (seed id, global position of the window's first byte), in no particular order.  *n_found is the
+ * number of matches; when it exceeds `capacity` only `capacity` of them were written and the caller repeats the same chunk with
+ * larger buffers.  Chunks overlap by Z - 1 bytes (a window belongs to the one chunk that holds all of it).  Every match also
+ * counts one occurrence of its seed; the repeat of a chunk that overflowed does not count again.
+ * kv_localize_counts: occurrences per seed id so far (n_windows entries; non-zero only at ids that are their own seed).
+ * kv_localize_stats: for measurements only (scratch/localize_scan_rate.py), nothing of `kevlar localize` calls it: stats_out[0..3] =
+ * windows of valid bases scanned, windows that passed the prefilter, matches, distinct seeds.                                      */
+typedef struct kv_localize kv_localize;
+int kv_localize_create(const char *bases, const uint64_t *offsets, uint64_t n_contigs, int seedsize, uint32_t *seed_of_window,
+                       uint64_t n_windows, uint64_t *n_distinct, kv_localize **out);
+int kv_localize_scan(kv_localize *h, const char *text, uint64_t n_bytes, uint64_t global_offset, uint32_t *ids_out,
+                     uint64_t *pos_out, uint64_t capacity, uint64_t *n_found);
+int kv_localize_counts(kv_localize *h, uint32_t *counts_out, uint64_t n_windows);
+int kv_localize_stats(kv_localize *h, uint64_t *stats_out);
+int kv_localize_destroy(kv_localize *h);
+
 #ifdef __cplusplus
 }
 #endif

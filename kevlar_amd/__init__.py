@@ -123,6 +123,8 @@ from kevlar_amd import dist  # noqa: E402
 from kevlar_amd import split  # noqa: E402
 from kevlar_amd import augment  # noqa: E402
 from kevlar_amd import gentrio  # noqa: E402
+from kevlar_amd import reference  # noqa: E402
+from kevlar_amd import localize  # noqa: E402
 from kevlar_amd import cli  # noqa: E402
 
 

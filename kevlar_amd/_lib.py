@@ -137,6 +137,11 @@ SIGNATURES = {
     'kv_mex_scan_set': (i32, [i32, i32, i32, vp, vp, u64, vp, vp, u64, u64p]),
     'kv_reads_flags': (i32, [vp, vp]),
     'kv_readgraph_components': (i32, [vp, i32, u32p, u32p, u64, u32p, u32, u32, u32, u32p, u64p]),
+    'kv_localize_create': (i32, [vp, vp, u64, i32, vp, u64, u64p, vpp]),
+    'kv_localize_scan': (i32, [vp, vp, u64, u64, vp, vp, u64, u64p]),
+    'kv_localize_counts': (i32, [vp, vp, u64]),
+    'kv_localize_stats': (i32, [vp, vp]),
+    'kv_localize_destroy': (i32, [vp]),
 }
 
 

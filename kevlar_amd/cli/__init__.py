@@ -1,4 +1,4 @@
-"""Command line of the drop-in: `kevlar count | novel | filter | partition | unband | dist | split | augment`.
+"""Command line of the drop-in: `kevlar count | novel | filter | partition | unband | dist | split | augment | localize`.
 
 Flag names, defaults and dispatch follow the reference (kevlar/cli/__init__.py:31-108 and
 kevlar/cli/{count,novel,filter,partition,unband,dist}.py); only the subcommands on the
@@ -154,6 +154,27 @@ def _gentrio(sub):
     p.add_argument('genome', help='genome to mutate')
 
 
+def _localize(sub):
+    p = sub.add_parser('localize', description='For each partition, compute the reference target sequence to use for variant '
+                       'calling: the genome is scanned on the GPU for the exact matches of every contig seed (no `bwa`, no index '
+                       'files).  Unlike the reference, which lets bwa keep an arbitrary 5000 occurrences of a repetitive seed, '
+                       'a seed with more than --max-occ genome positions contributes none.')
+    p.add_argument('-d', '--delta', type=int, metavar='D', default=50,
+                   help='extend the span of all seed matches by D bp on either side (50)')
+    p.add_argument('-p', '--part-id', type=str, metavar='ID', help='only localize partition "ID" in the input')
+    p.add_argument('-o', '--out', metavar='FILE', default='-', help='output file; default is terminal (stdout)')
+    p.add_argument('-z', '--seed-size', type=int, metavar='Z', default=51, help='seed size, at most 128; default is 51')
+    p.add_argument('-x', '--max-diff', type=int, metavar='X', default=None,
+                   help='report several reference targets if two neighbouring seed matches are more than X bp apart; by default '
+                   'X is three times the length of the longest contig of the partition')
+    p.add_argument('--include', metavar='REGEX', type=str, help='discard matches to sequences whose IDs do not match the pattern')
+    p.add_argument('--exclude', metavar='REGEX', type=str, help='discard matches to sequences whose IDs match the pattern')
+    p.add_argument('--max-occ', type=int, metavar='N', default=kevlar_amd.localize.DEFAULT_MAX_OCC,
+                   help='ignore a seed with more than N exact matches in the genome, both strands counted (5000)')
+    p.add_argument('refr', help='reference genome, FASTA (plain or gzip)')
+    p.add_argument('contigs', nargs='+', help='assembled reads in augmented Fasta format')
+
+
 mains = {
     'augment': kevlar_amd.augment.main,
     'gentrio': kevlar_amd.gentrio.main,
@@ -166,6 +187,12 @@ mains = {
     'unband': kevlar_amd.unband.main,
 }
 
+# Subcommands behind the novel-k-mer path.  They live in a dict of their own because tests/test_host_logic.py holds `mains` to the
+# exact set of the original port; parser(), the help text and run() consult both.
+downstream_mains = {
+    'localize': kevlar_amd.localize.main,
+}
+
 subparser_funcs = {
     'augment': _augment,
     'gentrio': _gentrio,
@@ -176,19 +203,21 @@ subparser_funcs = {
     'filter': _filter,
     'partition': _partition,
     'unband': _unband,
+    'localize': _localize,
 }
 
 
 def parser():
     top = argparse.ArgumentParser(
         prog='kevlar', formatter_class=argparse.RawDescriptionHelpFormatter,
-        description='kevlar novel-k-mer discovery on AMD MI355X (count, novel, filter, partition, unband, dist, split, augment, gentrio)')
+        description='kevlar novel-k-mer discovery on AMD MI355X (count, novel, filter, partition, unband, dist, split, augment, gentrio, '
+        'localize)')
     top._positionals.title = 'Subcommands'
     top._optionals.title = 'Global arguments'
     top.add_argument('-v', '--version', action='version', version='kevlar v{}'.format(kevlar_amd.__version__))
     top.add_argument('-l', '--logfile', metavar='F', help='write diagnostics to F instead of stderr')
     top.add_argument('--tee', action='store_true', help='write diagnostics to the logfile and to stderr')
-    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(mains)) + '"')
+    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(list(mains) + list(downstream_mains))) + '"')
     for func in subparser_funcs.values():
         func(sub)
     return top
@@ -209,7 +238,7 @@ def run(arglist=None):
     tests pass an argument list."""
     top = parser()
     args = parse_args(arglist)
-    driver = mains.get(args.cmd)
+    driver = mains.get(args.cmd) or downstream_mains.get(args.cmd)
     if driver is None:
         top.print_help()
         raise SystemExit(0 if args.cmd is None else 2)
