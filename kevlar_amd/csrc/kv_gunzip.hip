@@ -48,6 +48,7 @@ namespace {
 
 #define GZ_WIN 32768u
 #define GZ_MARK 0x8000u
+#define GZ_NOTEXT 0x0100u            // a window position in front of the first byte of the text: no byte, no marker; a match that copies it is invalid
 #define GZ_FAST_LL 9                 // bits of the literal/length lookup table (9: 32 workgroups of LDS per CU)
 #define GZ_SLACK 2048u               // readable zero bytes behind the compressed buffer
 #define GZ_FIND_KEEP 4u                // block starts kept per chunk
@@ -243,9 +244,9 @@ __global__ __launch_bounds__(GZ_FIND_THREADS) void k_gz_find(const uint8_t *__re
 }
 
 // ---------------------------------------------------------------- 2. decode into symbols
-__device__ __forceinline__ bool gz_build_code(const uint8_t *lengths, int n, uint16_t *count, uint16_t *symbol, uint16_t *table, int fast)
+__device__ __forceinline__ bool gz_build_code(const uint8_t *lengths, int n, uint16_t *count, uint16_t *symbol, uint16_t *table, int fast, int kind)
 {
-    return build_code(lengths, n, count, symbol, table, fast);
+    return build_code(lengths, n, count, symbol, table, fast, kind);
 }
 
 template <int RBITS>                 // the decoder's LDS window: the last 2^RBITS symbols
@@ -294,9 +295,9 @@ __device__ uint32_t gz_block_codes(BitReader &br, GunzipShared<RBITS> &sh, uint3
             for (int s = 144; s < 256; ++s) sh.lengths[s] = 9;
             for (int s = 256; s < 280; ++s) sh.lengths[s] = 7;
             for (int s = 280; s < 288; ++s) sh.lengths[s] = 8;
-            ok = gz_build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL);
+            ok = gz_build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL, INF_CODE_FIXED);
             for (int s = 0; s < 30; ++s) sh.lengths[s] = 5;
-            ok = ok && gz_build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+            ok = ok && gz_build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_FIXED);
         }
     } else {
         const uint32_t nlen = br_bits(br, 5) + 257, ndist = br_bits(br, 5) + 1, ncode = br_bits(br, 4) + 4;
@@ -308,7 +309,7 @@ __device__ uint32_t gz_block_codes(BitReader &br, GunzipShared<RBITS> &sh, uint3
             const uint32_t v = br_bits(br, 3);
             if (lane == 0) sh.lengths[inf_clen_order(s)] = (uint8_t)v;
         }
-        if (lane == 0) ok = gz_build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7);
+        if (lane == 0) ok = gz_build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7, INF_CODE_PRECODE);
         ok = INF_UNI(ok);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -334,8 +335,8 @@ __device__ uint32_t gz_block_codes(BitReader &br, GunzipShared<RBITS> &sh, uint3
         __builtin_amdgcn_wave_barrier();
         if (lane == 0 && ok) {
             ok = sh.lengths[19 + 256] != 0;
-            ok = ok && gz_build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL);
-            ok = ok && gz_build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+            ok = ok && gz_build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL, INF_CODE_BLOCK);
+            ok = ok && gz_build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_BLOCK);
         }
     }
     ok = INF_UNI(ok);
@@ -653,7 +654,7 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t ballot)       // set bi
 }
 
 __global__ __launch_bounds__(256) void k_gz_tails(const uint16_t *__restrict__ syms, const uint64_t *__restrict__ out_off, const uint32_t *__restrict__ n_out,
-                                                  const uint8_t *__restrict__ window_in, uint16_t *__restrict__ tails, uint16_t *__restrict__ tails_b,
+                                                  const uint8_t *__restrict__ window_in, uint32_t window_valid, uint16_t *__restrict__ tails, uint16_t *__restrict__ tails_b,
                                                   uint32_t *__restrict__ list, uint64_t list_cap, unsigned long long *__restrict__ n_markers)
 {
     __shared__ uint32_t sh_wave[4];
@@ -661,7 +662,8 @@ __global__ __launch_bounds__(256) void k_gz_tails(const uint16_t *__restrict__ s
     const uint32_t q = blockIdx.x;
     uint16_t *t = tails + (size_t)q * GZ_WIN, *tb = tails_b + (size_t)q * GZ_WIN;
     if (q == 0) {
-        for (uint32_t i = threadIdx.x; i < GZ_WIN; i += blockDim.x) { const uint16_t v = window_in[i]; t[i] = v; tb[i] = v; }
+        // (only the last window_valid bytes of the window are text: the stream has not produced more yet)
+        for (uint32_t i = threadIdx.x; i < GZ_WIN; i += blockDim.x) { const uint16_t v = i + window_valid >= GZ_WIN ? window_in[i] : (uint16_t)GZ_NOTEXT; t[i] = v; tb[i] = v; }
         return;
     }
     const uint32_t n = n_out[q - 1];
@@ -777,7 +779,7 @@ __global__ __launch_bounds__(256) void k_gz_scan(const uint16_t *__restrict__ in
 // ---------------------------------------------------------------- 4. bytes
 #define GZ_RESOLVE_SPLIT 8u
 __global__ void k_gz_resolve(const uint16_t *__restrict__ syms, const uint64_t *__restrict__ out_off, const uint32_t *__restrict__ n_out,
-                             const uint64_t *__restrict__ text_base, const uint16_t *__restrict__ tails, uint8_t *__restrict__ text)
+                             const uint64_t *__restrict__ text_base, const uint16_t *__restrict__ tails, uint8_t *__restrict__ text, unsigned int *__restrict__ no_text)
 {
     const uint32_t q = blockIdx.x / GZ_RESOLVE_SPLIT, part = blockIdx.x % GZ_RESOLVE_SPLIT;
     const uint16_t *t = tails + (size_t)q * GZ_WIN;             // the window in front of stretch q
@@ -787,6 +789,7 @@ __global__ void k_gz_resolve(const uint16_t *__restrict__ syms, const uint64_t *
     for (uint32_t i = part * blockDim.x + threadIdx.x; i < n; i += GZ_RESOLVE_SPLIT * blockDim.x) {
         uint16_t v = src[i];
         if (v & GZ_MARK) v = t[v & (GZ_WIN - 1u)];
+        if (v & 0xff00u) atomicOr(no_text, 1u);        // GZ_NOTEXT: a match reached back in front of the first byte of the text
         dst[i] = (uint8_t)v;
     }
 }
@@ -929,6 +932,7 @@ struct KvGunzip {
     const uint64_t *d_off = nullptr, *d_base = nullptr;           // device copies of v_off / v_base / v_n
     const uint32_t *d_n = nullptr;
     const uint16_t *d_tails = nullptr;                            // the resolved tails of the pending segment
+    unsigned int *d_no_text = nullptr;                            // set by k_gz_resolve: a match of the pending segment copied what is in front of the text
     uint64_t stat_jobs = 0, stat_dropped = 0, stat_repairs = 0, stat_segments = 0, stat_rounds = 0, stat_cuts = 0;
     // optional: bytes [off, off + n) of the file to d_dst on the stream, through the caller's pinned staging buffers (false: not done)
     std::function<bool(uint8_t *, uint64_t, uint64_t, hipStream_t)> upload;
@@ -1247,11 +1251,12 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     KV_HIP(hipMemcpyAsync(d_n, g->v_n.data(), nv * 4, hipMemcpyHostToDevice, st));
     unsigned long long *d_markers = d_ctr + 1;
     unsigned long long markers = 0;
-    KV_HIP(hipMemsetAsync(d_markers, 0, 8, st));
+    KV_HIP(hipMemsetAsync(d_markers, 0, 16, st));      // ... and d_no_text behind it
+    g->d_no_text = (unsigned int *)(d_ctr + 2);
     {
         KvProfScope prof("k_gz_tails");
         hipLaunchKernelGGL(k_gz_tails, dim3((unsigned)(nv + 1)), dim3(256), 0, st, (const uint16_t *)d_syms, (const uint64_t *)d_off, (const uint32_t *)d_n,
-                           (const uint8_t *)g->a->window.p, t0, t1, l0, list_cap, d_markers);
+                           (const uint8_t *)g->a->window.p, (uint32_t)std::min<uint64_t>(g->seen_text, GZ_WIN), t0, t1, l0, list_cap, d_markers);
     }
     KV_HIP(hipMemcpyAsync(&markers, d_markers, 8, hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
@@ -1306,10 +1311,13 @@ int kv_gunzip_emit(KvGunzip *g, uint8_t *d_text)
     const uint16_t *tails = g->d_tails;
     {
         KvProfScope prof("k_gz_resolve");
-        hipLaunchKernelGGL(k_gz_resolve, dim3((unsigned)(nv * GZ_RESOLVE_SPLIT)), dim3(256), 0, st, (const uint16_t *)g->a->syms.p, g->d_off, g->d_n, g->d_base, tails, d_text);
+        hipLaunchKernelGGL(k_gz_resolve, dim3((unsigned)(nv * GZ_RESOLVE_SPLIT)), dim3(256), 0, st, (const uint16_t *)g->a->syms.p, g->d_off, g->d_n, g->d_base, tails, d_text, g->d_no_text);
         hipLaunchKernelGGL(k_gz_window_out, dim3(16), dim3(256), 0, st, tails + (uint64_t)nv * GZ_WIN, (uint8_t *)g->a->window.p);
     }
     KV_HIP(hipGetLastError());
+    unsigned int no_text = 0;
+    KV_HIP(hipMemcpyAsync(&no_text, g->d_no_text, 4, hipMemcpyDeviceToHost, st));
+    if (!g->crc_on) KV_HIP(hipStreamSynchronize(st));            // (with the CRC on, kv_crc32_ranges waits for the stream)
     if (g->crc_on) {
         // the text member by member (ends from the decoders), every member in slices of 16 KB: one thread each, joined here
         std::vector<uint64_t> r_start;
@@ -1346,6 +1354,10 @@ int kv_gunzip_emit(KvGunzip *g, uint8_t *d_text)
             }
             g->crc_run = run;
         }
+    }
+    if (no_text) {
+        kv_set_error("gzip stream: invalid DEFLATE data: a match reaches back in front of the first byte of the text");
+        return KV_ERR_TYPE;
     }
     g->seen_comp += (g->pending_pos - g->pos_bit) / 8;
     g->seen_text += g->pending_text;

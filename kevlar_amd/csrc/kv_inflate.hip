@@ -60,7 +60,8 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
         job_id = INF_UNI(job_id);
         if (job_id >= n_jobs) return;
         const InflateJob job = jobs[job_id];
-        if (job.isize == 0) continue;                 // BGZF's end-of-file marker, or an empty member
+        // (a member that announces no text -- BGZF's end-of-file marker -- is decoded like any other: its payload must still
+        // be a valid stream that produces nothing)
         BitReader br;                                 // identical in every lane
         br_init(br, comp + job.in_off);
         const uint32_t limit_words = (job.in_len + 3u) / 4u + 4u;     // a reader further than this has left the payload (damaged data)
@@ -110,9 +111,9 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
                     for (int s = 144; s < 256; ++s) sh.lengths[s] = 9;
                     for (int s = 256; s < 280; ++s) sh.lengths[s] = 7;
                     for (int s = 280; s < 288; ++s) sh.lengths[s] = 8;
-                    ok = build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL);
+                    ok = build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL, INF_CODE_FIXED);
                     for (int s = 0; s < 30; ++s) sh.lengths[s] = 5;
-                    ok = ok && build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+                    ok = ok && build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_FIXED);
                 }
             } else {
                 const uint32_t nlen = br_bits(br, 5) + 257, ndist = br_bits(br, 5) + 1, ncode = br_bits(br, 4) + 4;
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
                     if (lane == 0) sh.lengths[inf_clen_order(s)] = (uint8_t)v;
                 }
                 // the code-length code lives in the distance arrays for a moment
-                if (lane == 0) ok = build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7);
+                if (lane == 0) ok = build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7, INF_CODE_PRECODE);
                 ok = INF_UNI(ok);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -152,8 +153,8 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
                 __builtin_amdgcn_wave_barrier();
                 if (lane == 0 && ok) {
                     ok = sh.lengths[19 + 256] != 0;     // a block without an end code cannot end
-                    ok = ok && build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL);
-                    ok = ok && build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+                    ok = ok && build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL, INF_CODE_BLOCK);
+                    ok = ok && build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_BLOCK);
                 }
             }
             ok = INF_UNI(ok);

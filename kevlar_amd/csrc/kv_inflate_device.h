@@ -51,8 +51,11 @@ __device__ __forceinline__ uint32_t br_bits(BitReader &br, uint32_t n)   // n <=
 
 // canonical Huffman code of `n` symbols with the given lengths: count[len], symbols sorted by (len, symbol), and the
 // lookup table of the codes of at most `fast` bits (entry = symbol | len << 9; 0 = longer code).  Returns false if the
-// lengths oversubscribe the code space.
-__device__ bool build_code(const uint8_t *lengths, int n, uint16_t *count, uint16_t *symbol, uint16_t *table, int fast)
+// lengths oversubscribe the code space, or leave some of it unused where zlib's inflate (inftrees.c) does not take that:
+// the code-length code must be complete; a literal/length or distance code may be incomplete only if no code is longer
+// than one bit (a single code of length 1, or none at all); the fixed distance code (30 of 32 codes) is as it is.
+enum { INF_CODE_PRECODE = 0, INF_CODE_BLOCK = 1, INF_CODE_FIXED = 2 };
+__device__ bool build_code(const uint8_t *lengths, int n, uint16_t *count, uint16_t *symbol, uint16_t *table, int fast, int kind)
 {
     for (int l = 0; l <= 15; ++l) count[l] = 0;
     for (int s = 0; s < n; ++s) count[lengths[s]]++;
@@ -61,6 +64,11 @@ __device__ bool build_code(const uint8_t *lengths, int n, uint16_t *count, uint1
         left <<= 1;
         left -= count[l];
         if (left < 0) return false;
+    }
+    if (left > 0 && kind != INF_CODE_FIXED) {
+        if (kind == INF_CODE_PRECODE) return false;
+        for (int l = 2; l <= 15; ++l)
+            if (count[l]) return false;
     }
     uint16_t offs[16];
     offs[1] = 0;
@@ -116,7 +124,8 @@ __device__ __forceinline__ int decode_sym(BitReader &br, const uint16_t *count, 
 
 // The length / distance code tables of RFC 1951 section 3.2.5 as arithmetic: a table in constant memory is a vector load
 // here, and the s_waitcnt vmcnt(0) behind it also waits for every text store the wave still has in flight -- a
-// microsecond per match.  (tests/test_gpu_ingest.py compares the text with zlib over every length and distance code.)
+// microsecond per match.  (tests/test_gpu_deflate.py compares the text with zlib over every length and distance symbol, each
+// at its smallest and largest extra bits: group 'tables' of tests/deflate_common.py.)
 __device__ __forceinline__ uint32_t inf_len_extra(uint32_t ls) { return ls < 8u || ls == 28u ? 0u : (ls - 4u) >> 2; }
 __device__ __forceinline__ uint32_t inf_len_base(uint32_t ls)
 {
