@@ -244,27 +244,18 @@ __global__ __launch_bounds__(GZ_FIND_THREADS) void k_gz_find(const uint8_t *__re
 }
 
 // ---------------------------------------------------------------- 2. decode into symbols
-__device__ __forceinline__ bool gz_build_code(const uint8_t *lengths, int n, uint16_t *count, uint16_t *symbol, uint16_t *table, int fast, int kind)
-{
-    return build_code(lengths, n, count, symbol, table, fast, kind);
-}
-
 template <int RBITS>                 // the decoder's LDS window: the last 2^RBITS symbols
 struct GunzipShared {
     uint16_t ring[1 << RBITS];
-    uint16_t ll_table[1 << GZ_FAST_LL];
-    uint16_t d_table[1 << INF_FAST_D];
-    uint16_t ll_count[16], d_count[16];
-    uint16_t ll_symbol[288], d_symbol[32];
-    uint8_t lengths[352];
+    InfCodes<GZ_FAST_LL> codes;
     // where the stretch is to stop (kept here, not in registers: looked at once per block and when the target comes near)
     unsigned long long target, cur_header;
     uint32_t target_idx, pad;
 };
 
-// gzip member header at byte `at` of the buffer: returns the byte its deflate data start at, 0 if this is no header,
-// ~0 if the buffer ends inside it
-__device__ __attribute__((noinline)) uint64_t gz_member_header(const uint8_t *comp, uint64_t at, uint64_t n_bytes)
+// gzip member header at byte `at` of the buffer (on the device, or of a host image): returns the byte its deflate data
+// start at, 0 if this is no header, ~0 if the buffer ends inside it
+__host__ __device__ __attribute__((noinline)) uint64_t gz_member_header(const uint8_t *comp, uint64_t at, uint64_t n_bytes)
 {
     if (at + 18 > n_bytes) return ~0ull;
     if (comp[at] != 0x1f || comp[at + 1] != 0x8b || comp[at + 2] != 8 || (comp[at + 3] & 0xe0)) return 0;
@@ -281,68 +272,6 @@ __device__ __attribute__((noinline)) uint64_t gz_member_header(const uint8_t *co
         }
     if (flags & 2) p += 2;
     return p + 8 <= n_bytes ? p : ~0ull;
-}
-
-// The Huffman codes of a block whose 3 header bits have been read (btype 1: the fixed ones, 2: the ones the block spells
-// out) -> lookup tables in LDS.  All lanes take part; returns 0 for an invalid description.
-template <int RBITS>
-__device__ uint32_t gz_block_codes(BitReader &br, GunzipShared<RBITS> &sh, uint32_t lane, uint32_t btype)
-{
-    uint32_t ok = 1;
-    if (btype == 1) {
-        if (lane == 0) {
-            for (int s = 0; s < 144; ++s) sh.lengths[s] = 8;
-            for (int s = 144; s < 256; ++s) sh.lengths[s] = 9;
-            for (int s = 256; s < 280; ++s) sh.lengths[s] = 7;
-            for (int s = 280; s < 288; ++s) sh.lengths[s] = 8;
-            ok = gz_build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL, INF_CODE_FIXED);
-            for (int s = 0; s < 30; ++s) sh.lengths[s] = 5;
-            ok = ok && gz_build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_FIXED);
-        }
-    } else {
-        const uint32_t nlen = br_bits(br, 5) + 257, ndist = br_bits(br, 5) + 1, ncode = br_bits(br, 4) + 4;
-        if (nlen > 286 || ndist > 30) return 0;
-        if (lane < 19) sh.lengths[lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t s = 0; s < ncode; ++s) {
-            const uint32_t v = br_bits(br, 3);
-            if (lane == 0) sh.lengths[inf_clen_order(s)] = (uint8_t)v;
-        }
-        if (lane == 0) ok = gz_build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7, INF_CODE_PRECODE);
-        ok = INF_UNI(ok);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t idx = 0, prev = 0;
-        while (ok && idx < nlen + ndist) {
-            const int sym = decode_sym(br, sh.d_count, sh.d_symbol, sh.d_table, 7);
-            if (sym < 0) { ok = 0; break; }
-            uint32_t rep = 1, val = (uint32_t)sym;
-            if (sym == 16) {
-                if (idx == 0) { ok = 0; break; }
-                val = prev;
-                rep = 3 + br_bits(br, 2);
-            } else if (sym == 17) { val = 0; rep = 3 + br_bits(br, 3); }
-            else if (sym == 18) { val = 0; rep = 11 + br_bits(br, 7); }
-            if (idx + rep > nlen + ndist) { ok = 0; break; }
-            if (lane < rep) sh.lengths[19 + idx + lane] = (uint8_t)val;
-            if (lane + 64 < rep) sh.lengths[19 + idx + lane + 64] = (uint8_t)val;
-            if (lane + 128 < rep) sh.lengths[19 + idx + lane + 128] = (uint8_t)val;
-            idx += rep;
-            prev = val;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0 && ok) {
-            ok = sh.lengths[19 + 256] != 0;
-            ok = ok && gz_build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL, INF_CODE_BLOCK);
-            ok = ok && gz_build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_BLOCK);
-        }
-    }
-    ok = INF_UNI(ok);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return ok;
 }
 
 // ---------------------------------------------------------------- 1b. symbol boundaries inside a block
@@ -401,7 +330,7 @@ __global__ __launch_bounds__(64) void k_gz_sync(const uint8_t *__restrict__ comp
     (void)br_bits(br, 1);
     const uint32_t btype = br_bits(br, 2);
     if (btype != 1 && btype != 2) return;
-    if (!gz_block_codes(br, sh, lane, btype)) return;
+    if (!inf_block_codes(br, sh.codes, lane, btype)) return;
     const uint64_t limit = n_bytes * 8ull;
     const uint64_t horizon = guess.guess_bit + 64 + 4096;
     if (horizon + 4096 > limit) return;
@@ -413,7 +342,7 @@ __global__ __launch_bounds__(64) void k_gz_sync(const uint8_t *__restrict__ comp
     bool ok = true;
     uint64_t pos = mine;
     for (int steps = 0; ok && pos < horizon && steps < 4096; ++steps) {
-        const int sym = lane_symbol(b, words, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL);
+        const int sym = lane_symbol(b, words, sh.codes.ll_count, sh.codes.ll_symbol, sh.codes.ll_table, GZ_FAST_LL);
         if (sym < 0 || sym == 256) ok = false;          // no code, or the block would end: not a place to start from
         else if (sym > 256) {
             const uint32_t ls = (uint32_t)sym - 257u;
@@ -421,7 +350,7 @@ __global__ __launch_bounds__(64) void k_gz_sync(const uint8_t *__restrict__ comp
             lane_need(b, words);
             const uint32_t le = inf_len_extra(ls);
             b.buf >>= le; b.cnt -= le;
-            const int ds = lane_symbol(b, words, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+            const int ds = lane_symbol(b, words, sh.codes.d_count, sh.codes.d_symbol, sh.codes.d_table, INF_FAST_D);
             if (ds < 0 || ds >= 30) { ok = false; break; }
             lane_need(b, words);
             const uint32_t de = inf_dist_extra((uint32_t)ds);
@@ -540,7 +469,7 @@ __global__ __launch_bounds__(64, 8) void k_gz_decode(const uint8_t *__restrict__
                 __builtin_amdgcn_wave_barrier();
                 br_seek(br, words, (from_byte + stored_len) * 8);
             } else {
-                const uint32_t ok = gz_block_codes(br, sh, lane, btype);
+                const uint32_t ok = inf_block_codes(br, sh.codes, lane, btype);
                 if (!ok) { status = GZ_BAD; break; }
                 if (mid_block) { br_seek(br, words, job.start_bit); mid_block = false; }
                 // ---- symbols
@@ -555,7 +484,7 @@ __global__ __launch_bounds__(64, 8) void k_gz_decode(const uint8_t *__restrict__
                         status = GZ_LANDED;
                         break;
                     }
-                    const int sym = decode_sym(br, sh.ll_count, sh.ll_symbol, sh.ll_table, GZ_FAST_LL);
+                    const int sym = decode_sym(br, sh.codes.ll_count, sh.codes.ll_symbol, sh.codes.ll_table, GZ_FAST_LL);
                     if ((uint32_t)sym < 256u) {
                         lit = lane == n_lit ? (uint32_t)sym : lit;
                         if (++n_lit == 64) {
@@ -573,7 +502,7 @@ __global__ __launch_bounds__(64, 8) void k_gz_decode(const uint8_t *__restrict__
                     const int ls = sym - 257;
                     if (ls >= 29) { status = GZ_BAD; break; }
                     const uint32_t len = inf_len_base((uint32_t)ls) + br_bits(br, inf_len_extra((uint32_t)ls));
-                    const int ds = decode_sym(br, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+                    const int ds = decode_sym(br, sh.codes.d_count, sh.codes.d_symbol, sh.codes.d_table, INF_FAST_D);
                     if (ds < 0 || ds >= 30) { status = GZ_BAD; break; }
                     const uint32_t extra = inf_dist_extra((uint32_t)ds);
                     br_need(br, 16);
@@ -836,26 +765,6 @@ __global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text
     out[r] = c ^ 0xffffffffu;
 }
 
-// start of the deflate data of the gzip member at byte `at` of a host image; 0 if there is no member header there
-uint64_t host_member_header(const uint8_t *file, uint64_t size, uint64_t at)
-{
-    if (at + 18 > size) return 0;
-    if (file[at] != 0x1f || file[at + 1] != 0x8b || file[at + 2] != 8 || (file[at + 3] & 0xe0)) return 0;
-    const uint32_t flags = file[at + 3];
-    uint64_t p = at + 10;
-    if (flags & 4) {
-        const uint32_t xlen = file[p] | (file[p + 1] << 8);
-        p += 2 + xlen;
-    }
-    for (int field = 0; field < 2; ++field)
-        if (flags & (field == 0 ? 8 : 16)) {
-            while (p < size && file[p]) ++p;
-            ++p;
-        }
-    if (flags & 2) p += 2;
-    return p + 8 <= size ? p : 0;
-}
-
 }  // namespace
 
 // CRC-32 of ranges of text that sits on the device: out[r] for d_text[start[r], start[r] + len[r]); returns when they are there
@@ -946,8 +855,8 @@ void kv_gunzip_set_uploader(KvGunzip *g, std::function<bool(uint8_t *, uint64_t,
 
 KvGunzip *kv_gunzip_open(const uint8_t *image, uint64_t size, KvGunzipArenas *arenas)
 {
-    const uint64_t data = host_member_header(image, size, 0);
-    if (!data) return nullptr;
+    const uint64_t data = gz_member_header(image, 0, size);
+    if (data == 0 || data == ~0ull) return nullptr;
     KvGunzip *g = new KvGunzip();
     g->image = image;
     g->size = size;
@@ -968,7 +877,7 @@ void kv_gunzip_stats(const KvGunzip *g, uint64_t out[4])
     out[0] = g->stat_segments; out[1] = g->stat_jobs; out[2] = g->stat_dropped; out[3] = g->stat_repairs;
 }
 
-static int gz_run_jobs(KvGunzip *g, const uint8_t *d_comp, uint64_t n_bytes, bool is_file_end, const GzJob *jobs, size_t n, GzJob *d_jobs,
+static int gz_run_jobs(const uint8_t *d_comp, uint64_t n_bytes, bool is_file_end, const GzJob *jobs, size_t n, GzJob *d_jobs,
                        const unsigned long long *d_starts, const unsigned long long *d_headers, uint64_t terminal_bit, bool exact, GzResult *d_results, unsigned long long *d_ctr, uint16_t *d_syms,
                        GzResult *results)
 {
@@ -986,7 +895,6 @@ static int gz_run_jobs(KvGunzip *g, const uint8_t *d_comp, uint64_t n_bytes, boo
     KV_HIP(hipGetLastError());
     KV_HIP(hipMemcpyAsync(results, d_results, n * sizeof(GzResult), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
-    (void)g;
     return KV_OK;
 }
 
@@ -1009,6 +917,8 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
         t_mark = now;
     };
     const uint32_t CH = g->chunk_bytes;
+    // consecutive pieces of an arena, each a multiple of 256 bytes
+    auto take = [](unsigned char *&at, uint64_t bytes) { unsigned char *piece = at; at += kv_round_up(bytes, 256); return piece; };
     const uint64_t margin = 4ull << 20;
     // ---- the compressed bytes of the segment, and behind them a margin in which the next segment's first block is looked for
     const uint64_t first_byte = (g->pos_bit >> 3) & ~255ull;
@@ -1028,10 +938,11 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     const uint64_t b_cand = kv_round_up((uint64_t)n_chunks * GZ_FIND_KEEP * 8, 256);
     const uint64_t max_guesses = (uint64_t)n_chunks * GZ_FIND_KEEP * 7 + 8;          // seven cuts per stretch at most
     KV_HIP(g->a->small.need(b_cand + 256 + kv_round_up(max_guesses * sizeof(GzGuess), 256) + kv_round_up(max_guesses * 8, 256)));
-    unsigned long long *d_cand = (unsigned long long *)g->a->small.p;
-    unsigned long long *d_ctr = (unsigned long long *)((unsigned char *)g->a->small.p + b_cand);
-    GzGuess *d_guesses = (GzGuess *)((unsigned char *)g->a->small.p + b_cand + 256);
-    unsigned long long *d_found = (unsigned long long *)((unsigned char *)d_guesses + kv_round_up(max_guesses * sizeof(GzGuess), 256));
+    unsigned char *small = (unsigned char *)g->a->small.p;
+    unsigned long long *d_cand = (unsigned long long *)take(small, b_cand);
+    unsigned long long *d_ctr = (unsigned long long *)take(small, 256);
+    GzGuess *d_guesses = (GzGuess *)take(small, max_guesses * sizeof(GzGuess));
+    unsigned long long *d_found = (unsigned long long *)take(small, max_guesses * 8);
     {
         KvProfScope prof("k_gz_find");
         hipLaunchKernelGGL(k_gz_find, dim3(n_chunks), dim3(GZ_FIND_THREADS), CH + GZ_SLACK + 8, st, (const uint8_t *)d_comp, n_bytes, CH, n_chunks, d_cand);
@@ -1111,6 +1022,8 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     bool exact = false;                                 // does any stretch begin inside a block?
     for (size_t i = 0; i < starts.size() && !exact; ++i) exact = headers[i] != starts[i];
     const double factor = std::min(std::max(2.5 * g->ratio, 8.0), 64.0);
+    // symbols of room for a stretch of `bits` of compressed data
+    auto room = [factor](uint64_t bits) { return (uint32_t)std::min<uint64_t>((uint64_t)((double)(bits / 8 + 1) * factor) + 16384, 0x7ffffff0u); };
     std::vector<GzJob> jobs(n_first);
     uint64_t total_cap = 0;
     for (size_t j = 0; j < n_first; ++j) {
@@ -1123,7 +1036,7 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
         jobs[j].header_bit = headers[j];
         jobs[j].target_idx = j + 1;                     // (starts[] on the device ends with ~0)
         jobs[j].out_off = total_cap;
-        jobs[j].out_cap = (uint32_t)std::min<uint64_t>((uint64_t)((double)((next - starts[j]) / 8 + 1) * factor) + 16384, 0x7ffffff0u);
+        jobs[j].out_cap = room(next - starts[j]);
         jobs[j].pad = 0;
         total_cap += kv_round_up(jobs[j].out_cap, 64);
     }
@@ -1132,13 +1045,14 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     KV_HIP(g->a->syms.need((total_cap + repair_room) * 2 + 256));
     KV_HIP(g->a->meta.need(kv_round_up(max_jobs * sizeof(GzJob), 256) + kv_round_up(max_jobs * sizeof(GzResult), 256) + kv_round_up(max_jobs * 8, 256) * 2 +
                         kv_round_up(max_jobs * 4, 256) + 2 * kv_round_up((starts.size() + 1) * 8, 256)));
-    GzJob *d_jobs = (GzJob *)g->a->meta.p;
-    GzResult *d_results = (GzResult *)((unsigned char *)d_jobs + kv_round_up(max_jobs * sizeof(GzJob), 256));
-    uint64_t *d_off = (uint64_t *)((unsigned char *)d_results + kv_round_up(max_jobs * sizeof(GzResult), 256));
-    uint64_t *d_base = (uint64_t *)((unsigned char *)d_off + kv_round_up(max_jobs * 8, 256));
-    uint32_t *d_n = (uint32_t *)((unsigned char *)d_base + kv_round_up(max_jobs * 8, 256));
-    unsigned long long *d_starts = (unsigned long long *)((unsigned char *)d_n + kv_round_up(max_jobs * 4, 256));
-    unsigned long long *d_headers = (unsigned long long *)((unsigned char *)d_starts + kv_round_up((starts.size() + 1) * 8, 256));
+    unsigned char *meta = (unsigned char *)g->a->meta.p;
+    GzJob *d_jobs = (GzJob *)take(meta, max_jobs * sizeof(GzJob));
+    GzResult *d_results = (GzResult *)take(meta, max_jobs * sizeof(GzResult));
+    uint64_t *d_off = (uint64_t *)take(meta, max_jobs * 8);
+    uint64_t *d_base = (uint64_t *)take(meta, max_jobs * 8);
+    uint32_t *d_n = (uint32_t *)take(meta, max_jobs * 4);
+    unsigned long long *d_starts = (unsigned long long *)take(meta, (starts.size() + 1) * 8);
+    unsigned long long *d_headers = (unsigned long long *)take(meta, (starts.size() + 1) * 8);
     {
         std::vector<unsigned long long> with_end(starts.begin(), starts.end()), kinds(headers.begin(), headers.end());
         with_end.push_back(~0ull);
@@ -1149,20 +1063,23 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     }
     uint16_t *d_syms = (uint16_t *)g->a->syms.p;
     std::vector<GzResult> results(n_first);
-    { const int rc = gz_run_jobs(g, d_comp, n_bytes, is_file_end, jobs.data(), n_first, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, results.data()); if (rc != KV_OK) return rc; }
+    { const int rc = gz_run_jobs(d_comp, n_bytes, is_file_end, jobs.data(), n_first, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, results.data()); if (rc != KV_OK) return rc; }
     lap("jobs + decode");
     // ---- the chain: stretch 0 starts at a known block; a later one counts iff a good stretch ends exactly on its start
     g->v_off.clear(); g->v_n.clear(); g->v_base.clear(); g->pending_ends.clear();
     bool crc_lost = false;
-    auto note_ends = [&](const GzResult &r, uint64_t base) {
-        if (r.members >= 1) g->pending_ends.emplace_back(base + r.trailer_at, r.trailer_crc);
-        if (r.members > 1) crc_lost = true;
-    };
     uint64_t repair_used = 0, text = 0, end_rel = 0;
     uint32_t repairs = 0, isize_seg = 0;
     bool ended = false;
     GzJob cur_job = jobs[0];
     GzResult cur = results[0];
+    auto accept = [&]() {                              // cur is part of the text
+        g->v_off.push_back(cur_job.out_off); g->v_n.push_back(cur.n_out); g->v_base.push_back(text);
+        if (cur.members >= 1) g->pending_ends.emplace_back(text + cur.trailer_at, cur.trailer_crc);
+        if (cur.members > 1) crc_lost = true;
+        text += cur.n_out;
+        isize_seg += cur.isize_sum;
+    };
     for (;;) {
         if (cur.status == GZ_FULL || (cur.status == GZ_LANDED && cur.end_bit < stop_rel && !std::binary_search(starts.begin() + 1, starts.end(), cur.end_bit))) {
             // out of room, or the stretch ran over a false start and stopped at a block nobody began at: decode again, from
@@ -1173,16 +1090,13 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
                 again = cur_job;
                 again.out_cap = (uint32_t)std::min<uint64_t>((uint64_t)cur_job.out_cap * 32, 0x7ffffff0u);
             } else {
-                g->v_off.push_back(cur_job.out_off); g->v_n.push_back(cur.n_out); g->v_base.push_back(text);
-                note_ends(cur, text);
-                text += cur.n_out;
-                isize_seg += cur.isize_sum;
+                accept();
                 again.start_bit = cur.end_bit;
                 again.header_bit = cur.end_bit;
                 const auto nx = std::upper_bound(starts.begin() + 1, starts.end(), cur.end_bit);
                 again.target_idx = (uint64_t)(nx - starts.begin());
                 const uint64_t next = nx == starts.end() ? n_bytes * 8 : *nx;
-                again.out_cap = (uint32_t)std::min<uint64_t>((uint64_t)((double)((next - again.start_bit) / 8 + 1) * factor) + 16384, 0x7ffffff0u);
+                again.out_cap = room(next - again.start_bit);
             }
             again.pad = 0;
             again.out_off = total_cap + repair_used;
@@ -1191,10 +1105,8 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
                 kv_set_error("gzip stream at byte %llu: too many stretches needed decoding again", (unsigned long long)(first_byte + cur_job.start_bit / 8));
                 return KV_ERR_TYPE;
             }
-            GzResult r;
-            { const int rc = gz_run_jobs(g, d_comp, n_bytes, is_file_end, &again, 1, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, &r); if (rc != KV_OK) return rc; }
+            { const int rc = gz_run_jobs(d_comp, n_bytes, is_file_end, &again, 1, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, &cur); if (rc != KV_OK) return rc; }
             cur_job = again;
-            cur = r;
             continue;
         }
         if (cur.status == GZ_BAD || cur.status == GZ_SHORT) {
@@ -1202,10 +1114,7 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
                          (unsigned long long)(first_byte + cur.end_bit / 8));
             return KV_ERR_TYPE;
         }
-        g->v_off.push_back(cur_job.out_off); g->v_n.push_back(cur.n_out); g->v_base.push_back(text);
-        note_ends(cur, text);
-        text += cur.n_out;
-        isize_seg += cur.isize_sum;
+        accept();
         end_rel = cur.end_bit;
         if (cur.status == GZ_END) { ended = true; break; }
         if (cur.end_bit >= stop_rel) break;

@@ -40,11 +40,7 @@ struct InflateJob {
 template <int RBITS>
 struct InflateShared {
     uint8_t ring[1 << RBITS];      // the last 2^RBITS bytes of text (byte t of the member at t mod 2^RBITS)
-    uint16_t ll_table[1 << INF_FAST_LL];
-    uint16_t d_table[1 << INF_FAST_D];
-    uint16_t ll_count[16], d_count[16];
-    uint16_t ll_symbol[288], d_symbol[32];
-    uint8_t lengths[352];          // 19 code-length codes, then up to 286 + 30 code lengths
+    InfCodes<INF_FAST_LL> codes;
 };
 
 template <int RBITS>
@@ -103,69 +99,17 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
                 flush();
                 continue;
             }
-            if (btype == 3) { failed = true; break; }
-            uint32_t ok = 1;
-            if (btype == 1) {
-                if (lane == 0) {
-                    for (int s = 0; s < 144; ++s) sh.lengths[s] = 8;
-                    for (int s = 144; s < 256; ++s) sh.lengths[s] = 9;
-                    for (int s = 256; s < 280; ++s) sh.lengths[s] = 7;
-                    for (int s = 280; s < 288; ++s) sh.lengths[s] = 8;
-                    ok = build_code(sh.lengths, 288, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL, INF_CODE_FIXED);
-                    for (int s = 0; s < 30; ++s) sh.lengths[s] = 5;
-                    ok = ok && build_code(sh.lengths, 30, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_FIXED);
-                }
-            } else {
-                const uint32_t nlen = br_bits(br, 5) + 257, ndist = br_bits(br, 5) + 1, ncode = br_bits(br, 4) + 4;
-                if (nlen > 286 || ndist > 30) { failed = true; break; }
-                if (lane < 19) sh.lengths[lane] = 0;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                for (uint32_t s = 0; s < ncode; ++s) {
-                    const uint32_t v = br_bits(br, 3);
-                    if (lane == 0) sh.lengths[inf_clen_order(s)] = (uint8_t)v;
-                }
-                // the code-length code lives in the distance arrays for a moment
-                if (lane == 0) ok = build_code(sh.lengths, 19, sh.d_count, sh.d_symbol, sh.d_table, 7, INF_CODE_PRECODE);
-                ok = INF_UNI(ok);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                uint32_t idx = 0, prev = 0;
-                while (ok && idx < nlen + ndist) {
-                    const int sym = decode_sym(br, sh.d_count, sh.d_symbol, sh.d_table, 7);
-                    if (sym < 0) { ok = 0; break; }
-                    uint32_t rep = 1, val = (uint32_t)sym;
-                    if (sym == 16) {
-                        if (idx == 0) { ok = 0; break; }
-                        val = prev;
-                        rep = 3 + br_bits(br, 2);
-                    } else if (sym == 17) { val = 0; rep = 3 + br_bits(br, 3); }
-                    else if (sym == 18) { val = 0; rep = 11 + br_bits(br, 7); }
-                    if (idx + rep > nlen + ndist) { ok = 0; break; }
-                    if (lane < rep) sh.lengths[19 + idx + lane] = (uint8_t)val;       // rep <= 138: at most three rows
-                    if (lane + 64 < rep) sh.lengths[19 + idx + lane + 64] = (uint8_t)val;
-                    if (lane + 128 < rep) sh.lengths[19 + idx + lane + 128] = (uint8_t)val;
-                    idx += rep;
-                    prev = val;
-                }
-                if (br.next > limit_words) ok = 0;      // the header alone can be ~560 bytes: a truncated member ends here
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                if (lane == 0 && ok) {
-                    ok = sh.lengths[19 + 256] != 0;     // a block without an end code cannot end
-                    ok = ok && build_code(sh.lengths + 19, (int)nlen, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL, INF_CODE_BLOCK);
-                    ok = ok && build_code(sh.lengths + 19 + nlen, (int)ndist, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D, INF_CODE_BLOCK);
-                }
-            }
-            ok = INF_UNI(ok);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (!ok) { failed = true; break; }
+            // (the header alone can be ~560 bytes: a member truncated inside it ends on the check behind the call.  The one in
+            // front of it decides nothing that one would not -- a reader that far out fails either way -- and is
+            // there for the register allocator: without it the kernel needs 332 B of scratch per lane, with it 248;
+            // profiles/README.md.  Do not remove it as redundant without looking at the kernel's resource usage)
+            if (btype == 3 || br.next > limit_words) { failed = true; break; }
+            if (!inf_block_codes(br, sh.codes, lane, btype) || br.next > limit_words) { failed = true; break; }
             // ---- symbols
             // (the size and the end of the payload are checked when text is stored, not per literal: the loop is bound by the
             // number of instructions it issues)
             for (;;) {
-                const int sym = decode_sym(br, sh.ll_count, sh.ll_symbol, sh.ll_table, INF_FAST_LL);
+                const int sym = decode_sym(br, sh.codes.ll_count, sh.codes.ll_symbol, sh.codes.ll_table, INF_FAST_LL);
                 if ((uint32_t)sym < 256u) {
                     lit = lane == n_lit ? (uint32_t)sym : lit;
                     if (++n_lit == 64) {
@@ -180,7 +124,7 @@ __global__ __launch_bounds__(64, 8) void k_inflate(const uint8_t *__restrict__ c
                 const int ls = sym - 257;
                 if (ls >= 29) { failed = true; break; }
                 const uint32_t len = inf_len_base((uint32_t)ls) + br_bits(br, inf_len_extra((uint32_t)ls));
-                const int ds = decode_sym(br, sh.d_count, sh.d_symbol, sh.d_table, INF_FAST_D);
+                const int ds = decode_sym(br, sh.codes.d_count, sh.codes.d_symbol, sh.codes.d_table, INF_FAST_D);
                 if (ds < 0 || ds >= 30) { failed = true; break; }
                 const uint32_t extra = inf_dist_extra((uint32_t)ds);
                 br_need(br, 16);
@@ -262,7 +206,7 @@ int kv_bgzf_index(const uint8_t *file, uint64_t size, std::vector<KvBgzfMember> 
 }
 
 // Inflate members [first, first + count) of a BGZF image whose bytes [comp_base, comp_base + comp_len) sit at d_comp (with
-// 512 readable bytes behind them): member i's text goes to d_text + text_off[i].  Runs on the calling thread's stream and
+// KV_INFLATE_SLACK readable, zeroed bytes behind them): member i's text goes to d_text + text_off[i].  Runs on the calling thread's stream and
 // returns once the text is there.
 int kv_bgzf_inflate(const uint8_t *d_comp, uint64_t comp_base, const KvBgzfMember *members, uint64_t count, const uint64_t *text_off,
                     uint8_t *d_text, KvArena &scratch)
