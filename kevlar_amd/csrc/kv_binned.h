@@ -1,9 +1,6 @@
 // kv_binned.h -- geometry and host entry points of the partitioned count (kv_binned.hip), shared with the
 // super-k-mer front end (kv_skm.hip), which feeds the same coarse buckets with (bin, count) items.
 #pragma once
-#include <map>
-#include <mutex>
-
 #include "kv_internal.h"
 
 #define BIN_C 64            // most coarse buckets per table
@@ -86,48 +83,7 @@ __device__ __forceinline__ void spill_items_wave(const BinGeom &g, const uint64_
 }
 #endif
 
-// grow-only device scratch; one arena per stream so host threads counting different samples do not share buffers
-struct KvArena {
-    void *p = nullptr;
-    size_t bytes = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    hipError_t need(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        kv_thread_device();
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        // an eighth of headroom: the geometry of the next batch (bucket sizes follow the previous batch's statistics) may
-        // ask for a little more, and releasing and allocating gigabytes costs a hundred milliseconds
-        const size_t roomy = n + n / 8;
-        hipError_t e = hipMalloc(&p, roomy);
-        if (e == hipSuccess) { bytes = roomy; return e; }
-        (void)hipGetLastError();
-        e = hipMalloc(&p, n);
-        if (e != hipSuccess) {                          // the table buffers kept for future sketches are worth less than this
-            (void)hipGetLastError();
-            kv_table_cache_release();
-            kv_unique_scratch_release();                // (skips the arena of a kv_unique_new that is itself the caller)
-            e = hipMalloc(&p, n);
-        }
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-};
-
-// device buffers of the gzip inflater (kv_gunzip.hip); gigabytes for a big file, so the FASTQ reader pools them with its own
-struct KvGunzipArenas {
-    KvArena comp, syms, tails, meta, window, small, crc;
-    void release()
-    {
-        for (KvArena *a : {&comp, &syms, &tails, &meta, &window, &small, &crc})
-            if (a->p) { (void)hipFree(a->p); a->p = nullptr; a->bytes = 0; }
-    }
-};
-
 bool kv_bin_two_bit(const kv_sketch *s, const kv_reads *reads);      // stage A can hash this batch from its 2-bit form (k_bin_hash_2bit)
-int kv_device_cus();
-static inline uint64_t kv_round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
 // Geometry + scratch for a count of at most `n_items_max` k-mers into `s` on the calling thread's stream.
 // work_units / threads: the stage-A front end's units of work and workgroup size (0 threads: pick by geometry);

@@ -27,7 +27,6 @@
 // if even that overflows, the launcher reports it and kv_consume falls back to k_consume.
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <type_traits>
 
 #include "kv_binned.h"
@@ -827,19 +826,11 @@ __global__ void k_bin_spill(const SketchDev *__restrict__ sk, BinGeom g)
 }
 
 // one grow-only arena per stream, so host threads counting different samples do not share buffers
-std::map<hipStream_t, KvArena> g_scratch;
-std::mutex g_scratch_mu;
-
-KvArena &scratch_for(hipStream_t st)
-{
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    return g_scratch[kv_stream_key(st)];
-}
+KvPerStream<KvArena> g_scratch;
 }
 void kv_bin_scratch_release()
 {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    for (auto &kv : g_scratch) kv.second.release();
+    g_scratch.for_each([](KvArena &a) { a.release(); });
 }
 namespace {
 
@@ -902,7 +893,7 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
                 uint32_t nwgA_fixed, bool weighted, BinPlan *plan)
 {
     hipStream_t st = kv_stream();
-    KvArena &scratch = scratch_for(st);
+    KvArena &scratch = g_scratch.get(st);
     BinGeom &g = plan->g;
     memset(&g, 0, sizeof(g));
     plan->weighted = weighted;

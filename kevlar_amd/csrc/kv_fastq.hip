@@ -30,7 +30,6 @@
 #include <thread>
 #include <vector>
 
-#include "kv_binned.h"
 #include "kv_device.h"
 #include "kv_internal.h"
 
@@ -292,8 +291,7 @@ struct FastqBuffers {
     KvStager stage;
     void release()
     {
-        for (KvArena *a : {&text[0], &text[1], &comp, &lines, &recs, &scratch, &fetch})
-            if (a->p) { (void)hipFree(a->p); a->p = nullptr; a->bytes = 0; }
+        for (KvArena *a : {&text[0], &text[1], &comp, &lines, &recs, &scratch, &fetch}) a->release();
         gz.release();
         stage.release();
     }

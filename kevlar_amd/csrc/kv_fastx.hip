@@ -17,7 +17,6 @@
 
 #include <algorithm>
 
-#include "kv_binned.h"          // KvArena, KvGunzipArenas
 #include "kv_internal.h"
 
 // ---------------------------------------------------------------------------------------
@@ -78,11 +77,9 @@ struct DevTextSource {
     uint64_t delivered = 0;        // bytes of text handed to the parser so far
     ~DevTextSource()
     {
-        for (KvArena *a : {&comp, &scratch})
-            if (a->p) (void)hipFree(a->p);
+        for (KvArena *a : {&text, &comp, &scratch}) a->release();
         if (gz) kv_gunzip_close(gz);
         arenas.release();
-        if (text.p) (void)hipFree(text.p);
         if (image) munmap((void *)image, image_size);
         if (fd >= 0) close(fd);
     }

@@ -10,7 +10,6 @@
 // (c) count distinct (k-mer, node) pairs, (d) union every node of a retained k-mer with that
 // k-mer's representative node (lock-free hooking, larger root under smaller), (e) flatten.
 #include <algorithm>
-#include <map>
 #include <mutex>
 
 #include "kv_binned.h"
@@ -276,13 +275,6 @@ __global__ __launch_bounds__(KV_TILE_THREADS) void k_abund_hist(ReadsDev rd, con
         if (lhist[i]) atomicAdd(&p.hist[i], (unsigned long long)lhist[i]);
 }
 
-struct DevBuf {  // frees on scope exit
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return kv_hip_malloc(&p, n ? n : 4); }
-    template <typename T> T *as() { return (T *)p; }
-};
-
 inline unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096)); }
 inline uint64_t pow2_at_least(uint64_t n) { uint64_t c = 1024; while (c < n) c <<= 1; return c; }
 
@@ -306,7 +298,7 @@ extern "C" int kv_readgraph_components(const kv_reads *reads, int ksize, const u
     for (uint64_t r = 0; r < reads->n_reads; ++r)
         KV_REQUIRE(node_of_read[r] < n_nodes, KV_ERR_ARG, "node id %u out of range", node_of_read[r]);
     hipStream_t st = kv_stream();
-    DevBuf d_ar, d_ao, d_nr, d_keys, d_owner, d_grp, d_pairset, d_cnt, d_head, d_next, d_pairs, d_np, d_parent, d_labels;
+    KvDevBuf d_ar, d_ao, d_nr, d_keys, d_owner, d_grp, d_pairset, d_cnt, d_head, d_next, d_pairs, d_np, d_parent, d_labels;
     const uint64_t cap = pow2_at_least(2 * n_ann + 16);
     hipError_t e = d_ar.alloc(n_ann * 4);
     if (e == hipSuccess) e = d_ao.alloc(n_ann * 4);
@@ -371,7 +363,7 @@ extern "C" int kv_readgraph_components(const kv_reads *reads, int ksize, const u
             KV_REQUIRE(bound < (1ull << 31), KV_ERR_CAPACITY, "edge count bound %llu too large to enumerate",
                        (unsigned long long)bound);
             const uint64_t ecap = pow2_at_least(2 * bound + 16);
-            DevBuf d_edges;
+            KvDevBuf d_edges;
             KV_HIP(d_edges.alloc(ecap * 8));
             KV_HIP(hipMemsetAsync(d_edges.p, 0xFF, ecap * 8, st));
             KV_HIP(hipMemsetAsync(d_np.p, 0, 16, st));
@@ -411,7 +403,7 @@ extern "C" int kv_unique_exact(kv_sketch *s, const kv_reads *const *batches, int
     FirstTouchParams p;
     memset(&p, 0, sizeof(p));
     p.f = make_consume_filter(k, s->h.hashfam, nbands, band, mask != nullptr, threshold, consume_masked);
-    std::vector<DevBuf> first(s->h.ntables);
+    std::vector<KvDevBuf> first(s->h.ntables);
     for (int t = 0; t < s->h.ntables; ++t) {
         hipError_t e = first[t].alloc(s->h.size[t] * 4);
         KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "first-touch scratch (%llu bytes) allocation failed: %s",
@@ -420,7 +412,7 @@ extern "C" int kv_unique_exact(kv_sketch *s, const kv_reads *const *batches, int
         p.first[t] = first[t].as<uint32_t>();
     }
     const uint64_t bm_words = (total + 31) / 32;
-    DevBuf d_bm, d_out;
+    KvDevBuf d_bm, d_out;
     KV_HIP(d_bm.alloc(bm_words * 4));
     KV_HIP(d_out.alloc(8));
     KV_HIP(hipMemsetAsync(d_bm.p, 0, bm_words * 4, st));
@@ -431,7 +423,7 @@ extern "C" int kv_unique_exact(kv_sketch *s, const kv_reads *const *batches, int
         std::vector<uint64_t> kpre(r->n_reads + 1, 0);
         for (uint64_t i = 0; i < r->n_reads; ++i)
             kpre[i + 1] = kpre[i] + (r->h_len[i] >= (uint32_t)k ? r->h_len[i] - (uint32_t)k + 1 : 0);
-        DevBuf d_kpre;
+        KvDevBuf d_kpre;
         KV_HIP(d_kpre.alloc(kpre.size() * 8));
         KV_HIP(hipMemcpyAsync(d_kpre.p, kpre.data(), kpre.size() * 8, hipMemcpyHostToDevice, st));
         p.ordinal_base = base;
@@ -469,19 +461,17 @@ struct UniqueArena {
     KvArena a;
     std::mutex busy;            // held for the whole of a kv_unique_new call on this stream
 };
-std::map<hipStream_t, UniqueArena> g_unique_arena;
-std::mutex g_unique_arena_mu;
+KvPerStream<UniqueArena> g_unique_arena;
 thread_local const UniqueArena *tl_unique_held = nullptr;      // the arena the calling thread's own kv_unique_new holds (never try_lock a mutex one owns)
 }
 void kv_unique_scratch_release()
 {
-    std::lock_guard<std::mutex> alk(g_unique_arena_mu);
-    for (auto &kv : g_unique_arena) {
-        if (&kv.second == tl_unique_held) continue;     // the caller's own call is using it
-        if (!kv.second.busy.try_lock()) continue;       // in use by another thread's running call: not ours to free
-        kv.second.a.release();
-        kv.second.busy.unlock();
-    }
+    g_unique_arena.for_each([](UniqueArena &ua) {
+        if (&ua == tl_unique_held) return;      // the caller's own call is using it
+        if (!ua.busy.try_lock()) return;        // in use by another thread's running call: not ours to free
+        ua.a.release();
+        ua.busy.unlock();
+    });
 }
 extern "C" int kv_unique_release(void)
 {
@@ -507,11 +497,7 @@ extern "C" int kv_unique_new(kv_sketch *s, const kv_reads *batch, int nbands, in
     FirstTouchParams p;
     memset(&p, 0, sizeof(p));
     p.f = make_consume_filter(k, s->h.hashfam, nbands, band, mask != nullptr, threshold, consume_masked);
-    UniqueArena *ua;
-    {
-        std::lock_guard<std::mutex> alk(g_unique_arena_mu);
-        ua = &g_unique_arena[kv_stream_key(st)];
-    }
+    UniqueArena *ua = &g_unique_arena.get(st);
     std::lock_guard<std::mutex> busy(ua->busy);
     struct Held { Held(const UniqueArena *u) { tl_unique_held = u; } ~Held() { tl_unique_held = nullptr; } } held(ua);
     KvArena *arena = &ua->a;
@@ -535,7 +521,7 @@ extern "C" int kv_unique_new(kv_sketch *s, const kv_reads *batch, int nbands, in
     std::vector<uint64_t> kpre(batch->n_reads + 1, 0);
     for (uint64_t i = 0; i < batch->n_reads; ++i)
         kpre[i + 1] = kpre[i] + (batch->h_len[i] >= (uint32_t)k ? batch->h_len[i] - (uint32_t)k + 1 : 0);
-    DevBuf d_kpre;
+    KvDevBuf d_kpre;
     KV_HIP(d_kpre.alloc(kpre.size() * 8));
     KV_HIP(hipMemcpyAsync(d_kpre.p, kpre.data(), kpre.size() * 8, hipMemcpyHostToDevice, st));
     p.ordinal_base = 0;
@@ -589,7 +575,7 @@ extern "C" int kv_abundance_distribution(kv_sketch *counts, kv_sketch *tracking,
         FirstTouchParams p;
         memset(&p, 0, sizeof(p));
         p.f = make_consume_filter(k, tracking->h.hashfam, 0, 0, false, 0, 0);
-        std::vector<DevBuf> first(tracking->h.ntables);
+        std::vector<KvDevBuf> first(tracking->h.ntables);
         for (int t = 0; t < tracking->h.ntables; ++t) {
             hipError_t e = first[t].alloc(tracking->h.size[t] * 4);
             KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "first-touch scratch (%llu bytes) allocation failed: %s",
@@ -598,12 +584,12 @@ extern "C" int kv_abundance_distribution(kv_sketch *counts, kv_sketch *tracking,
             p.first[t] = first[t].as<uint32_t>();
         }
         const uint64_t bm_words = (total + 31) / 32;
-        DevBuf d_bm, d_hist;
+        KvDevBuf d_bm, d_hist;
         KV_HIP(d_bm.alloc(bm_words * 4));
         KV_HIP(d_hist.alloc(256 * 8));
         KV_HIP(hipMemsetAsync(d_bm.p, 0, bm_words * 4, st));
         KV_HIP(hipMemsetAsync(d_hist.p, 0, 256 * 8, st));
-        std::vector<DevBuf> d_kpre(n_batches);
+        std::vector<KvDevBuf> d_kpre(n_batches);
         std::vector<uint64_t> bases(n_batches, 0);
         uint64_t base = 0;
         for (int b = 0; b < n_batches; ++b) {

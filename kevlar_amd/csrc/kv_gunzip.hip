@@ -40,7 +40,6 @@
 
 #include <zlib.h>
 
-#include "kv_binned.h"
 #include "kv_internal.h"
 #include "kv_inflate_device.h"
 

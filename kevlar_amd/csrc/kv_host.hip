@@ -795,134 +795,6 @@ __global__ void k_pack_reads(const char *__restrict__ ascii, const uint64_t *__r
     }
 }
 
-extern "C" int kv_reads_create(const char *bases, const uint64_t *offs, uint64_t n_reads, kv_reads **out)
-{
-    KV_REQUIRE(out && offs && (bases || n_reads == 0), KV_ERR_ARG, "kv_reads_create: null argument");
-    KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
-    kv_reads *r = new kv_reads();
-    r->n_reads = n_reads;
-    r->n_bases = n_reads ? offs[n_reads] - offs[0] : 0;
-    r->d_words = nullptr; r->d_woff = nullptr; r->d_len = nullptr; r->d_flags = nullptr; r->d_tile = nullptr;
-    r->h_len.resize(n_reads);
-    std::vector<uint64_t> woff(n_reads + 1);
-    std::vector<TileDesc> tiles;
-    uint64_t nw = 0;
-    uint32_t max_len = 0;
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        uint64_t len = offs[i + 1] - offs[i];
-        if (len > KV_MAX_READ_LEN) {
-            kv_set_error("read %llu has %llu bases; this build handles reads up to %d bases",
-                         (unsigned long long)i, (unsigned long long)len, (int)KV_MAX_READ_LEN);
-            delete r;
-            return KV_ERR_ARG;
-        }
-        r->h_len[i] = (uint32_t)len;
-        if (len > max_len) max_len = (uint32_t)len;
-        woff[i] = nw;
-        nw += (len + 15) / 16;
-    }
-    woff[n_reads] = nw;
-    r->n_words = nw;
-    r->max_len = max_len;
-    // tiles: consecutive reads whose staged ASCII (both strands, padded) fits the LDS budget; a sequence
-    // too long for one tile (contigs, the chromosomes of a reference genome counted into a mask) becomes a
-    // series of segment tiles of KV_SEG_BASES k-mer starts each
-    {
-        const uint32_t budget = KV_TILE_LDS_BYTES - 64;
-        uint32_t used = 0, count = 0, first = 0;
-        uint32_t run_bases = 0, most_bases = 0;
-        auto close_run = [&](uint32_t next_first) {
-            if (count) tiles.push_back(TileDesc{first, count, 0u, 0u});
-            most_bases = std::max(most_bases, run_bases);
-            used = 0; count = 0; first = next_first; run_bases = 0;
-        };
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            const uint32_t need = 2 * ((r->h_len[i] + KV_READ_PAD + 3) & ~3u);
-            if (need > budget) {
-                close_run((uint32_t)i + 1);
-                for (uint32_t start = 0; start < r->h_len[i]; start += KV_SEG_BASES)
-                    tiles.push_back(TileDesc{(uint32_t)i, 1u, start, 1u});
-                most_bases = std::max<uint32_t>(most_bases, std::min<uint32_t>(r->h_len[i], KV_SEG_BASES + KV_MAX_K));
-                continue;
-            }
-            if (count > 0 && (count == KV_TILE_MAX_READS || used + need > budget)) close_run((uint32_t)i);
-            if (count == 0) first = (uint32_t)i;
-            used += need; count += 1; run_bases += r->h_len[i];
-        }
-        close_run((uint32_t)n_reads);
-        r->tile_max_bases = most_bases;
-        r->n_tiles = (uint32_t)tiles.size();
-        // reads of one length (packed on the host: uniform_reads above takes only text on the device) lie exactly as uniform_reads
-        // lays them out -- read i at word i * wpr, the same reads per tile: say so, the lane-per-read cut asks for it
-        {
-            bool same = n_reads > 0 && r->h_len[0] > 0 && 2 * ((r->h_len[0] + KV_READ_PAD + 3) & ~3u) <= budget;
-            for (uint64_t i = 1; same && i < n_reads; ++i) same = r->h_len[i] == r->h_len[0];
-            if (same) {
-                r->uni_len = r->h_len[0];
-                r->uni_per_tile = std::min<uint32_t>(KV_TILE_MAX_READS, budget / (2 * ((r->h_len[0] + KV_READ_PAD + 3) & ~3u)));
-            }
-        }
-        r->tile_lds_bytes = KV_TILE_LDS_BYTES + 256;   // + rolling-window over-read
-        if (tiles.empty()) tiles.push_back(TileDesc{0u, 0u, 0u, 0u});
-    }
-    const uint64_t flag_bytes = ((n_reads + 3) & ~3ull) + 4;
-    char *d_ascii = nullptr;
-    uint64_t *d_offs = nullptr;
-    hipStream_t st = kv_stream();
-    hipError_t e = kv_hip_malloc((void **)&r->d_words, (nw + 4) * 4);   // + slack: k-mer extraction reads up to two words ahead
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_woff, woff.size() * 8);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_len, (n_reads ? n_reads : 1) * 4);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_flags, flag_bytes);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_tile, tiles.size() * sizeof(TileDesc));
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&d_ascii, r->n_bases ? r->n_bases : 1);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&d_offs, woff.size() * 8);
-    if (e == hipSuccess && r->n_bases) e = hipMemcpyAsync(d_ascii, bases + offs[0], r->n_bases, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_offs, offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_woff, woff.data(), woff.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_reads) e = hipMemcpyAsync(r->d_len, r->h_len.data(), n_reads * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_flags, 0, flag_bytes, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_tile, tiles.data(), tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nw) {
-        KvProfScope prof("k_pack_reads");
-        const unsigned grid = (unsigned)std::min<uint64_t>((nw + 255) / 256, 65536);
-        hipLaunchKernelGGL(k_pack_reads, dim3(grid), dim3(256), 0, st, (const char *)d_ascii, (const uint64_t *)d_offs,
-                           (const uint64_t *)r->d_woff, n_reads, nw, r->d_words, (uint32_t *)r->d_flags);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);      // the host vectors and the caller's blob are free after this
-    if (d_ascii) (void)hipFree(d_ascii);
-    if (d_offs) (void)hipFree(d_offs);
-    if (e != hipSuccess) {
-        kv_last_hip_code = (int)e;
-        kv_set_error("read batch upload failed: %s", hipGetErrorString(e));
-        kv_reads_destroy(r);
-        return KV_ERR_HIP;
-    }
-    *out = r;
-    return KV_OK;
-}
-
-// reads that are already 2-bit packed on the host, any lengths: word offsets, tile table and uploads as kv_reads_create
-// builds them, minus the ASCII upload and the packing kernel (the packed-read cache of kv_fastx.hip comes through here)
-namespace {
-struct TextSource { const uint8_t *d_text; const uint64_t *d_seq_start; const uint32_t *d_seq_len; };
-int reads_from_packed(const uint32_t *words, const TextSource *text, const uint32_t *lens, const uint8_t *flags, uint64_t n_reads, kv_reads **out);
-}
-
-int kv_reads_from_packed_var(const uint32_t *words, const uint32_t *lens, const uint8_t *flags, uint64_t n_reads, kv_reads **out)
-{
-    KV_REQUIRE(out && ((words && lens) || n_reads == 0), KV_ERR_ARG, "kv_reads_from_packed_var: null argument");
-    return reads_from_packed(words, nullptr, lens, flags, n_reads, out);
-}
-
-int kv_reads_from_device_text(const uint8_t *d_text, const uint64_t *d_seq_start, const uint32_t *d_seq_len, const uint32_t *lens,
-                              uint64_t n_reads, kv_reads **out)
-{
-    KV_REQUIRE(out && ((d_text && d_seq_start && d_seq_len && lens) || n_reads == 0), KV_ERR_ARG, "kv_reads_from_device_text: null argument");
-    const TextSource src = {d_text, d_seq_start, d_seq_len};
-    return reads_from_packed(nullptr, &src, lens, nullptr, n_reads, out);
-}
-
 namespace {
 // word offsets and tile table of a batch whose reads all have the same length: nothing per read crosses PCIe
 __global__ void k_uniform_layout(uint64_t *woff, TileDesc *tiles, uint64_t n_reads, uint64_t wpr, uint32_t per_tile, uint32_t n_tiles)
@@ -935,121 +807,71 @@ __global__ void k_uniform_layout(uint64_t *woff, TileDesc *tiles, uint64_t n_rea
     }
 }
 
-// the same layout reads_from_packed builds read by read, in closed form; false if the batch is not uniform (or its reads
-// need segment tiles)
-bool uniform_reads(kv_reads *r, const TextSource *text, const uint32_t *lens, uint64_t n_reads, int *rc)
-{
-    if (!text || n_reads == 0) return false;
-    const uint32_t L = lens[0];
-    if (L == 0) return false;
-    for (uint64_t i = 1; i < n_reads; ++i)
-        if (lens[i] != L) return false;
-    const uint32_t budget = KV_TILE_LDS_BYTES - 64, need = 2 * ((L + KV_READ_PAD + 3) & ~3u);
-    if (need > budget) return false;
-    const uint32_t per_tile = std::min<uint32_t>(KV_TILE_MAX_READS, budget / need);
-    const uint64_t wpr = ((uint64_t)L + 15) / 16, nw = n_reads * wpr;
-    r->n_words = nw; r->n_bases = n_reads * (uint64_t)L; r->max_len = L;
-    r->tile_max_bases = (uint32_t)std::min<uint64_t>(per_tile, n_reads) * L;
-    r->n_tiles = (uint32_t)((n_reads + per_tile - 1) / per_tile);
-    r->uni_len = L; r->uni_per_tile = per_tile;
-    r->tile_lds_bytes = KV_TILE_LDS_BYTES + 256;
-    const uint64_t flag_bytes = ((n_reads + 3) & ~3ull) + 4;
-    hipStream_t st = kv_stream();
-    hipError_t e = kv_hip_malloc((void **)&r->d_words, (nw + 4) * 4);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_woff, (n_reads + 1) * 8);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_len, n_reads * 4);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_flags, flag_bytes);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_tile, (size_t)r->n_tiles * sizeof(TileDesc));
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_words + nw, 0, 16, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_len, text->d_seq_len, n_reads * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_flags, 0, flag_bytes, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_uniform_layout, dim3(1024), dim3(256), 0, st, r->d_woff, r->d_tile, n_reads, wpr, per_tile, r->n_tiles);
-        kv_fastq_pack_launch(text->d_text, text->d_seq_start, text->d_seq_len, r->d_woff, n_reads, nw, r->d_words, (uint32_t *)r->d_flags, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        kv_last_hip_code = (int)e;
-        kv_set_error("read batch upload failed: %s", hipGetErrorString(e));
-        *rc = KV_ERR_HIP;
-    }
-    return true;
-}
+// where the words of a batch come from: one of ascii / words / text / fill
+struct TextSource { const uint8_t *d_text; const uint64_t *d_seq_start; const uint32_t *d_seq_len; };
+struct ReadsSource {
+    const char *ascii = nullptr;         // a blob on the host, read i at [offs[i], offs[i + 1]): packed and flagged by k_pack_reads
+    const uint64_t *offs = nullptr;
+    const uint32_t *words = nullptr;     // 2-bit words packed on the host ...
+    const uint8_t *flags = nullptr;      // ... and, if the caller has them, a flag byte per read
+    const TextSource *text = nullptr;    // text in HBM: packed and flagged by kv_fastq_pack_launch
+    const std::function<void(uint32_t *, hipStream_t)> *fill = nullptr;   // writes the words on the device
+};
 
-int reads_from_packed(const uint32_t *words, const TextSource *text, const uint32_t *lens, const uint8_t *flags, uint64_t n_reads, kv_reads **out)
+// The one constructor: the five device arrays of a batch laid out as `plan` says (kv_reads_layout.h) and filled from `src`.
+// A plan in closed form (a uniform batch planned without tables) has its word offsets, lengths and tile table written on the device.
+int build_reads(std::vector<uint32_t> &&lens, const KvReadsPlan &plan, const ReadsSource &src, kv_reads **out)
 {
-    KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
     kv_reads *r = new kv_reads();
-    r->n_reads = n_reads;
+    const uint64_t n_reads = lens.size(), nw = plan.n_words;
+    r->n_reads = n_reads; r->n_bases = plan.n_bases; r->n_words = nw;
     r->d_words = nullptr; r->d_woff = nullptr; r->d_len = nullptr; r->d_flags = nullptr; r->d_tile = nullptr;
-    r->h_len.assign(lens, lens + n_reads);
-    {
-        int rc = KV_OK;
-        if (uniform_reads(r, text, lens, n_reads, &rc)) {
-            if (rc != KV_OK) { kv_reads_destroy(r); return rc; }
-            *out = r;
-            return KV_OK;
-        }
-    }
-    std::vector<uint64_t> woff(n_reads + 1);
-    std::vector<TileDesc> tiles;
-    uint64_t nw = 0, nb = 0;
-    uint32_t max_len = 0;
-    for (uint64_t i = 0; i < n_reads; ++i) {
-        woff[i] = nw;
-        nw += ((uint64_t)lens[i] + 15) / 16;
-        nb += lens[i];
-        if (lens[i] > max_len) max_len = lens[i];
-    }
-    woff[n_reads] = nw;
-    r->n_words = nw; r->n_bases = nb; r->max_len = max_len;
-    {
-        const uint32_t budget = KV_TILE_LDS_BYTES - 64;
-        uint32_t used = 0, count = 0, first = 0, run_bases = 0, most_bases = 0;
-        auto close_run = [&](uint32_t next_first) {
-            if (count) tiles.push_back(TileDesc{first, count, 0u, 0u});
-            most_bases = std::max(most_bases, run_bases);
-            used = 0; count = 0; first = next_first; run_bases = 0;
-        };
-        for (uint64_t i = 0; i < n_reads; ++i) {
-            const uint32_t need = 2 * ((r->h_len[i] + KV_READ_PAD + 3) & ~3u);
-            if (need > budget) {
-                close_run((uint32_t)i + 1);
-                for (uint32_t start = 0; start < r->h_len[i]; start += KV_SEG_BASES)
-                    tiles.push_back(TileDesc{(uint32_t)i, 1u, start, 1u});
-                most_bases = std::max<uint32_t>(most_bases, std::min<uint32_t>(r->h_len[i], KV_SEG_BASES + KV_MAX_K));
-                continue;
-            }
-            if (count > 0 && (count == KV_TILE_MAX_READS || used + need > budget)) close_run((uint32_t)i);
-            if (count == 0) first = (uint32_t)i;
-            used += need; count += 1; run_bases += r->h_len[i];
-        }
-        close_run((uint32_t)n_reads);
-        r->tile_max_bases = most_bases;
-        r->n_tiles = (uint32_t)tiles.size();
-        r->tile_lds_bytes = KV_TILE_LDS_BYTES + 256;
-        if (tiles.empty()) tiles.push_back(TileDesc{0u, 0u, 0u, 0u});
-    }
-    const uint64_t flag_bytes = ((n_reads + 3) & ~3ull) + 4;
+    r->n_tiles = plan.n_tiles; r->max_len = plan.max_len; r->tile_max_bases = plan.tile_max_bases;
+    r->uni_len = plan.uni_len; r->uni_per_tile = plan.uni_per_tile;
+    r->tile_lds_bytes = KV_TILE_LDS_BYTES + 256;   // + rolling-window over-read
+    r->h_len = std::move(lens);
+    const uint64_t flag_bytes = ((n_reads + 3) & ~3ull) + 4;          // the pack kernels address the flags as uint32_t
+    const size_t n_desc = std::max<uint32_t>(plan.n_tiles, 1u);      // (a batch without tiles keeps one zero descriptor)
+    const bool closed_form = plan.closed_form;
+    KvDevBuf d_ascii, d_offs;
     hipStream_t st = kv_stream();
-    hipError_t e = kv_hip_malloc((void **)&r->d_words, (nw + 4) * 4);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_woff, woff.size() * 8);
+    hipError_t e = kv_hip_malloc((void **)&r->d_words, (nw + 4) * 4);   // + slack: k-mer extraction reads up to two words ahead
+    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_woff, (n_reads + 1) * 8);
     if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_len, (n_reads ? n_reads : 1) * 4);
     if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_flags, flag_bytes);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_tile, tiles.size() * sizeof(TileDesc));
-    if (e == hipSuccess && nw && words) e = hipMemcpyAsync(r->d_words, words, nw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_tile, n_desc * sizeof(TileDesc));
     if (e == hipSuccess) e = hipMemsetAsync(r->d_words + nw, 0, 16, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_woff, woff.data(), woff.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_reads) e = hipMemcpyAsync(r->d_len, r->h_len.data(), n_reads * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(r->d_flags, 0, flag_bytes, st);
-    if (e == hipSuccess && n_reads && flags) e = hipMemcpyAsync(r->d_flags, flags, n_reads, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_tile, tiles.data(), tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nw && text) {
-        kv_fastq_pack_launch(text->d_text, text->d_seq_start, text->d_seq_len, r->d_woff, n_reads, nw, r->d_words, (uint32_t *)r->d_flags, st);
+    if (e == hipSuccess && n_reads && src.flags) e = hipMemcpyAsync(r->d_flags, src.flags, n_reads, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && closed_form) e = hipMemsetD32Async((hipDeviceptr_t)r->d_len, (int)plan.uni_len, n_reads, st);
+    if (e == hipSuccess && closed_form) {
+        hipLaunchKernelGGL(k_uniform_layout, dim3(1024), dim3(256), 0, st, r->d_woff, r->d_tile, n_reads, ((uint64_t)plan.uni_len + 15) / 16,
+                           plan.uni_per_tile, plan.n_tiles);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && !closed_form) e = hipMemcpyAsync(r->d_woff, plan.woff.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !closed_form && n_reads) e = hipMemcpyAsync(r->d_len, r->h_len.data(), n_reads * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !closed_form) e = hipMemcpyAsync(r->d_tile, plan.tiles.data(), n_desc * sizeof(TileDesc), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nw && src.words) e = hipMemcpyAsync(r->d_words, src.words, nw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nw && src.fill) { (*src.fill)(r->d_words, st); e = hipGetLastError(); }
+    if (e == hipSuccess && nw && src.text) {
+        kv_fastq_pack_launch(src.text->d_text, src.text->d_seq_start, src.text->d_seq_len, r->d_woff, n_reads, nw, r->d_words, (uint32_t *)r->d_flags, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && nw && src.ascii) {
+        e = d_ascii.alloc(r->n_bases);
+        if (e == hipSuccess) e = d_offs.alloc((n_reads + 1) * 8);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ascii.p, src.ascii + src.offs[0], r->n_bases, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_offs.p, src.offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            KvProfScope prof("k_pack_reads");
+            const unsigned grid = (unsigned)std::min<uint64_t>((nw + 255) / 256, 65536);
+            hipLaunchKernelGGL(k_pack_reads, dim3(grid), dim3(256), 0, st, d_ascii.as<const char>(), d_offs.as<const uint64_t>(),
+                               (const uint64_t *)r->d_woff, n_reads, nw, r->d_words, (uint32_t *)r->d_flags);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // the plan, the caller's buffers and the staged ASCII are free after this
     if (e != hipSuccess) {
         kv_last_hip_code = (int)e;
         kv_set_error("read batch upload failed: %s", hipGetErrorString(e));
@@ -1061,55 +883,61 @@ int reads_from_packed(const uint32_t *words, const TextSource *text, const uint3
 }
 }  // namespace
 
-// equal-length reads from packed words on the host, or (words == nullptr) written on the device by `fill(d_words, stream)`
+extern "C" int kv_reads_create(const char *bases, const uint64_t *offs, uint64_t n_reads, kv_reads **out)
+{
+    KV_REQUIRE(out && offs && (bases || n_reads == 0), KV_ERR_ARG, "kv_reads_create: null argument");
+    KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
+    std::vector<uint32_t> lens(n_reads);
+    for (uint64_t i = 0; i < n_reads; ++i) {
+        const uint64_t len = offs[i + 1] - offs[i];
+        KV_REQUIRE(len <= KV_MAX_READ_LEN, KV_ERR_ARG, "read %llu has %llu bases; this build handles reads up to %d bases",
+                   (unsigned long long)i, (unsigned long long)len, (int)KV_MAX_READ_LEN);
+        lens[i] = (uint32_t)len;
+    }
+    const KvReadsPlan plan = kv_reads_plan(lens.data(), n_reads, true);
+    ReadsSource src;
+    src.ascii = bases; src.offs = offs;
+    return build_reads(std::move(lens), plan, src, out);
+}
+
+// reads that are already 2-bit packed on the host, any lengths (the packed-read cache of kv_fastx.hip comes through here)
+int kv_reads_from_packed_var(const uint32_t *words, const uint32_t *lens, const uint8_t *flags, uint64_t n_reads, kv_reads **out)
+{
+    KV_REQUIRE(out && ((words && lens) || n_reads == 0), KV_ERR_ARG, "kv_reads_from_packed_var: null argument");
+    KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
+    KvReadsPlan plan = kv_reads_plan(lens, n_reads, true);
+    plan.uni_len = plan.uni_per_tile = 0;      // this path has never announced a uniform batch: doing so changes the emit kernel a cached batch takes
+    ReadsSource src;
+    src.words = words; src.flags = flags;
+    return build_reads(std::vector<uint32_t>(lens, lens + n_reads), plan, src, out);
+}
+
+int kv_reads_from_device_text(const uint8_t *d_text, const uint64_t *d_seq_start, const uint32_t *d_seq_len, const uint32_t *lens,
+                              uint64_t n_reads, kv_reads **out)
+{
+    KV_REQUIRE(out && ((d_text && d_seq_start && d_seq_len && lens) || n_reads == 0), KV_ERR_ARG, "kv_reads_from_device_text: null argument");
+    KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
+    const TextSource text = {d_text, d_seq_start, d_seq_len};
+    ReadsSource src;
+    src.text = &text;
+    return build_reads(std::vector<uint32_t>(lens, lens + n_reads), kv_reads_plan(lens, n_reads, false), src, out);
+}
+
+// equal-length reads from packed words on the host, or (words == nullptr) written on the device by `fill(d_words, stream)`: only
+// the words cross PCIe
 static int reads_packed_uniform(const uint32_t *words, const std::function<void(uint32_t *, hipStream_t)> *fill, uint64_t n_reads,
                                 uint32_t read_len, kv_reads **out)
 {
     KV_REQUIRE(out && (words || fill || n_reads == 0), KV_ERR_ARG, "kv_reads_create_packed: null argument");
     KV_REQUIRE(n_reads < 0xFFFFFFF0ull, KV_ERR_ARG, "too many reads in one batch");
     KV_REQUIRE(read_len >= 1 && read_len <= KV_MAX_READ_LEN, KV_ERR_ARG, "read length %u out of range", read_len);
-    kv_reads *r = new kv_reads();
-    const uint64_t wpr = (read_len + 15) / 16;
-    r->n_reads = n_reads; r->n_bases = n_reads * read_len; r->n_words = n_reads * wpr; r->max_len = read_len;
-    r->d_words = nullptr; r->d_woff = nullptr; r->d_len = nullptr; r->d_flags = nullptr; r->d_tile = nullptr;
-    r->h_len.assign(n_reads, read_len);
-    const uint32_t need = 2 * ((read_len + KV_READ_PAD + 3) & ~3u);
-    uint32_t per_tile = (KV_TILE_LDS_BYTES - 64) / need;
-    if (per_tile > KV_TILE_MAX_READS) per_tile = KV_TILE_MAX_READS;
-    if (per_tile < 1) per_tile = 1;
-    KV_REQUIRE(need <= KV_TILE_LDS_BYTES - 64, KV_ERR_ARG, "kv_reads_create_packed: read length %u needs kv_reads_create", read_len);
-    r->n_tiles = (uint32_t)((n_reads + per_tile - 1) / per_tile);
-    r->tile_max_bases = (uint32_t)std::min<uint64_t>(per_tile, n_reads) * read_len;
-    r->uni_len = read_len; r->uni_per_tile = per_tile;
-    r->tile_lds_bytes = KV_TILE_LDS_BYTES + 256;
-    // only the packed words cross PCIe: word offsets, lengths and the tile table of equal-length reads are written on
-    // the device in closed form
-    hipStream_t st = kv_stream();
-    const uint32_t tiles_alloc = std::max<uint32_t>(r->n_tiles, 1u);
-    hipError_t e = kv_hip_malloc((void **)&r->d_words, (r->n_words + 4) * 4);   // + slack: k-mer extraction reads up to two words ahead
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_woff, (n_reads + 1) * 8);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_len, (n_reads ? n_reads : 1) * 4);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_flags, n_reads ? n_reads : 1);
-    if (e == hipSuccess) e = kv_hip_malloc((void **)&r->d_tile, (size_t)tiles_alloc * sizeof(TileDesc));
-    if (e == hipSuccess && r->n_words && words) e = hipMemcpyAsync(r->d_words, words, r->n_words * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && r->n_words && !words) { (*fill)(r->d_words, st); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_words + r->n_words, 0, 16, st);
-    if (e == hipSuccess && n_reads) e = hipMemsetD32Async((hipDeviceptr_t)r->d_len, (int)read_len, n_reads, st);
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_flags, 0, n_reads ? n_reads : 1, st);
-    if (e == hipSuccess) e = hipMemsetAsync(r->d_tile, 0, (size_t)tiles_alloc * sizeof(TileDesc), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_uniform_layout, dim3(1024), dim3(256), 0, st, r->d_woff, r->d_tile, n_reads, wpr, per_tile, r->n_tiles);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        kv_last_hip_code = (int)e;
-        kv_set_error("read batch upload failed: %s", hipGetErrorString(e));
-        kv_reads_destroy(r);
-        return KV_ERR_HIP;
-    }
-    *out = r;
-    return KV_OK;
+    KV_REQUIRE(kv_reads_per_tile(read_len) > 0, KV_ERR_ARG, "kv_reads_create_packed: read length %u needs kv_reads_create", read_len);
+    std::vector<uint32_t> lens(n_reads, read_len);
+    KvReadsPlan plan = kv_reads_plan(lens.data(), n_reads, false);
+    if (n_reads == 0) { plan.max_len = plan.uni_len = read_len; plan.uni_per_tile = kv_reads_per_tile(read_len); }   // an empty batch keeps its announced length
+    ReadsSource src;
+    src.words = words; src.fill = words ? nullptr : fill;
+    return build_reads(std::move(lens), plan, src, out);
 }
 
 extern "C" int kv_reads_create_packed(const uint32_t *words, uint64_t n_reads, uint32_t read_len, kv_reads **out)

@@ -24,7 +24,6 @@
 #include <cstring>
 #include <vector>
 
-#include "kv_binned.h"
 #include "kv_internal.h"
 #include "kv_inflate_device.h"
 

@@ -15,6 +15,8 @@
 
 #include "../../include/kvsketch.h"
 #include "kv_fastmod.h"
+#include "kv_reads_layout.h"   // TileDesc, the tile geometry and the layout planner
+#include "kv_mem.h"            // KvDevBuf, KvArena, KvPerStream
 
 enum { ST_BYTE = 0, ST_NIBBLE = 1, ST_BIT = 2 };
 enum { HF_MURMUR = 0, HF_TWOBIT = 1 };
@@ -91,14 +93,6 @@ struct kv_sketch {
     bool scan_hint = false; // kv_sketch_scan_hint: batches counted into this sketch are scanned next (a case sample)
     bool scan_steady = false; // ... and the process does so sample after sample: the distinct list pays from the first batch on
     std::mutex mu;
-};
-
-// One unit of work of the hashing kernels: `count` whole reads starting at read `first`, or (seg != 0) the
-// segment of read `first` whose k-mers START in [seg_start, seg_start + KV_SEG_BASES): the kernel stages
-// KV_SEG_BASES + k - 1 bases, so every k-mer of a chromosome-length sequence belongs to exactly one tile
-// whatever k is (the tile table itself does not depend on k).
-struct TileDesc {
-    uint32_t first, count, seg_start, seg;
 };
 
 // Packed read batch.  Read r occupies words [woff[r], woff[r+1]) of `words`; base j sits in
@@ -270,13 +264,9 @@ struct NovelParams;
 int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8_t *d_abund, uint64_t cap, uint64_t *n_hits);
 int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32_t *d_cnt, uint64_t *d_out, uint64_t *records_per_dest);
 
-// tile geometry of the hashing kernels
+// tile geometry of the hashing kernels (the rest of it: kv_reads_layout.h)
 #define KV_TILE_THREADS 256
-#define KV_TILE_MAX_READS 64
-#define KV_TILE_LDS_BYTES 16384  // ASCII staging (forward + reverse complement) per tile: 64 reads of 100 bp
-#define KV_READ_PAD 24           // over-read slack after each staged strand
 #define KV_MAX_READ_LEN 0x7fffffff   // sequences longer than a tile are cut into segment tiles (reference genomes for masks)
-#define KV_SEG_BASES 7680        // k-mer starts per segment tile: 2 x (7680 + KV_MAX_K - 1 + pad) bytes of ASCII fit the tile budget
 
 // error plumbing -------------------------------------------------------------------------
 void kv_set_error(const char *fmt, ...);
@@ -334,6 +324,8 @@ hipError_t kv_hip_malloc(void **p, size_t bytes);
 template <typename T> static inline hipError_t kv_hip_malloc(T **p, size_t bytes) { return kv_hip_malloc((void **)p, bytes); }
 
 // host helpers shared between files
+int kv_device_cus();
+static inline uint64_t kv_round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 uint64_t kv_host_murmur_lo(const void *data, int len, uint32_t seed);
 uint64_t kv_host_hash(int hashfam, const char *kmer, int k, bool *ok);
 int kv_sketch_alloc(int kind, int ksize, int ntables, const uint64_t *sizes, kv_sketch **out);
@@ -347,7 +339,6 @@ struct KvBgzfMember {
     uint32_t crc;        // CRC-32 of them, as the member's trailer has it
     uint32_t pad;
 };
-struct KvArena;
 int kv_bgzf_index(const uint8_t *file, uint64_t size, std::vector<KvBgzfMember> *members, int *is_bgzf);
 // readable (and zeroed) bytes the caller keeps behind the compressed image it hands to kv_bgzf_inflate
 #define KV_INFLATE_SLACK 2048
@@ -361,7 +352,11 @@ uint32_t kv_crc32_join(uint32_t crc_a, uint32_t crc_b, uint32_t len_b);
 
 // ---- ordinary gzip on the device (kv_gunzip.hip): a segment of the stream per decode/emit pair ----
 struct KvGunzip;
-struct KvGunzipArenas;                                          // its device buffers (kv_binned.h has the definition)
+// its device buffers; gigabytes for a big file, so the FASTQ reader pools them with its own
+struct KvGunzipArenas {
+    KvArena comp, syms, tails, meta, window, small, crc;
+    void release() { for (KvArena *a : {&comp, &syms, &tails, &meta, &window, &small, &crc}) a->release(); }
+};
 // NULL unless the image starts with a gzip member header; arenas: buffers to work in (kept by the caller across files), or NULL
 KvGunzip *kv_gunzip_open(const uint8_t *image, uint64_t size, KvGunzipArenas *arenas);
 void kv_gunzip_set_uploader(KvGunzip *g, std::function<bool(uint8_t *, uint64_t, uint64_t, hipStream_t)> upload);

@@ -10,9 +10,8 @@
 //
 // No MFMA anywhere: this is 64-bit integer hashing plus random byte-granular table access.
 #include <algorithm>
-#include <map>
 
-#include "kv_binned.h"
+#include "kv_internal.h"
 #include "kv_device.h"
 
 namespace {
@@ -290,13 +289,8 @@ namespace {
 // grow-only device scratch of the point-query entry points, one per stream (hipMalloc + hipFree per call cost more
 // than the kernels they wrap when filter / simlike issue thousands of small queries)
 struct PointScratch { KvArena arena; std::mutex mu; };
-std::map<hipStream_t, PointScratch> g_point_scratch;
-std::mutex g_point_scratch_mu;
-PointScratch &point_scratch()
-{
-    std::lock_guard<std::mutex> lk(g_point_scratch_mu);
-    return g_point_scratch[kv_stream_key(kv_stream())];
-}
+KvPerStream<PointScratch> g_point_scratch;
+PointScratch &point_scratch() { return g_point_scratch.get(kv_stream()); }
 inline size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace
 

@@ -305,16 +305,6 @@ __global__ __launch_bounds__(LOC_THREADS) void k_loc_scan(LocScan p)
 inline unsigned loc_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096)); }
 inline uint64_t loc_pow2(uint64_t n, uint64_t least) { uint64_t c = least; while (c < n) c <<= 1; return c; }
 
-template <typename T>
-hipError_t loc_grow(T **p, uint64_t *cap, uint64_t want)
-{
-    if (want <= *cap) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const hipError_t e = kv_hip_malloc(p, want * sizeof(T));
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
 }  // namespace
 
 struct kv_localize {
@@ -324,16 +314,13 @@ struct kv_localize {
     uint64_t *d_keys = nullptr;
     unsigned long long *d_table = nullptr, *d_ctr = nullptr;
     uint32_t *d_pf = nullptr, *d_occ = nullptr;
-    uint8_t *d_text = nullptr;
-    uint64_t text_cap = 0;                  // bytes, a multiple of 16
-    uint32_t *d_ids = nullptr;
-    uint64_t *d_pos = nullptr;
-    uint64_t ids_cap = 0, pos_cap = 0;
+    KvArena text;                           // the chunk being scanned; bytes, a multiple of 16
+    KvArena ids, pos;                       // its matches: uint32_t contig ids, uint64_t positions
     bool ovf = false;                       // the last call overflowed its buffer at (ovf_off, ovf_len): its repeat must not count again
     uint64_t ovf_off = 0, ovf_len = 0;
     ~kv_localize()
     {
-        void *all[] = {d_keys, d_table, d_ctr, d_pf, d_occ, d_text, d_ids, d_pos};
+        void *all[] = {d_keys, d_table, d_ctr, d_pf, d_occ, text.p, ids.p, pos.p};
         for (void *p : all)
             if (p) (void)hipFree(p);
     }
@@ -452,16 +439,16 @@ extern "C" int kv_localize_scan(kv_localize *h, const char *text, uint64_t n_byt
     h->ovf = false;
     if (n_bytes < (uint64_t)h->Z || h->n_distinct == 0) return KV_OK;
     hipStream_t st = kv_stream();
-    hipError_t e = loc_grow(&h->d_text, &h->text_cap, (n_bytes + 15) & ~15ull);
-    if (e == hipSuccess) e = loc_grow(&h->d_ids, &h->ids_cap, std::max<uint64_t>(capacity, 1));
-    if (e == hipSuccess) e = loc_grow(&h->d_pos, &h->pos_cap, std::max<uint64_t>(capacity, 1));
+    hipError_t e = h->text.need_exact((n_bytes + 15) & ~15ull);
+    if (e == hipSuccess) e = h->ids.need_exact(std::max<uint64_t>(capacity, 1) * 4);
+    if (e == hipSuccess) e = h->pos.need_exact(std::max<uint64_t>(capacity, 1) * 8);
     KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "scan buffers allocation failed: %s", hipGetErrorString(e));
-    KV_HIP(hipMemcpyAsync(h->d_text, text, n_bytes, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(h->text.p, text, n_bytes, hipMemcpyHostToDevice, st));
     KV_HIP(hipMemsetAsync(h->d_ctr, 0, 8, st));
     LocScan p;
-    p.text = h->d_text; p.n = n_bytes; p.alloc = h->text_cap; p.goff = global_offset; p.Z = h->Z;
+    p.text = (const uint8_t *)h->text.p; p.n = n_bytes; p.alloc = h->text.bytes; p.goff = global_offset; p.Z = h->Z;
     p.keys = h->d_keys; p.table = h->d_table; p.capmask = h->capmask; p.pf = h->d_pf; p.pfmask = h->pfmask;
-    p.occ = h->d_occ; p.ctr = h->d_ctr; p.out_ids = h->d_ids; p.out_pos = h->d_pos; p.cap = capacity; p.count = repeat ? 0 : 1;
+    p.occ = h->d_occ; p.ctr = h->d_ctr; p.out_ids = (uint32_t *)h->ids.p; p.out_pos = (uint64_t *)h->pos.p; p.cap = capacity; p.count = repeat ? 0 : 1;
     const uint64_t n_tiles = (n_bytes - (uint64_t)h->Z + 1 + LOC_TILE - 1) / LOC_TILE;
     KV_REQUIRE(n_tiles < 0x7FFFFFFFull, KV_ERR_ARG, "kv_localize_scan: chunk too large");
     {
@@ -483,8 +470,8 @@ extern "C" int kv_localize_scan(kv_localize *h, const char *text, uint64_t n_byt
     *n_found = *found;
     const uint64_t n_copy = std::min<uint64_t>(*found, capacity);
     if (n_copy) {
-        KV_HIP(hipMemcpyAsync(ids_out, h->d_ids, n_copy * 4, hipMemcpyDeviceToHost, st));
-        KV_HIP(hipMemcpyAsync(pos_out, h->d_pos, n_copy * 8, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipMemcpyAsync(ids_out, h->ids.p, n_copy * 4, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipMemcpyAsync(pos_out, h->pos.p, n_copy * 8, hipMemcpyDeviceToHost, st));
         KV_HIP(hipStreamSynchronize(st));
     }
     if (*found > capacity) { h->ovf = true; h->ovf_off = global_offset; h->ovf_len = n_bytes; }

@@ -13,9 +13,8 @@
 // them, and the bit mask doubles as the per-band mask that the multi-GPU merge all-reduces.
 #include <algorithm>
 #include <functional>
-#include <map>
 
-#include "kv_binned.h"          // kv_device_cus
+#include "kv_internal.h"
 #include "kv_novel_device.h"
 #include "kv_kmer2bit_device.h"
 
@@ -455,33 +454,12 @@ struct VerdictCache {
     int bits = 0;
     uint64_t signature = 0;
 };
-std::map<hipStream_t, VerdictCache> g_vcache;
-std::mutex g_vcache_mu;
+KvPerStream<VerdictCache> g_vcache;
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return kv_hip_malloc(&p, n ? n : 4); }
-    template <typename T> T *as() { return (T *)p; }
-};
-
-// grow-only scratch of the scan, one pair of arenas per stream: hipMalloc / hipFree of the 66 MB bit mask and
+// grow-only scratch of the scan, one set of arenas per stream: hipMalloc / hipFree of the 66 MB bit mask and
 // the hit arrays on every call cost more than the emit kernel
-struct Arena {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t need(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        hipError_t e = kv_hip_malloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-};
 struct ScanArenas {
-    Arena work, hits, set, abund;
+    KvArena work, hits, set, abund;
     std::mutex mu;                                  // one scan at a time per stream
     // kv_hits_lazy: the hit arrays leave `hits` on a copy stream of this stream's own, behind the scan's last kernel (kdone); the
     // next scan that writes `hits` queues behind the copy (copied)
@@ -490,8 +468,7 @@ struct ScanArenas {
     bool copy_pending = false;
 };
 thread_local bool g_hits_lazy = false;
-std::map<hipStream_t, ScanArenas> g_scan_arenas;
-std::mutex g_scan_arenas_mu;
+KvPerStream<ScanArenas> g_scan_arenas;
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // point p.vcache at this stream's verdict cache, (re)allocating or clearing it as the signature requires
@@ -505,11 +482,7 @@ int attach_vcache(NovelParams &p, kv_sketch *const *ctrls, int ncase, int nctrl,
             sig = (sig ^ sk->uid) * 0xff51afd7ed558ccdull;
             sig = (sig ^ sk->version) * 0xc4ceb9fe1a85ec53ull;
         }
-        VerdictCache *vc;
-        {
-            std::lock_guard<std::mutex> lk(g_vcache_mu);
-            vc = &g_vcache[kv_stream_key(st)];
-        }
+        VerdictCache *vc = &g_vcache.get(st);
         int want = 20;
         // ~2 slots per distinct inherited k-mer at 30x; a batch of many (vcache_2bit) meets the sample's, not its own: room for 2^29
         while (want < (p.vcache_2bit ? 29 : 28) && (1ull << want) < n_kmers / 2) ++want;
@@ -634,11 +607,7 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
     *out = hits;
     if (reads->n_tiles == 0) return KV_OK;
 
-    ScanArenas *arenas;
-    {
-        std::lock_guard<std::mutex> lk(g_scan_arenas_mu);
-        arenas = &g_scan_arenas[kv_stream_key(st)];
-    }
+    ScanArenas *arenas = &g_scan_arenas.get(st);
     std::lock_guard<std::mutex> arena_lock(arenas->mu);
     hipError_t e = hipSuccess;
     if (arenas->copy_pending) {                     // the previous scan's hits may still be leaving the buffers this one writes
@@ -657,7 +626,7 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
     }
     const size_t b_mask = up256(mask_words * 4), b_flags = p.screen > 0 ? up256(reads->n_reads * 4) : 0;
     const size_t b_tcount = up256((uint64_t)reads->n_tiles * 4), b_tbase = up256(((uint64_t)reads->n_tiles + 1) * 8);
-    e = arenas->work.need(b_mask + b_flags + b_tcount + b_tbase + 256);
+    e = arenas->work.need_exact(b_mask + b_flags + b_tcount + b_tbase + 256);
     unsigned char *wp = (unsigned char *)arenas->work.p;
     if (e == hipSuccess) {
         if (d_mask) {
@@ -685,7 +654,7 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
         uint64_t slots = 1u << 16;
         while (slots < n_kmers / 64 && slots < (1ull << 24)) slots <<= 1;
         const uint64_t list_cap = slots / 8;
-        if (arenas->abund.need(up256(slots * 8) + up256(slots * (uint64_t)S) + up256(list_cap * 4) + 256) == hipSuccess) {
+        if (arenas->abund.need_exact(up256(slots * 8) + up256(slots * (uint64_t)S) + up256(list_cap * 4) + 256) == hipSuccess) {
             p.ab_keys = (unsigned long long *)arenas->abund.p;
             p.ab_vals = (uint8_t *)arenas->abund.p + up256(slots * 8);
             p.ab_mask = slots - 1;
@@ -742,7 +711,7 @@ int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers,
     if (e == hipSuccess) e = hipMemcpyAsync(&nhits, d_tbase_p + reads->n_tiles, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess && nhits) {
-        e = arenas->hits.need(2 * up256(nhits * 4) + up256(nhits * (uint64_t)S));
+        e = arenas->hits.need_exact(2 * up256(nhits * 4) + up256(nhits * (uint64_t)S));
         p.hit_read = (uint32_t *)arenas->hits.p;
         p.hit_off = (uint32_t *)((unsigned char *)arenas->hits.p + up256(nhits * 4));
         p.hit_abund = (uint8_t *)arenas->hits.p + 2 * up256(nhits * 4);
@@ -1030,13 +999,11 @@ __global__ __launch_bounds__(256) void k_novel_pairs(NovelParams p, const uint64
 namespace {
 int scan_items(kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, int nctrl, const void *d_items, uint64_t n_items,
                int case_min, int ctrl_max, void *d_hit_tags, void *d_hit_abund, uint64_t hit_cap, uint64_t *n_hits, bool want_hash);
-std::map<hipStream_t, KvArena> g_pairs_bits;     // per stream: the bit map of the pairs scan's first probe (grow-only; kv_scratch_trim)
-std::mutex g_pairs_bits_mu;
+KvPerStream<KvArena> g_pairs_bits;     // per stream: the bit map of the pairs scan's first probe (grow-only; kv_scratch_trim)
 }
 void kv_novel_scratch_release()
 {
-    std::lock_guard<std::mutex> lk(g_pairs_bits_mu);
-    for (auto &kv : g_pairs_bits) kv.second.release();
+    g_pairs_bits.for_each([](KvArena &a) { a.release(); });
 }
 
 extern "C" int kv_novel_scan_hashes(kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, int nctrl,
@@ -1085,15 +1052,14 @@ int scan_items(kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, int 
     // pairs (want_hash): every k-mer once, no verdict cache, several first probes in flight (KV_NOVEL_PAIRS=0: the list kernel)
     const bool pairs = want_hash && !(kv_knob("KV_NOVEL_PAIRS") && atoi(kv_knob("KV_NOVEL_PAIRS")) == 0);
     if (!pairs) { const int rc = attach_vcache(p, ctrls, ncase, nctrl, ctrl_max, n_items, st); if (rc != KV_OK) return rc; }
-    DevBuf d_count;
+    KvDevBuf d_count;
     KV_HIP(d_count.alloc(8));
     KV_HIP(hipMemsetAsync(d_count.p, 0, 8, st));
     const uint64_t bits_from = kv_knob("KV_NOVEL_BITS_MIN") ? strtoull(kv_knob("KV_NOVEL_BITS_MIN"), nullptr, 10) : (1ull << 20);      // (tests: 1)
     if (pairs && cases[0]->h.storage == ST_BYTE && n_items >= bits_from && !(kv_knob("KV_NOVEL_BITS") && atoi(kv_knob("KV_NOVEL_BITS")) == 0)) {
         // the first probe -- where a sequencing-error k-mer ends -- from a bit map of table 0 (a streaming pass over the table first: worth it
         // from a million pairs up)
-        KvArena *bits;
-        { std::lock_guard<std::mutex> lk(g_pairs_bits_mu); bits = &g_pairs_bits[kv_stream_key(st)]; }
+        KvArena *bits = &g_pairs_bits.get(st);
         if (bits->need(kv_round_up(((cases[0]->h.size[0] + 31) >> 5) * 4, 256)) == hipSuccess) {
             kv_case_bits_launch((const uint8_t *)cases[0]->h.tab[0], (uint64_t)cases[0]->h.size[0], case_min, (uint32_t *)bits->p, st);
             p.case0_bits = (const uint32_t *)bits->p;
@@ -1156,16 +1122,12 @@ int build_hit_set(NovelParams &p, int kind, int ksize, int nsamples, const void 
     const int fam = kv_hashfam_of(kind);
     p.hp = make_hash_params(ksize, fam);
     p.ncase = nsamples;
-    ScanArenas *arenas;
-    {
-        std::lock_guard<std::mutex> lk(g_scan_arenas_mu);
-        arenas = &g_scan_arenas[kv_stream_key(st)];
-    }
+    ScanArenas *arenas = &g_scan_arenas.get(st);
     uint64_t slots = 1024;
     while (slots < 2 * n + 64) slots <<= 1;
     {
         std::lock_guard<std::mutex> arena_lock(arenas->mu);
-        KV_HIP(arenas->set.need(up256(slots * 8) + up256(slots * (uint64_t)nsamples)));
+        KV_HIP(arenas->set.need_exact(up256(slots * 8) + up256(slots * (uint64_t)nsamples)));
     }
     unsigned long long *keys = (unsigned long long *)arenas->set.p;
     uint8_t *abund = (uint8_t *)arenas->set.p + up256(slots * 8);

@@ -20,7 +20,6 @@
 //                   (read, offset) key (k_merge_keys, k_merge_rank): `kevlar novel --all-bands`.
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -214,26 +213,11 @@ __global__ __launch_bounds__(256) void k_route_tail(RouteParams p)
     }
 }
 
-struct Scratch {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t need(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        hipError_t e = kv_hip_malloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-};
-std::map<hipStream_t, Scratch> g_route_scratch;   // grow-only, one arena per stream
-std::mutex g_route_mu;
+KvPerStream<KvArena> g_route_scratch;   // grow-only, one arena per stream
 }
 void kv_route_scratch_release()
 {
-    std::lock_guard<std::mutex> lk(g_route_mu);
-    for (auto &kv : g_route_scratch) { if (kv.second.p) (void)hipFree(kv.second.p); kv.second.p = nullptr; kv.second.bytes = 0; }
+    g_route_scratch.for_each([](KvArena &a) { a.release(); });
 }
 namespace {
 
@@ -252,12 +236,8 @@ int route_scratch(RouteParams &p, uint64_t n_kmers, uint32_t W, hipStream_t st)
     const size_t b_seg = round_up((uint64_t)p.ndest * p.nwg * p.seg_cap * 8 * W, 256);
     const size_t b_cnt = round_up((uint64_t)p.ndest * p.nwg * 4, 256), b_off = round_up((uint64_t)p.ndest * p.nwg * 8, 256);
     const size_t b_ovf = round_up(p.ovf_cap * 8 * W, 256), b_od = round_up(p.ovf_cap, 256), b_ctr = 1024;
-    Scratch *scratch;
-    {
-        std::lock_guard<std::mutex> lk(g_route_mu);
-        scratch = &g_route_scratch[kv_stream_key(st)];
-    }
-    KV_HIP(scratch->need(b_seg + b_cnt + b_off + b_ovf + b_od + b_ctr));
+    KvArena *scratch = &g_route_scratch.get(st);
+    KV_HIP(scratch->need_exact(b_seg + b_cnt + b_off + b_ovf + b_od + b_ctr));
     unsigned char *base = (unsigned char *)scratch->p;
     p.seg = (uint64_t *)base; base += b_seg;
     p.seg_count = (uint32_t *)base; base += b_cnt;
@@ -327,13 +307,6 @@ __global__ void k_gather_hits(const uint64_t *sorted_tags, const uint32_t *sorte
         for (int c = 0; c < S; ++c) out_abund[i * (uint64_t)S + c] = abund[src * (uint64_t)S + c];
     }
 }
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return kv_hip_malloc(&p, n ? n : 4); }
-    template <typename T> T *as() { return (T *)p; }
-};
 
 // ---- kv_hits_merge: R runs of hits, each sorted by (read, offset) and pairwise disjoint, into one sorted list ------------------
 // Merge by rank: the place of a hit in the output is its index in its own run plus, for every other run, the number of
@@ -834,7 +807,7 @@ __global__ void k_row_keys(const uint8_t *rows, const uint32_t *idx, uint64_t n,
     }
 }
 
-int argsort_pairs(DevBuf &keys_in, DevBuf &idx_in, DevBuf &keys_out, DevBuf &idx_out, DevBuf &tmp, size_t &tmp_bytes, uint64_t n, hipStream_t st)
+int argsort_pairs(KvDevBuf &keys_in, KvDevBuf &idx_in, KvDevBuf &keys_out, KvDevBuf &idx_out, KvDevBuf &tmp, size_t &tmp_bytes, uint64_t n, hipStream_t st)
 {
     size_t need = 0;
     KV_HIP(rocprim::radix_sort_pairs(nullptr, need, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(), idx_in.as<uint32_t>(),
@@ -857,7 +830,7 @@ extern "C" int kv_argsort_u64(const uint64_t *keys, uint64_t n, uint32_t *order)
     KV_REQUIRE(n < (1ull << 32), KV_ERR_ARG, "kv_argsort_u64: too many keys");
     if (n == 0) return KV_OK;
     hipStream_t st = kv_stream();
-    DevBuf k_in, k_out, v_in, v_out, tmp;
+    KvDevBuf k_in, k_out, v_in, v_out, tmp;
     size_t tmp_bytes = 0;
     KV_HIP(k_in.alloc(n * 8)); KV_HIP(k_out.alloc(n * 8)); KV_HIP(v_in.alloc(n * 4)); KV_HIP(v_out.alloc(n * 4));
     KV_HIP(hipMemcpyAsync(k_in.p, keys, n * 8, hipMemcpyHostToDevice, st));
@@ -876,12 +849,12 @@ extern "C" int kv_argsort_rows(const void *rows, uint64_t n, uint32_t width, uin
     KV_REQUIRE(n < (1ull << 32) && width >= 1, KV_ERR_ARG, "kv_argsort_rows: bad size");
     if (n == 0) return KV_OK;
     hipStream_t st = kv_stream();
-    DevBuf d_rows, k_in, k_out, v_a, v_b, tmp;
+    KvDevBuf d_rows, k_in, k_out, v_a, v_b, tmp;
     size_t tmp_bytes = 0;
     KV_HIP(d_rows.alloc(n * (uint64_t)width)); KV_HIP(k_in.alloc(n * 8)); KV_HIP(k_out.alloc(n * 8)); KV_HIP(v_a.alloc(n * 4)); KV_HIP(v_b.alloc(n * 4));
     KV_HIP(hipMemcpyAsync(d_rows.p, rows, n * (uint64_t)width, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_iota_u32, dim3(256), dim3(256), 0, st, v_a.as<uint32_t>(), n);
-    DevBuf *cur = &v_a, *nxt = &v_b;
+    KvDevBuf *cur = &v_a, *nxt = &v_b;
     const uint32_t chunks = (width + 7u) / 8u;
     for (uint32_t c = chunks; c-- > 0;) {
         hipLaunchKernelGGL(k_row_keys, dim3(1024), dim3(256), 0, st, d_rows.as<uint8_t>(), cur->as<uint32_t>(), n, width, c * 8u, k_in.as<unsigned long long>());
@@ -908,7 +881,7 @@ extern "C" int kv_hits_from_tagged(const void *d_tags, const void *d_abund, uint
     *out = hits;
     if (n_valid == 0) return KV_OK;
     hipStream_t st = kv_stream();
-    DevBuf k_out, v_in, v_out, tmp, o_read, o_off, o_abund;
+    KvDevBuf k_out, v_in, v_out, tmp, o_read, o_off, o_abund;
     hipError_t e = k_out.alloc(n_total * 8);
     if (e == hipSuccess) e = v_in.alloc(n_total * 4);
     if (e == hipSuccess) e = v_out.alloc(n_total * 4);
@@ -966,7 +939,7 @@ extern "C" int kv_hits_merge(const void *d_read, const void *d_offset, const voi
     hits->nsamples = nsamples;
     if (n == 0) { *out = hits; return KV_OK; }
     hipStream_t st = kv_stream();
-    DevBuf keys, starts, bad, o_read, o_off, o_abund;
+    KvDevBuf keys, starts, bad, o_read, o_off, o_abund;
     KvReadback back;
     const uint32_t *flag = nullptr;
     hipError_t e = keys.alloc(n * 8);
