@@ -499,6 +499,36 @@ int kv_localize_counts(kv_localize *h, uint32_t *counts_out, uint64_t n_windows)
 int kv_localize_stats(kv_localize *h, uint64_t *stats_out);
 int kv_localize_destroy(kv_localize *h);
 
+/* ---- contig-to-cutout alignment, the first half of `kevlar call` (kevlar/alignment.pyx, src/align.c; kv_align.hip) ----------
+ * The reference aligns one contig against one cutout with ksw2's extension aligner, unbanded and without z-drop: a global
+ * alignment, score = H(tlen - 1, qlen - 1), traceback from that corner.  Here a batch of such jobs runs on the device and
+ * reproduces score and CIGAR exactly (the rule, with its tie-breaking: DESIGN.md section 10).
+ * Targets and queries are two sets of ASCII sequences, each concatenated with offsets (the convention of the seed set above).
+ * Job k is jobs[3k .. 3k + 2] = (target index, query index, reverse flag); with the flag set the device aligns the reverse
+ * complement of the query, which the caller therefore uploads once.  A/a C/c G/g T/t are the four bases, every other byte scores 0
+ * against everything.  match, gapopen and gapextend lie in 0..127, mismatch in -127..127 (either sign means the penalty).  An
+ * empty sequence, an index out of range or a score out of range is KV_ERR_ARG before anything touches the device.
+ * Results per job: scores[k]; the CIGAR as run_counts[k] runs at runs[run_offsets[k] ..], in forward order, a run being
+ * length << 4 | op with op 0 = M, 1 = I, 2 = D.  `runs` is one pool of `capacity` runs for the whole batch and the jobs' places in
+ * it are in no particular order; *n_runs is the number of runs the batch needs, and when it exceeds `capacity` the pool's content
+ * is undefined and the caller repeats the call with a larger pool.  There is no fixed 4096-character CIGAR buffer as in the
+ * reference: a CIGAR is as long as it is.
+ * Working memory: one direction byte per cell, padded to whole strips of KV_ALIGN_STRIP query columns (the size of one job: the
+ * z_bytes call).  z_budget bounds the direction bytes alive at a time: the jobs are ordered by cell count, largest first, and cut
+ * into as many launches as that takes (the plan call, host code only: order[] = the jobs in that order, launch_ends[l] = one past
+ * the last position of launch l; both hold n_jobs entries).  One job that alone exceeds the budget is KV_ERR_CAPACITY.
+ * The stats call is for measurements only (scratch/align_rate.py): of the last batch, stats_out[0..3] = launches, 100 MHz ticks
+ * all waves spent filling, ticks they spent in traceback and copy, cells.                                                      */
+#define KV_ALIGN_STRIP 256
+int kv_align_z_bytes(uint32_t tlen, uint32_t qlen, uint64_t *bytes);
+int kv_align_plan(const uint32_t *tlens, const uint32_t *qlens, uint64_t n_jobs, uint64_t z_budget, uint32_t *order,
+                  uint64_t *launch_ends, uint64_t *n_launches);
+int kv_align_batch(const char *tbases, const uint64_t *toffsets, uint64_t n_targets, const char *qbases,
+                   const uint64_t *qoffsets, uint64_t n_queries, const uint32_t *jobs, uint64_t n_jobs, int match, int mismatch,
+                   int gapopen, int gapextend, uint64_t z_budget, int32_t *scores, uint64_t *run_offsets, uint32_t *run_counts,
+                   uint32_t *runs, uint64_t capacity, uint64_t *n_runs);
+int kv_align_stats(uint64_t *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

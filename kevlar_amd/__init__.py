@@ -125,6 +125,8 @@ from kevlar_amd import augment  # noqa: E402
 from kevlar_amd import gentrio  # noqa: E402
 from kevlar_amd import reference  # noqa: E402
 from kevlar_amd import localize  # noqa: E402
+from kevlar_amd import alignment  # noqa: E402
+from kevlar_amd.alignment import contig_align as align  # noqa: E402
 from kevlar_amd import cli  # noqa: E402
 
 

@@ -142,6 +142,10 @@ SIGNATURES = {
     'kv_localize_counts': (i32, [vp, vp, u64]),
     'kv_localize_stats': (i32, [vp, vp]),
     'kv_localize_destroy': (i32, [vp]),
+    'kv_align_z_bytes': (i32, [u32, u32, u64p]),
+    'kv_align_plan': (i32, [vp, vp, u64, u64, vp, vp, u64p]),
+    'kv_align_batch': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, i32, i32, i32, i32, u64, vp, vp, vp, vp, u64, u64p]),
+    'kv_align_stats': (i32, [vp]),
 }
 
 
