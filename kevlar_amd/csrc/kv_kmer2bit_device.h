@@ -2,7 +2,7 @@
 //
 // The per-k-mer kernels of rounds 1-2 (k_consume, k_bin_hash_direct, k_novel_mark) stage a tile's reads as ASCII of both strands in
 // LDS and roll byte windows over it: ~470-540 lane-instructions per k-mer (profiles/r4_final/sq_counters_cfg4_band.txt).  The
-// per-distinct-k-mer kernels of kv_skm.hip hash a k-mer from its packed key through a 256-entry byte -> 4 characters table
+// per-distinct-k-mer kernels of kv_skm_bucket_device.h hash a k-mer from its packed key through a 256-entry byte -> 4 characters table
 // (skm_key_hash): ~290.  Batches with nothing to deduplicate -- config 4's 0.6x batches under banding, where seven k-mers in
 // eight are hashed only to learn that they belong to another band -- are all hashing, so they get that path too: a thread takes
 // CH consecutive k-mers of one read, cuts the first out of the packed words, takes its reverse complement once and rolls both

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_route_compact(RouteParams p)
 
 // overflow items join the tail of their destination (after the packed segments).  A workgroup counts its items per destination, takes
 // its stretch of every tail with ONE device atomic each and deals the places out through LDS cursors (a device atomic per item, then per
-// wave and destination, was most of the 8-26 ms this took for 4.5 M items); entries marked 0xff hold no item (kv_skm.hip, k_skm_loose_route)
+// wave and destination, was most of the 8-26 ms this took for 4.5 M items); entries marked 0xff hold no item (kv_skm_bucket_device.h, k_skm_loose_route)
 template <int W>
 __global__ __launch_bounds__(256) void k_route_tail(RouteParams p)
 {

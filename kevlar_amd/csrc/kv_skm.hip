@@ -15,6 +15,10 @@
 //                     k-mer, then walk the records again and set the hit-mask bit of every occurrence of an
 //                     interesting k-mer; k_tile_hits + the ordinary emit kernels do the rest.
 //
+// This file is the host half: geometry planning, arenas, launches, the C entry points.  The kernels are in two headers that
+// only this translation unit includes: kv_skm_emit_device.h (S1, S2) and kv_skm_bucket_device.h (the LDS table, the bucket
+// walk, S3, S3', S6, the owner's scan and the loose-list kernels).
+//
 // Nothing here can lose a k-mer: a full segment, a full LDS table or an uncacheable key diverts single records to a
 // "loose" list that is processed one occurrence at a time (k_skm_loose_*); if that list overflows too, a flag makes
 #include <algorithm>
@@ -23,2204 +27,10 @@
 #include "kv_binned.h"
 #include "kv_novel_device.h"
 #include "kv_skm_device.h"
-
-struct SkmGeom {
-    int k, m, w, wpow;               // wpow: largest power of two <= w
-    int kw, nbw, recw, ncap;         // key words, base words and total words of a record, most k-mers of a record
-    uint32_t C1, F2, fbits;          // coarse buckets, fine buckets per coarse bucket (2^fbits)
-    uint32_t nwg1, nwg2, quota1;     // writers of S1 (persistent workgroups) and S2 (workgroups per coarse bucket)
-    uint32_t cap1, cap2;             // records per private segment
-    uint32_t np_max;                 // most bases any tile stages
-    uint64_t stride;                 // record position = read * stride + offset
-    uint64_t *seg1; uint32_t *cnt1;  // [C1][nwg1][cap1] records / [C1][nwg1]
-    uint64_t *seg2; uint32_t *cnt2;  // [C1 * F2][nwg2][cap2] / [C1 * F2][nwg2]
-    uint64_t *loose; uint64_t loose_cap;
-    unsigned long long *ctr;         // [SKM_CTR_COUNT] counters, zeroed for every batch: the slots are the SkmCtr enumerators below
-    uint32_t n_buckets, quota3;
-    uint32_t sbw;                    // words of record-start bits per wave in the bucket walk
-    uint64_t bucket_kmers;           // average k-mers per fine bucket
-    uint32_t force_loose;            // KV_SKM_FORCE_LOOSE: k_skm_count sends one key in 64 through the loose list
-    // abundance list the count pass writes (KvAbundList; abl_keys == nullptr: off): every workgroup appends to its own
-    // stretch of abl_cap_wg entries and notes where each bucket's entries start
-    uint64_t *abl_keys; uint8_t *abl_cnts; uint32_t *abl_bstart, *abl_bcount; uint32_t abl_cap_wg;
-    // S2 over records that several ranks emitted (minimizer-sharded exchange, kv_skm_mex_route): seg1 / cnt1 then hold n_src
-    // slabs of [C1][nwg1] segments one after the other, and a coarse bucket has n_src * nwg1 segments (0 / 1: the usual one slab)
-    // distinct list the count pass writes for a batch that is going to be scanned (SkmIndex::dl; dl_keys == nullptr: off): EVERY
-    // distinct k-mer of a bucket with its hash, appended like the abundance list (a stretch per workgroup, start + count per bucket)
-    uint64_t *dl_keys, *dl_hash; uint32_t *dl_bstart, *dl_bcount; uint32_t dl_cap_wg;
-    uint32_t dl_chunk, dl_nchunks;   // k_skm_route only: != 0 -- the list is a pool of dl_nchunks chunks of dl_chunk entries that the workgroups draw from (SKM_CTR_POOL_CHUNKS) instead of one stretch each
-    uint32_t n_src;
-    const uint64_t *seg1_off;        // non-null: segment `slot` starts at record seg1_off[slot] (compacted records) instead of slot * cap1
-    uint64_t read_base;              // global index of the batch's first read (record positions of a read shard; 0 otherwise)
-    // seg1 / cnt1 laid out [nwg1][C1] instead of [C1][nwg1]: a writer's ~250 open segments then lie within a few megabytes -- two or
-    // three pages of the address translation -- instead of one every nwg1 x cap1 records (11 MB: a page each).  The exchange
-    // layouts keep bucket-major order (a destination's coarse buckets must be contiguous: kv_skm_mex_pack).
-    uint32_t seg1_wmajor;
-    // compact: the records of this batch are 16-byte records without positions (kv_skm_device.h; recw = 2) -- a count into a sketch
-    // that is not going to be scanned from this batch.  Loose records keep the classic form: lrecw = 1 + nbw words each.
-    uint32_t compact;
-    int lrecw;
-    // (records are oriented: a record whose minimizer stands reversed in the read (strand bit of its value, skm_order_s) holds the
-    // REVERSE COMPLEMENT of the read's bases (header flag), so every k-mer of every record is stored on the strand on which its minimizer
-    // is canonical -- and that strand is the k-mer's key in the bucket tables: the walk takes k-mers as they stand, no second strand, no
-    // comparison.  The exchange layouts cut them the same way.)
-    uint32_t passes;                 // k_skm_route takes a bucket's k-mers in at least this many passes (0 / 1: one) -- buckets bigger than its LDS table
-    uint32_t bpt;                    // buckets per ticket of the bucket kernels' work counter (a power of two)
-};
-
-// the slots of SkmGeom::ctr
-enum SkmCtr {
-    SKM_CTR_LOOSE = 0,               // records on the loose list
-    SKM_CTR_FAIL = 1,                // failure flag: a record was lost (loose list overflow), a table could not take a key, or the pass was given up
-    SKM_CTR_TICKET_S1 = 2, SKM_CTR_TICKET_COUNT = 3, SKM_CTR_TICKET_SCAN = 4,     // work tickets of S1 (tiles), of the count / route pass and of the scan (buckets)
-    SKM_CTR_RECORDS = 5,             // records S1 emitted
-    SKM_CTR_LOOSE_S12 = 6,           // loose records S1 + S2 left behind (the host copies SKM_CTR_LOOSE here before the bucket kernels add theirs)
-    SKM_CTR_DISTINCT = 7,            // distinct k-mers the count / route pass found in its LDS tables
-    SKM_CTR_ARRIVED = 8,             // k-mer occurrences that arrived at an exchange owner (k_mex_sum_kmers)
-    SKM_CTR_DL_RAN_OUT = 9,          // workgroups whose stretch of the distinct list ran out, or draws from its pool of chunks that found it empty
-    SKM_CTR_SET_HITS = 10,           // hits kv_skm_mex_scan_set stored (SetHitSink::count)
-    SKM_CTR_POOL_CHUNKS = 13,        // (nothing uses 11 and 12) chunks drawn from the distinct list's pool (k_skm_route, dl_chunk != 0)
-    SKM_CTR_COUNT
-};
-// the slots of other stages' counters that kernels here touch: BinGeom::ctr (kv_binned.h), KvRouteSink::ctr (kv_internal.h)
-enum { BIN_CTR_FAIL = 1, BIN_CTR_ADDED = 2, ROUTE_CTR_OVERFLOW = 1, ROUTE_CTR_DEST0 = 18 };
-
-// segment `seg` of coarse bucket c in seg1 / cnt1, counted in segments
-__device__ __forceinline__ uint64_t skm_seg1_slot(const SkmGeom &sg, uint32_t c, uint32_t seg)
-{
-    if (sg.seg1_wmajor) return (uint64_t)seg * sg.C1 + c;
-    if (sg.n_src <= 1u) return (uint64_t)c * sg.nwg1 + seg;
-    const uint32_t src = seg / sg.nwg1, w = seg - src * sg.nwg1;
-    return ((uint64_t)src * sg.C1 + c) * sg.nwg1 + w;
-}
-__device__ __forceinline__ uint32_t skm_seg1_count(const SkmGeom &sg) { return sg.nwg1 * (sg.n_src > 1u ? sg.n_src : 1u); }
-// first record of segment `slot`
-__device__ __forceinline__ uint64_t skm_seg1_first(const SkmGeom &sg, uint64_t slot) { return sg.seg1_off ? sg.seg1_off[slot] : slot * sg.cap1; }
-
-// the controls' abundance lists a scan may use (same bucket geometry as the case sample's buckets)
-#define SKM_MAX_ABL 8
-struct SkmAblSet {
-    int n, ctrl_max;
-    const uint64_t *keys[SKM_MAX_ABL];
-    const uint8_t *cnts[SKM_MAX_ABL];
-    const uint32_t *bstart[SKM_MAX_ABL], *bcount[SKM_MAX_ABL];
-    uint32_t maxv[SKM_MAX_ABL];      // what a counter of that control can hold: an entry rejects if min(count, maxv) > ctrl_max
-};
+#include "kv_skm_emit_device.h"
+#include "kv_skm_bucket_device.h"
 
 namespace {
-
-#define SKM_THREADS1 512
-#define SKM_S1_WAVE_THREADS_DEFAULT 512u      // threads per workgroup of k_skm_emit_wave (1024: one workgroup per CU, see the kernel)
-#define SKM_THREADS3 512
-#define SKM_MAXPROBE 48
-// One global counter hands out work; a returning atomic on one word saturates at ~90 per microsecond on this chip
-// (MI355X_MICROARCH.md, "dequeue"), i.e. 1.3 ms for the 117 k tiles of a 7.5 M-read sample if every tile were a
-// ticket.  A ticket therefore covers several units of work.
-#define SKM_TILES_PER_TICKET 8u
-#define SKM_BUCKETS_PER_TICKET 8u
-// workgroups of the loose-list kernels (grid-stride over a list that is all but empty when the batch fits: 4096 workgroups cost
-// 0.14 ms each launch just to start, find nothing and leave)
-#define SKM_LOOSE_WGS 1024
-
-// (32-byte records -- one aligned sector each, two 16-byte stores -- were measured against these 24-byte ones: WRITE_SIZE
-// fell from 2.5 to 2.3 GB per sample for 1.3 / 1.7 GB stored, the readers fetched 0.4 GB more each, times did not move.)
-// a record in as few store instructions as its size allows (every lane of a scattered store is its own cache line: the memory pipe
-// takes an instruction's 64 lines one by one, so three 8-byte stores cost three passes where a 16-byte and an 8-byte one cost two)
-__device__ __forceinline__ void skm_store_record_wide(uint64_t *dst, uint64_t hdr, const uint64_t *bw, int nbw)
-{
-    typedef uint64_t u64x2 __attribute__((ext_vector_type(2), aligned(8)));
-    *(u64x2 *)dst = u64x2{hdr, bw[0]};
-    if (nbw == 2) dst[2] = bw[1];
-    else if (nbw == 3) *(u64x2 *)(dst + 2) = u64x2{bw[1], bw[2]};
-}
-
-__device__ __forceinline__ void skm_store_record(uint64_t *dst, uint64_t hdr, const uint64_t *bw, int nbw)
-{
-    dst[0] = hdr;
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-        if (t < nbw) dst[1 + t] = bw[t];
-}
-
-__device__ __forceinline__ void skm_loose_push(const SkmGeom &sg, uint64_t hdr, const uint64_t *bw)
-{
-    const unsigned long long idx = atomicAdd(&sg.ctr[SKM_CTR_LOOSE], 1ull);
-    if (idx < sg.loose_cap) skm_store_record(sg.loose + idx * (uint64_t)sg.lrecw, hdr, bw, sg.nbw);
-    else sg.ctr[SKM_CTR_FAIL] = 1;
-}
-
-// ---- S1 ------------------------------------------------------------------------------------------------
-struct SkmTile {
-    uint32_t len[KV_TILE_MAX_READS], nk[KV_TILE_MAX_READS];
-    uint32_t bpre[KV_TILE_MAX_READS + 1];      // staged-base prefix: flat position of a read's first base
-    uint32_t wpre[KV_TILE_MAX_READS + 1];      // packed-word prefix inside the tile
-    uint32_t cpre[KV_TILE_MAX_READS + 1];      // chunk prefix (a chunk = CH consecutive k-mer starts of one read)
-    uint32_t uni_wpr, uni_cpr, uni_len;        // words / chunks / bases per read if all reads of the tile have the same length, else 0
-    float inv_wpr, inv_cpr, inv_len;
-    uint32_t seg_start, read0, next_tile;
-    uint32_t wtot[3][SKM_THREADS1 / 64];       // run starts per (round, wave)
-};
-
-// q / d for q < 2^16 with the precomputed float reciprocal (off by at most one before the fix-up)
-__device__ __forceinline__ uint32_t skm_div(uint32_t q, uint32_t d, float inv)
-{
-    uint32_t r = (uint32_t)((float)q * inv);
-    if (r * d > q) r -= 1;
-    else if ((r + 1) * d <= q) r += 1;
-    return r;
-}
-
-__device__ __forceinline__ uint32_t skm_search(const uint32_t *pre, uint32_t n, uint32_t q)
-{
-    uint32_t lo = 0, hi = n;      // largest r with pre[r] <= q (empty entries share their successor's prefix)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (pre[mid] <= q) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// CH consecutive k-mer starts per thread in the window-minimum pass; needs w > CH
-template <int CH>
-__global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint32_t n_tiles, SkmGeom sg)   // 6 waves per SIMD: three workgroups per CU
-{
-    __shared__ SkmTile sh;
-    __shared__ uint32_t cur[256];
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const uint32_t nwl = sg.np_max / 16u + KV_TILE_MAX_READS + 8u;     // every read starts on a word: up to one partial word each
-    uint32_t *wl = smem;                                              // the tile's packed words
-    uint32_t *mh = smem + nwl;                                        // order value of the m-mer starting at every base
-    uint16_t *starts = (uint16_t *)(mh + sg.np_max + 96u);            // run starts (flat positions < 2^16), in position order
-    const int k = sg.k, m = sg.m, w = sg.w;
-    const int lane = threadIdx.x & 63;
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_THREADS1) cur[c] = 0;
-    if (threadIdx.x == 0) sh.next_tile = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull) * SKM_TILES_PER_TICKET;
-    uint64_t n_rec = 0;
-    // Batches of equal-length reads (rd.uni_len): the layout of a tile is arithmetic, so the packed words of the NEXT
-    // tile are requested while this one is processed (two registers per thread) and the per-tile chain of dependent loads
-    // -- tile descriptor, word offsets, lengths, words: half of this kernel's time went there -- disappears.
-    const bool uni = rd.uni_len != 0;
-    const uint32_t uni_wpr = (rd.uni_len + 15u) >> 4;
-    uint32_t pf0 = 0, pf1 = 0, pf_tile = 0xffffffffu;
-    auto prefetch = [&](uint32_t tile) {
-        pf_tile = tile;
-        if (tile >= n_tiles) return;
-        const uint64_t r0 = (uint64_t)tile * rd.uni_per_tile;
-        const uint32_t nr = (uint32_t)min((uint64_t)rd.uni_per_tile, rd.n_reads - r0), nw = nr * uni_wpr;
-        const uint32_t *src = rd.words + r0 * uni_wpr;
-        pf0 = threadIdx.x < nw ? src[threadIdx.x] : 0u;
-        pf1 = threadIdx.x + SKM_THREADS1 < nw ? src[threadIdx.x + SKM_THREADS1] : 0u;
-    };
-    if (uni) {
-        __syncthreads();
-        prefetch(sh.next_tile);
-    }
-    for (uint32_t taken = 0; taken < sg.quota1; ++taken) {
-        __syncthreads();                                   // previous tile finished, ticket visible
-        const uint32_t tile = sh.next_tile;
-        if (tile >= n_tiles) break;
-        TileDesc td;
-        if (uni) { td.first = tile * rd.uni_per_tile; td.count = (uint32_t)min((uint64_t)rd.uni_per_tile, rd.n_reads - td.first); td.seg_start = 0; td.seg = 0; }
-        else td = rd.tile[tile];
-        const uint32_t r0 = td.first, nr = td.count;
-        const uint32_t seg_start = td.seg ? td.seg_start : 0u;
-        const uint64_t w0 = uni ? (uint64_t)r0 * uni_wpr : rd.woff[r0] + (seg_start >> 4);
-        uint32_t nwords;
-        if (uni) {
-            nwords = nr * uni_wpr;
-        } else if (td.seg) {
-            const uint32_t rest = rd.len[r0] - seg_start, want = (uint32_t)KV_SEG_BASES + (uint32_t)k - 1u;
-            nwords = ((rest < want ? rest : want) + 15u) >> 4;
-        } else {
-            nwords = (uint32_t)(rd.woff[r0 + nr] - w0);
-        }
-        if (uni) {
-            if (threadIdx.x < 64) {
-                const uint32_t i0 = 2 * threadIdx.x, i1 = i0 + 1, L = rd.uni_len;
-                const uint32_t kk = L >= (uint32_t)k ? L - (uint32_t)k + 1u : 0u, cc = (kk + CH - 1) / CH;
-                if (i0 < nr) { sh.len[i0] = L; sh.nk[i0] = kk; sh.bpre[i0] = i0 * L; sh.cpre[i0] = i0 * cc; sh.wpre[i0] = i0 * uni_wpr; }
-                if (i1 < nr) { sh.len[i1] = L; sh.nk[i1] = kk; sh.bpre[i1] = i1 * L; sh.cpre[i1] = i1 * cc; sh.wpre[i1] = i1 * uni_wpr; }
-                if (threadIdx.x == 0) {
-                    sh.bpre[nr] = nr * L; sh.cpre[nr] = nr * cc; sh.wpre[nr] = nr * uni_wpr; sh.seg_start = 0; sh.read0 = r0;
-                    const bool okk = L >= (uint32_t)k;
-                    sh.uni_wpr = okk ? uni_wpr : 0u; sh.uni_cpr = okk ? cc : 0u;
-                    sh.inv_wpr = okk ? 1.0f / (float)uni_wpr : 0.0f; sh.inv_cpr = okk ? 1.0f / (float)cc : 0.0f;
-                    sh.uni_len = okk ? L : 0u; sh.inv_len = okk ? 1.0f / (float)L : 0.0f;
-                }
-            }
-        } else if (threadIdx.x < 64) {
-            const uint32_t i0 = 2 * threadIdx.x, i1 = i0 + 1;
-            uint32_t l0 = 0, l1 = 0;
-            if (i0 < nr) {
-                l0 = rd.len[r0 + i0];
-                if (td.seg) {
-                    const uint32_t rest = l0 - seg_start, want = (uint32_t)KV_SEG_BASES + (uint32_t)k - 1u;
-                    l0 = rest < want ? rest : want;
-                }
-            }
-            if (i1 < nr) l1 = rd.len[r0 + i1];
-            const uint32_t k0 = l0 >= (uint32_t)k ? l0 - (uint32_t)k + 1u : 0u, k1 = l1 >= (uint32_t)k ? l1 - (uint32_t)k + 1u : 0u;
-            const uint32_t c0 = (k0 + CH - 1) / CH, c1 = (k1 + CH - 1) / CH;
-            uint32_t eb, tot, ecb, ctot;
-            const uint32_t ea = wave_excl_scan2(l0, l1, eb, tot);
-            const uint32_t eca = wave_excl_scan2(c0, c1, ecb, ctot);
-            if (i0 < nr) { sh.len[i0] = l0; sh.nk[i0] = k0; sh.bpre[i0] = ea; sh.cpre[i0] = eca; }
-            if (i1 < nr) { sh.len[i1] = l1; sh.nk[i1] = k1; sh.bpre[i1] = eb; sh.cpre[i1] = ecb; }
-            if (threadIdx.x == 0) { sh.bpre[nr] = tot; sh.cpre[nr] = ctot; sh.seg_start = seg_start; sh.read0 = r0; }
-            const uint32_t ref = __shfl(l0, 0);
-            const bool same = (i0 >= nr || l0 == ref) && (i1 >= nr || l1 == ref);
-            const bool uniform = __all(same) && ref >= (uint32_t)k;
-            if (threadIdx.x == 0) {
-                const uint32_t wpr = (ref + 15u) >> 4, cpr = (ref - (uint32_t)k + 1u + CH - 1) / CH;
-                sh.uni_wpr = uniform ? wpr : 0u; sh.uni_cpr = uniform ? cpr : 0u;
-                sh.inv_wpr = uniform ? 1.0f / (float)wpr : 0.0f; sh.inv_cpr = uniform ? 1.0f / (float)cpr : 0.0f;
-                sh.uni_len = uniform ? ref : 0u; sh.inv_len = uniform ? 1.0f / (float)ref : 0.0f;
-            }
-            if (td.seg) {
-                if (threadIdx.x == 0) { sh.wpre[0] = 0; sh.wpre[1] = (l0 + 15) >> 4; }
-            } else {
-                if (i0 < nr) sh.wpre[i0] = (uint32_t)(rd.woff[r0 + i0] - w0);
-                if (i1 < nr) sh.wpre[i1] = (uint32_t)(rd.woff[r0 + i1] - w0);
-                if (threadIdx.x == 0) sh.wpre[nr] = (uint32_t)(rd.woff[r0 + nr] - w0);
-            }
-        }
-        if (uni && pf_tile == tile && nwords + 8u <= 2u * SKM_THREADS1) {
-            wl[threadIdx.x] = pf0;                                             // (zero beyond the tile's words)
-            if (threadIdx.x + SKM_THREADS1 < nwords + 8u) wl[threadIdx.x + SKM_THREADS1] = pf1;
-        } else {
-            for (uint32_t i = threadIdx.x; i < nwords + 8u; i += SKM_THREADS1) wl[i] = i < nwords ? rd.words[w0 + i] : 0u;
-        }
-        __syncthreads();
-        // the next ticket is fetched while this tile is processed (everybody has read the current one by now)
-        if (threadIdx.x == 0) {
-            if ((tile + 1u) % SKM_TILES_PER_TICKET) sh.next_tile = tile + 1u;       // same ticket
-            else sh.next_tile = taken + 1 < sg.quota1 ? (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull) * SKM_TILES_PER_TICKET : 0xffffffffu;
-        }
-        const uint32_t NB = sh.bpre[nr];
-        // P1: one thread per packed word: the order values of the m-mers starting at its 16 bases
-        const uint32_t mmask = m == 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u);
-        for (uint32_t wi = threadIdx.x; wi < nwords; wi += SKM_THREADS1) {
-            const uint32_t r = sh.uni_wpr ? skm_div(wi, sh.uni_wpr, sh.inv_wpr) : skm_search(sh.wpre, nr, wi);
-            const uint32_t j0 = (wi - sh.wpre[r]) * 16u, L = sh.len[r];
-            const uint32_t q0 = sh.bpre[r] + j0;
-            const uint64_t win = (uint64_t)wl[wi] | ((uint64_t)wl[wi + 1] << 32);
-            // the reverse complement of all 32 bases once: base i of `win`, complemented, is base 31 - i of `rcw`, so the reverse
-            // complement of the m-mer at base jj is the m-mer of rcw at base 32 - m - jj (m <= 16, jj <= 15)
-            const uint64_t rcw = ~skm_rev2_64(win);
-            const uint32_t rc0 = 2u * (32u - (uint32_t)m);
-            // lane l starts at base l mod 16 of its word: the 64 stores of one instruction then fall into different banks
-#pragma unroll
-            for (int step = 0; step < 16; ++step) {
-                const uint32_t jj = ((uint32_t)step + (uint32_t)lane) & 15u, j = j0 + jj;
-                const uint32_t f = (uint32_t)(win >> (2u * jj)) & mmask, r = (uint32_t)(rcw >> (rc0 - 2u * jj)) & mmask;
-                if (j < L) mh[q0 + jj] = j + (uint32_t)m <= L ? skm_order_s(f, r) : 0xffffffffu;
-            }
-        }
-        if (threadIdx.x < 96) mh[NB + threadIdx.x] = 0xffffffffu;
-        __syncthreads();
-        if (uni) prefetch(sh.next_tile);                   // written before this barrier; lands during P2 .. P4
-        // P2: one thread per chunk of CH k-mer starts: the minimum over the w m-mers of each (shared suffix of the chunk + the
-        // w - 1 - CH values every window contains + a growing prefix) and where it changes.  A run is a stretch of k-mers with the
-        // same minimizer VALUE (its bucket is a function of that value, taken once per run in P4; two values that share a bucket
-        // -- one pair in C1 x F2 -- merely give two records where one would have done).
-        const uint32_t nchunks = sh.cpre[nr];                                      // <= 8192 / CH + 64 < 3 * SKM_THREADS1
-        const uint32_t nrounds = (nchunks + SKM_THREADS1 - 1u) / SKM_THREADS1;
-        uint32_t my_q[3], my_starts[3];
-#pragma unroll
-        for (int round = 0; round < 3; ++round) {
-            const uint32_t ci = (uint32_t)round * SKM_THREADS1 + threadIdx.x;
-            uint32_t startmask = 0, q = 0;
-            if (ci < nchunks) {
-                const uint32_t r = sh.uni_cpr ? skm_div(ci, sh.uni_cpr, sh.inv_cpr) : skm_search(sh.cpre, nr, ci);
-                const uint32_t j = (ci - sh.cpre[r]) * CH, nkr = sh.nk[r];
-                q = sh.bpre[r] + j;
-                uint32_t suf[CH + 1];                     // suf[i + 1] = min(mh[q + i .. q + CH - 1]), i = -1 .. CH - 1
-                uint32_t run = 0xffffffffu;
-#pragma unroll
-                for (int i = CH - 1; i >= 0; --i) { run = min(run, mh[q + i]); suf[i + 1] = run; }
-                suf[0] = j > 0 ? min(run, mh[q - 1]) : run;
-                uint32_t mid = 0xffffffffu;
-                for (uint32_t t = CH; t + 2 <= (uint32_t)w; ++t) mid = min(mid, mh[q + t]);     // mh[q + CH .. q + w - 2]
-                uint32_t prev = min(suf[0], mid);         // minimizer of the k-mer in front of the chunk (unused when j == 0)
-                uint32_t diff = j == 0 ? 1u : 0u;
-                run = 0xffffffffu;
-#pragma unroll
-                for (int i = 0; i < CH; ++i) {
-                    run = min(run, mh[q + (uint32_t)w - 1u + i]);
-                    const uint32_t v = min(min(suf[i + 1], mid), run);
-                    diff |= (v != prev ? 1u : 0u) << i;
-                    prev = v;
-                }
-                const uint32_t nv = min((uint32_t)CH, nkr - j);          // k-mers of the read that start in this chunk (>= 1)
-                startmask = diff & ((2u << (nv - 1u)) - 1u);
-            }
-            my_q[round] = q; my_starts[round] = startmask;
-        }
-        // run starts in position order (chunks are numbered in position order): prefix over lanes, waves, rounds
-        uint32_t incl[3] = {0u, 0u, 0u};
-#pragma unroll
-        for (int round = 0; round < 3; ++round) {
-            if ((uint32_t)round < nrounds) {
-                uint32_t v = (uint32_t)__popc(my_starts[round]);
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(v, d);
-                    if (lane >= d) v += up;
-                }
-                incl[round] = v;
-                if (lane == 63) sh.wtot[round][threadIdx.x >> 6] = v;
-            }
-        }
-        __syncthreads();
-        uint32_t nstart = 0;
-#pragma unroll
-        for (int round = 0; round < 3; ++round) {
-            if ((uint32_t)round < nrounds) {
-                uint32_t before = nstart;
-                for (uint32_t wv = 0; wv < SKM_THREADS1 / 64; ++wv) {
-                    const uint32_t n = sh.wtot[round][wv];
-                    if (wv < (threadIdx.x >> 6)) before += n;
-                    nstart += n;
-                }
-                uint32_t base = before + incl[round] - (uint32_t)__popc(my_starts[round]);
-                uint32_t bits = my_starts[round];
-                while (bits) {
-                    const int i = __ffs((int)bits) - 1;
-                    bits &= bits - 1;
-                    starts[base++] = (uint16_t)(my_q[round] + (uint32_t)i);
-                }
-            }
-        }
-        __syncthreads();
-        // P4: one thread per run: measure it, cut it into records of <= ncap k-mers, store them
-        for (uint32_t i = threadIdx.x; i < nstart; i += SKM_THREADS1) {
-            const uint32_t q = starts[i];
-            const uint32_t r = sh.uni_len ? skm_div(q, sh.uni_len, sh.inv_len) : skm_search(sh.bpre, nr, q), j = q - sh.bpre[r];
-            const uint32_t limit = q - j + sh.nk[r];          // flat position one past the read's last k-mer
-            const uint32_t nxt = i + 1 < nstart ? (uint32_t)starts[i + 1] : limit;     // the next run (of this read or a later one)
-            uint32_t left = (nxt < limit ? nxt : limit) - q;
-            uint32_t minv = 0xffffffffu;
-            for (uint32_t t = 0; t < (uint32_t)w; ++t) minv = min(minv, mh[q + t]);
-            uint32_t coarse, fine;
-            skm_bucket_of(minv, sg.C1, sg.fbits, coarse, fine);
-            uint64_t pos = (sg.read_base + sh.read0 + r) * sg.stride + sh.seg_start + j;
-            uint32_t b = sh.wpre[r] * 16u + j;                // base index inside wl
-            while (left) {
-                const uint32_t n = min(left, (uint32_t)sg.ncap);
-                uint64_t bw[3];
-#pragma unroll
-                for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? skm_bases32(wl, b + 32u * t) : 0ull;
-                const uint32_t rev = minv & 1u;
-                if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
-                const uint64_t hdr = skm_header(pos, n, fine, rev);
-                const uint32_t p = atomicAdd(&cur[coarse], 1u);
-                if (p < sg.cap1) skm_store_record(sg.seg1 + (skm_seg1_slot(sg, coarse, blockIdx.x) * sg.cap1 + p) * (uint64_t)sg.recw, hdr, bw, sg.nbw);
-                else skm_loose_push(sg, hdr, bw);
-                n_rec += 1;
-                left -= n; pos += n; b += n;
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_THREADS1) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
-    n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
-}
-
-// ---- S1, batches of equal-length reads: a wave per group of reads -----------------------------------------------
-// The tile kernel above spends most of its time parked: six workgroup barriers per tile, between phases that keep 60-80 % of
-// the lanes busy, and a phase is as slow as its slowest wave (dissected: skeleton 0.37 ms, order values 0.37, minima + run
-// starts 0.43, records 0.30, their stores 0.43 per 7.5 M reads).  When every read of the batch has the same length the layout
-// is arithmetic, so a WAVE can take R consecutive reads (R x words per read <= 64: one packed word per lane) through the same
-// four phases on its own slice of LDS with no workgroup barrier at all -- only the order of its own LDS operations -- and the
-// 24 waves of a CU are in different phases at any time.  The workgroup still shares the coarse cursors and its segments.
-#define SKM_MT_PER_TICKET 64u     // 1 M groups per 7.5 M reads: one device-wide counter takes ~90 updates per microsecond (16 per ticket: 0.74 ms of the kernel)
-#define SKM_WAVE_RUNS 128u        // runs of a group listed at a time (a group has ~55; more go round again)
-// Flat position of base j of the group's read r: r * Lp + j with Lp = 16 * words per read, so a position is also the base index
-// into the staged words.  Order values live at mh[p + (p >> PS)], PS = log2(CH): a padding word per chunk, so that lanes that
-// walk consecutive chunks (P2) or consecutive words (P1) hit different banks and every offset inside a chunk is a constant.
-__host__ __device__ inline uint32_t skm_wave_slice_words(uint32_t R, uint32_t L, uint32_t nk, int ch)
-{
-    const uint32_t lp = 16u * ((L + 15u) >> 4), pmax = R * lp + 96u;
-    (void)nk;
-    return 132u + pmax + pmax / (uint32_t)ch + 2u + SKM_WAVE_RUNS + (SKM_WAVE_RUNS + 2u) / 2u;      // words (twice), order values, minimizer + start of SKM_WAVE_RUNS runs at a time
-}
-
-// THREADS: 512 (three workgroups per CU, 768 writers) or 1024 (ONE workgroup of 16 waves per CU, 256 writers).  A writer keeps one
-// open cache line per coarse bucket, and the L2 of an XCD (4 MB) merges a record's 16- and 8-byte stores into whole lines only while
-// the open lines of the XCD's workgroups fit beside the rest of its traffic: 251 buckets x 96 workgroups x 128 B = 3 MB do not
-// (WRITE_SIZE 2.5-2.7 GB per 1.36 GB of records, measured with 512 and with 768 writers), 251 x 32 x 128 B = 1 MB do (1.0 x).
-template <int CH, int THREADS>
-__global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_wave(ReadsDev rd, SkmGeom sg, uint32_t R, uint32_t n_mt, uint32_t quota_mt, uint32_t per_ticket)
-{
-    constexpr uint32_t PS = CH == 16 ? 4u : 3u;
-    __shared__ uint32_t cur[256];
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const uint32_t wave = threadIdx.x >> 6;
-    const int k = sg.k, m = sg.m, w = sg.w;
-    const uint32_t L = rd.uni_len, wpr = (L + 15u) >> 4, Lp = 16u * wpr, nk = L - (uint32_t)k + 1u, cpr = (nk + CH - 1) / CH;
-    const float inv_wpr = 1.0f / (float)wpr, inv_cpr = 1.0f / (float)cpr;
-    const uint32_t pmax = R * Lp + 96u;
-    uint32_t *wl0 = smem + wave * skm_wave_slice_words(R, L, nk, CH), *mh = wl0 + 132u;
-    uint32_t *sval = mh + pmax + pmax / CH + 2u;
-    uint16_t *starts = (uint16_t *)(sval + SKM_WAVE_RUNS);
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += THREADS) cur[c] = 0;
-    if ((threadIdx.x & 63u) < 2u) { wl0[64u + (threadIdx.x & 63u)] = 0; wl0[130u + (threadIdx.x & 63u)] = 0; }
-    __syncthreads();
-    const uint32_t mmask = m == 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u);
-    const uint32_t rc0 = 2u * (32u - (uint32_t)m);
-    uint64_t n_rec = 0;
-    uint64_t *const my_seg = sg.seg1 + skm_seg1_slot(sg, 0u, blockIdx.x) * sg.cap1 * (uint64_t)sg.recw;       // + coarse * cstride: this workgroup's segment of a coarse bucket
-    const uint64_t cstride = (sg.seg1_wmajor ? 1ull : (uint64_t)sg.nwg1) * sg.cap1 * (uint64_t)sg.recw;
-    uint32_t mt = 0, mt_end = 0, taken = 0, pf = 0, pf_mt = 0xffffffffu, parity = 0;
-    for (;;) {
-        // (everything P1 and P2 derive from the lane number alone is the same for every group; left to itself the compiler
-        // computes all of it once in front of the loop -- 16 shift pairs, 32 lane masks -- and spills it: 196 bytes of scratch
-        // per lane and two reloads per order value.  An opaque copy of the lane number keeps the arithmetic where it is used.)
-        uint32_t lane = threadIdx.x & 63u;
-        asm volatile("" : "+v"(lane));
-        auto words_of = [&](uint32_t t) -> uint32_t {
-            const uint64_t r0 = (uint64_t)t * R;
-            const uint32_t nr = (uint32_t)min((uint64_t)R, rd.n_reads - r0);
-            return lane < nr * wpr ? rd.words[r0 * wpr + lane] : 0u;
-        };
-        if (mt == mt_end) {
-            if (taken >= quota_mt) break;
-            uint32_t t = 0;
-            if (lane == 0) t = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_S1], 1ull);
-            t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-            if ((uint64_t)t * per_ticket >= n_mt) break;
-            mt = t * per_ticket;
-            mt_end = min(mt + per_ticket, n_mt);
-        }
-        const uint64_t r0 = (uint64_t)mt * R;
-        const uint32_t nr = (uint32_t)min((uint64_t)R, rd.n_reads - r0), nwords = nr * wpr;
-        // The next group's words are requested now and WAITED FOR in front of P4: a wait at the top of the next round would also
-        // wait for this round's record stores (one counter, in order), i.e. for a round trip to HBM per group.
-        uint32_t *wl = wl0 + 66u * parity;
-        uint32_t word;
-        if (pf_mt == mt) word = pf;                               // (already in the other buffer's place: stored below)
-        else { word = words_of(mt); wl[lane] = word; }
-        const bool more = mt + 1u < mt_end;
-        if (more) { pf = words_of(mt + 1u); pf_mt = mt + 1u; }
-        // P1: the order values of the m-mers starting at the 16 bases of this lane's word.  (Values of m-mers that run past the
-        // end of their read are garbage: no window of a k-mer of the read contains them.)
-        if (lane < nwords) {
-            const uint32_t up = (uint32_t)__shfl_down((int)word, 1);
-            const uint64_t win = (uint64_t)word | ((uint64_t)(lane == 63u ? 0u : up) << 32);
-            const uint64_t rcw = ~skm_rev2_64(win);
-            uint32_t *dst = mh + 16u * lane + (CH == 16 ? lane : 2u * lane);
-#pragma unroll
-            for (int step = 0; step < 16; ++step) {
-                const uint32_t f = (uint32_t)(win >> (2 * step)) & mmask, rv = (uint32_t)(rcw >> (rc0 - 2u * (uint32_t)step)) & mmask;
-                dst[step + (step >> PS)] = skm_order_s(f, rv);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // P2: a lane per chunk of CH k-mer starts: window minima (shared suffix of the chunk + the values every window of the chunk
-        // contains + a growing prefix) and where they change; then every run start with its minimizer, in position order
-        const uint32_t nchunks = nr * cpr;
-        uint32_t startmask = 0, q = 0;
-        uint32_t v[CH];
-#pragma unroll
-        for (int i = 0; i < CH; ++i) v[i] = 0;
-        if (lane < nchunks) {
-            const uint32_t r = skm_div(lane, cpr, inv_cpr);
-            const uint32_t j = (lane - r * cpr) * CH;
-            q = r * Lp + j;                                   // a multiple of CH
-            const uint32_t *src = mh + q + (q >> PS);
-            auto at = [&](uint32_t i) -> uint32_t { return src[i + (i >> PS)]; };       // i: constant offsets from the chunk's first value
-            uint32_t suf[CH + 1];
-            uint32_t run = 0xffffffffu;
-#pragma unroll
-            for (int i = CH - 1; i >= 0; --i) { run = min(run, at((uint32_t)i)); suf[i + 1] = run; }
-            suf[0] = j > 0 ? min(run, mh[q - 1u + ((q - 1u) >> PS)]) : run;
-            uint32_t mid = 0xffffffffu;
-            for (uint32_t t = CH; t + 2 <= (uint32_t)w; ++t) mid = min(mid, at(t));
-            uint32_t prev = min(suf[0], mid);
-            uint32_t diff = j == 0 ? 1u : 0u;
-            run = 0xffffffffu;
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                run = min(run, at((uint32_t)w - 1u + (uint32_t)i));
-                v[i] = min(min(suf[i + 1], mid), run);
-                diff |= (v[i] != prev ? 1u : 0u) << i;
-                prev = v[i];
-            }
-            const uint32_t nv = min((uint32_t)CH, nk - j);
-            startmask = diff & ((2u << (nv - 1u)) - 1u);
-        }
-        uint32_t incl = (uint32_t)__popc(startmask);
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t upv = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += upv;
-        }
-        const uint32_t nstart = (uint32_t)__shfl((int)incl, 63);
-        if (more) wl0[66u * (parity ^ 1u) + lane] = pf;
-        for (uint32_t lo = 0; lo < nstart; lo += SKM_WAVE_RUNS) {
-            // runs lo .. lo + SKM_WAVE_RUNS (one more than are processed: the end of the last one), listed by the lanes that found them
-            {
-                uint32_t at = incl - (uint32_t)__popc(startmask) - lo;          // wraps for runs in front of this round: fails the test below
-#pragma unroll
-                for (int i = 0; i < CH; ++i) {
-                    if ((startmask >> i) & 1u) {
-                        if (at <= SKM_WAVE_RUNS) { starts[at] = (uint16_t)(q + (uint32_t)i); if (at < SKM_WAVE_RUNS) sval[at] = v[i]; }
-                        at += 1u;
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // P4: a lane per run: its bucket, its records
-            const uint32_t here = min(SKM_WAVE_RUNS, nstart - lo);
-            for (uint32_t i = lane; i < here; i += 64u) {
-                const uint32_t qs = starts[i];
-                const uint32_t r = skm_div(qs >> 4, wpr, inv_wpr), j = qs - r * Lp;
-                const uint32_t limit = qs - j + nk;                // position one past the read's last k-mer
-                const uint32_t nxt = lo + i + 1u < nstart ? (uint32_t)starts[i + 1] : limit;
-                uint32_t left = (nxt < limit ? nxt : limit) - qs;
-                uint32_t coarse, fine;
-                skm_bucket_of(sval[i], sg.C1, sg.fbits, coarse, fine);
-                uint64_t pos = (sg.read_base + r0 + r) * sg.stride + j;
-                uint32_t b = qs;
-                while (left) {
-                    const uint32_t n = min(left, (uint32_t)sg.ncap);
-                    uint64_t bw[3];
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? skm_bases32(wl, b + 32u * t) : 0ull;
-                    const uint32_t rev = sval[i] & 1u;
-                    if (rev) skm_rc_bases(bw, sg.nbw, n + (uint32_t)k - 1u);
-                    const uint64_t hdr = skm_header(pos, n, fine, rev);
-                    const uint32_t p = atomicAdd(&cur[coarse], 1u);
-                    if (p < sg.cap1) skm_store_record_wide(my_seg + coarse * cstride + p * (uint32_t)sg.recw, hdr, bw, sg.nbw);
-                    else skm_loose_push(sg, hdr, bw);
-                    n_rec += 1;
-                    left -= n; pos += n; b += n;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        parity ^= 1u;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        mt += 1; taken += 1;
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += THREADS) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
-    n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
-}
-
-// ---- S1, batches of equal-length reads: a LANE per read (round 5) ---------------------------------------------------
-// The wave kernel above deals a group of 7 reads over the lanes three different ways (a lane per packed word, per chunk of k-mer
-// starts, per run) with the order values, the run starts and their minimizers passing through LDS between the phases: 57
-// lane-instructions per base, a third of the lanes idle in every phase (100 bases are 6.25 words; 7 reads are 49 words and 63 chunks).
-// Here a lane takes ONE READ and walks its m-mers in order, all 64 lanes at the same position -- so everything that depends on the
-// position alone (which words, which shifts, whether a k-mer ends here) is scalar -- and the window minimum is the streaming form of
-// the block decomposition: m-mers in blocks of B = 20; the k-mer whose window ENDS at m-mer p takes min(suffix minimum of the block
-// it starts in, [the whole block between, for w = 40,] prefix minimum of the block p is in); a block's values overwrite the suffix
-// minima they have just been compared with, and one backward pass turns them into the next block's suffix minima.  Per m-mer:
-// two extractions (forward and reverse complement from the block's 64-bit window, constant shifts), a minimum, the order multiply;
-// per k-mer: three minima and a compare.  A lane whose minimizer changes appends the run it has just finished -- (minimizer, read,
-// first k-mer, length) -- to the wave's list in LDS (ballot + mbcnt; one in thirteen lanes per position), and every few blocks the
-// list is turned into records a lane per RUN, all lanes busy: the record code of the kernels above, unchanged, so the records are
-// the same records.  No order value, window minimum or run start ever goes through LDS; the words do, once.
-// Work is dealt statically (group g to wave g mod waves): a wave has ~19 groups of 64 reads per 7.5 M-read sample, tickets of any
-// useful size would leave a tail of a ticket, and the device-wide counter is not in the picture.
-// Instances: w = 20 (k = 31: C = 1) and w = 40 (k = 51: C = 2), m = 12, reads of up to 16 x NW bases; everything else takes the kernels above.
-#define SKM_LANE_B 20
-#define SKM_LANE_CAP 320u         // finished runs a wave lists between two flushes (64 reads x 40 k-mers bring ~250; what does not fit is written at once)
-#define SKM_LANE_FLUSH_BLOCKS 2u  // blocks of B m-mers between two flushes of that list (the kernel takes it as an argument: compiled in, the
-                                  // cut of 24-byte records measured ~5 us of 1040 slower per launch)
-#define SKM_LANE_THREADS 512
-#define SKM_LANE_WAVES 6          // waves per SIMD the kernel is compiled for (3 workgroups per CU)
-// a wave's slice of LDS: the group's words, their reverse complement read by read (oriented records), the run list
-__host__ __device__ inline uint32_t skm_lane_slice_words(uint32_t wpr) { return 2u * (64u * wpr + 4u) + 2u * SKM_LANE_CAP + 2u; }
-
-// one block of B m-mers for every lane's read: Sold holds the suffix minima of the block the finishing k-mers START in (C blocks
-// back) and receives this block's values; Smid (C = 2) the suffix minima of the block between, Smid[0] its minimum
-template <int C, typename Append>
-__device__ __forceinline__ void skm_lane_block(const uint32_t *wl, uint32_t rbase, uint32_t lane, uint32_t b, uint32_t npos, uint32_t nk,
-                                               uint32_t (&Sold)[SKM_LANE_B], const uint32_t (&Smid)[SKM_LANE_B], uint32_t &prev_v, uint32_t &start_prev,
-                                               uint32_t &n_ent, Append append)
-{
-    constexpr int B = SKM_LANE_B;
-    const uint32_t bit0 = 2u * B * b, w0 = bit0 >> 5, s0 = bit0 & 31u;
-    const uint32_t x0 = wl[rbase + w0], x1 = wl[rbase + w0 + 1u], x2 = wl[rbase + w0 + 2u];
-    const uint32_t xlo = __builtin_amdgcn_alignbit(x1, x0, s0), xhi = __builtin_amdgcn_alignbit(x2, x1, s0);
-    const uint64_t X = (uint64_t)xlo | ((uint64_t)xhi << 32);          // bases 20 b .. 20 b + 31 of the read
-    const uint64_t R = ~skm_rev2_64(X);                                // their reverse complement: the m-mer at base j in bits 40 - 2 j .. 63 - 2 j
-    uint32_t pre = 0xffffffffu;
-#pragma unroll
-    for (int j = 0; j < B; ++j) {
-        const uint32_t p = (uint32_t)B * b + (uint32_t)j;
-        if (p >= npos) break;                                          // (the same for every lane: a scalar branch)
-        const uint32_t f = (uint32_t)(X >> (2 * j)) & 0xffffffu, rv = (uint32_t)(R >> (40 - 2 * j)) & 0xffffffu;
-        const uint32_t val = skm_order_s(f, rv);
-        pre = min(pre, val);
-        if (p + 1u >= (uint32_t)(C * B)) {
-            const uint32_t i = p + 1u - (uint32_t)(C * B);             // the k-mer whose window ends at this m-mer
-            if (i < nk) {
-                uint32_t minv;
-                if (C == 1) minv = j == B - 1 ? pre : min(Sold[j == B - 1 ? 0 : j + 1], pre);
-                else minv = j == B - 1 ? min(Smid[0], pre) : min(min(Sold[j == B - 1 ? 0 : j + 1], Smid[0]), pre);
-                if (i == 0u) {
-                    prev_v = minv; start_prev = lane;                 // lane | first k-mer << 6: the upper word of the run's entry, but for its end
-                } else {
-                    // (a lane that finds the list full keeps its run open and asks again at the next k-mer, after the flush that full
-                    // list brings about: the run is then cut a few k-mers late -- k-mers in a bucket other than their minimizer's, which
-                    // costs deduplication, never correctness: adds of a k-mer's occurrences compose whichever buckets they met in)
-                    // (lanes without a read walk words of zeros: one minimizer from end to end, no run ever finishes)
-                    const bool want = minv != prev_v;
-                    const unsigned long long bal = __ballot(want);
-                    if (want && append(bal, prev_v, start_prev, i)) { prev_v = minv; start_prev = lane | (i << 6); }
-                    n_ent += (uint32_t)__popcll(bal);
-                }
-            }
-        }
-        Sold[j] = val;
-    }
-#pragma unroll
-    for (int j = B - 2; j >= 0; --j) Sold[j] = min(Sold[j], Sold[j + 1]);
-}
-
-// (C = 2 keeps two arrays of suffix minima: 4 waves per SIMD -- two workgroups per CU, 128 registers -- where C = 1 runs 6; the kernel
-// is bound by instruction issue from 4 waves per SIMD up, so the lower occupancy costs nothing: measured with 512 writers at C = 1)
-template <int C, int NW>
-__global__ __launch_bounds__(SKM_LANE_THREADS, C == 2 ? 4 : SKM_LANE_WAVES) void k_skm_emit_lane(ReadsDev rd, SkmGeom sg, uint32_t n_groups, uint32_t flush_blocks)
-{
-    constexpr int B = SKM_LANE_B;
-    __shared__ uint32_t cur[256];
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, nwaves = SKM_LANE_THREADS / 64;
-    const uint32_t L = rd.uni_len, wpr = (L + 15u) >> 4, nk = L - (uint32_t)sg.k + 1u, npos = L - 12u + 1u;
-    uint32_t *wl = smem + wave * skm_lane_slice_words(wpr);
-    uint32_t *rcl = wl + 64u * wpr + 4u;             // read r's reverse complement: base i of it = complement of the read's base L - 1 - i
-    unsigned long long *ent = (unsigned long long *)(rcl + 64u * wpr + 4u);
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_LANE_THREADS) cur[c] = 0;
-    __syncthreads();
-    uint64_t n_rec = 0;
-    uint64_t *const my_seg = sg.seg1 + skm_seg1_slot(sg, 0u, blockIdx.x) * sg.cap1 * (uint64_t)sg.recw;       // + coarse * cstride: this workgroup's segment of a coarse bucket
-    const uint64_t cstride = (sg.seg1_wmajor ? 1ull : (uint64_t)sg.nwg1) * sg.cap1 * (uint64_t)sg.recw;
-    const uint64_t n_words = rd.n_reads * (uint64_t)wpr;
-    const uint32_t nblocks = (npos + B - 1u) / B;
-    const uint32_t gstep = gridDim.x * nwaves;
-    // words of group g as the wave loads them: word t = lane + 64 i of the group's 64 x wpr
-    // (lanes and words beyond the batch's end read as zeros)
-    auto fetch = [&](uint32_t g, uint32_t (&dst)[NW]) {
-        const uint64_t first = (uint64_t)g * 64u * wpr;
-        const uint32_t *gw = rd.words + first;
-        const uint32_t have = (uint32_t)min((uint64_t)64u * wpr, n_words - first);
-        uint32_t ln = lane;
-        asm volatile("" : "+v"(ln));              // (or the 64-bit addresses of all NW words are computed once in front of the loop, and spilled)
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            const uint32_t t = ln + 64u * (uint32_t)i;
-            dst[i] = t < have ? gw[t] : 0u;
-        }
-    };
-    uint32_t pf[NW];
-    uint32_t g = blockIdx.x * nwaves + wave;
-    if (g < n_groups) fetch(g, pf);
-    for (; g < n_groups; g += gstep) {
-        const uint64_t r0 = (uint64_t)g * 64u;
-        const uint32_t nr = (uint32_t)min((uint64_t)64u, rd.n_reads - r0);
-        const bool active = lane < nr;
-#pragma unroll
-        for (int i = 0; i < NW; ++i)
-            if ((uint32_t)i < wpr) wl[lane + 64u * (uint32_t)i] = pf[i];
-        if (lane < 4u) { wl[64u * wpr + lane] = 0u; rcl[64u * wpr + lane] = 0u; }
-        // the next group's words are requested now; they are waited for in front of the first flush (below), not at the top of the
-        // next round, where the wait would also cover this round's record stores
-        const bool more = g + gstep < n_groups;
-        if (more) fetch(g + gstep, pf);
-        bool pf_waited = !more;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        {
-            // every lane reverses and complements its own read once: the 16 wpr base slots of its words turned round (word order and
-            // the bases inside each word), complemented, and the 16 wpr - L slots of padding that came to the front shifted out.  A
-            // reversed run's bases are then read from this image exactly as a forward run's are read from the words.
-            const uint32_t sh = 2u * (16u * wpr - L);                  // < 32
-            uint32_t prev = ~skm_rev2_32(wl[lane * wpr + wpr - 1u]);
-            for (uint32_t t = 0; t < wpr; ++t) {
-                const uint32_t next = t + 1u < wpr ? ~skm_rev2_32(wl[lane * wpr + wpr - 2u - t]) : 0u;
-                rcl[lane * wpr + t] = __builtin_amdgcn_alignbit(next, prev, sh);
-                prev = next;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        // a finished run as records (a run of more than ncap k-mers is cut)
-        auto emit_run = [&](uint32_t v, uint32_t r, uint32_t j, uint32_t left) {
-            uint32_t coarse, fine;
-            skm_bucket_of(v, sg.C1, sg.fbits, coarse, fine);
-            uint64_t pos = (sg.read_base + r0 + r) * sg.stride + j;
-            const uint32_t rev = v & 1u;
-            const uint32_t *src = rev ? rcl : wl;
-            uint32_t bidx = r * wpr * 16u + j;                        // the piece's first base in the read (in wl)
-            while (left) {
-                const uint32_t n = min(left, (uint32_t)sg.ncap);
-                // (a reversed piece: its n + k - 1 bases end at base L - j' of the reverse complement, j' its first base in the read)
-                const uint32_t from = rev ? 2u * r * wpr * 16u + L - bidx - (n + (uint32_t)sg.k - 1u) : bidx;
-                uint64_t bw[3];
-#pragma unroll
-                for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? skm_bases32(src, from + 32u * t) : 0ull;
-                const uint64_t hdr = skm_header(pos, n, fine, rev);
-                const uint32_t p = atomicAdd(&cur[coarse], 1u);
-                if (p < sg.cap1) {
-                    if (sg.compact) {                                 // one aligned 16-byte store: bases, n and the fine bucket (no position)
-                        typedef uint64_t u64x2a __attribute__((ext_vector_type(2), aligned(16)));
-                        *(u64x2a *)(my_seg + coarse * cstride + p * 2u) = u64x2a{bw[0], skm_c_pack1(bw[1], n, fine, rev)};
-                    } else {
-                        skm_store_record_wide(my_seg + coarse * cstride + p * (uint32_t)sg.recw, hdr, bw, sg.nbw);
-                    }
-                }
-                else skm_loose_push(sg, hdr, bw);
-                n_rec += 1;
-                left -= n; pos += n; bidx += n;
-            }
-        };
-        uint32_t n_ent = 0;
-        // an entry: the run's minimizer | (lane | first k-mer << 6 | the k-mer behind its last << 18) << 32
-        auto append = [&](unsigned long long bal, uint32_t v, uint32_t lane_start, uint32_t end) -> bool {
-            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, n_ent));
-            if (slot >= SKM_LANE_CAP) return false;                   // (a wave of reads that change minimizer at nearly every k-mer)
-            ent[slot] = (unsigned long long)v | ((unsigned long long)(lane_start | (end << 18)) << 32);
-            return true;
-        };
-        auto flush = [&]() {
-            if (!pf_waited) {
-#pragma unroll
-                for (int i = 0; i < NW; ++i) asm volatile("" : "+v"(pf[i]));          // the prefetched words have arrived from here on
-                pf_waited = true;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t n = min(n_ent, SKM_LANE_CAP);
-            for (uint32_t e = lane; e < n; e += 64u) {
-                const unsigned long long en = ent[e];
-                const uint32_t hi = (uint32_t)(en >> 32), first = (hi >> 6) & 4095u;
-                emit_run((uint32_t)en, hi & 63u, first, (hi >> 18) - first);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            n_ent = 0;
-        };
-        uint32_t Sa[B], Sb[B];
-#pragma unroll
-        for (int j = 0; j < B; ++j) { Sa[j] = 0xffffffffu; Sb[j] = 0xffffffffu; }
-        uint32_t prev_v = 0, start_prev = 0;
-        const uint32_t rbase = lane * wpr;
-        uint32_t since = 0;
-        for (uint32_t b = 0; b < nblocks; b += (C == 2 ? 2u : 1u)) {
-            skm_lane_block<C>(wl, rbase, lane, b, npos, nk, Sa, Sb, prev_v, start_prev, n_ent, append);
-            if (C == 2 && b + 1u < nblocks) skm_lane_block<C>(wl, rbase, lane, b + 1u, npos, nk, Sb, Sa, prev_v, start_prev, n_ent, append);
-            since += (C == 2 ? 2u : 1u);
-            // (the last block's runs leave with the final ones; a list that is filling up is flushed whatever the count says)
-            if ((since >= flush_blocks || n_ent + 192u > SKM_LANE_CAP) && n_ent && b + (C == 2 ? 2u : 1u) < nblocks) { flush(); since = 0; }
-        }
-        // the run every read ends in (room for all 64: the list is emptied first if need be)
-        if (n_ent + 64u > SKM_LANE_CAP) flush();
-        {
-            const unsigned long long bal = __ballot(active);
-            if (active) (void)append(bal, prev_v, start_prev, nk);
-            n_ent += (uint32_t)__popcll(bal);
-        }
-        flush();
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < sg.C1; c += SKM_LANE_THREADS) sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x)] = min(cur[c], sg.cap1);
-    n_rec = wave_sum_u64(n_rec);
-    if ((threadIdx.x & 63u) == 0 && n_rec) atomicAdd(&sg.ctr[SKM_CTR_RECORDS], (unsigned long long)n_rec);
-}
-
-// ---- S2 ------------------------------------------------------------------------------------------------
-#define SKM_THREADS2 512
-#define SKM_MAX_F2 4096u          // fine buckets per coarse bucket (12 bits of a k-mer's bucket id in S1; 16 in a record header)
-// COMPACT: 16-byte records (kv_skm_device.h: the fine bucket sits in the second word; one 16-byte load and store each)
-template <bool COMPACT>
-__global__ __launch_bounds__(SKM_THREADS2) void k_skm_split(SkmGeom sg)
-{
-    __shared__ uint32_t cur[SKM_MAX_F2];
-    __shared__ uint32_t spre[769];                    // record prefix over the coarse segments this workgroup drains
-    const uint32_t c = blockIdx.y;
-    for (uint32_t f = threadIdx.x; f < sg.F2; f += SKM_THREADS2) cur[f] = 0;
-    // segments seg = blockIdx.x, blockIdx.x + nwg2, ...: their records are enumerated flat, so every thread has work
-    const uint32_t nmine = (skm_seg1_count(sg) - blockIdx.x + sg.nwg2 - 1) / sg.nwg2;       // <= 768
-    for (uint32_t i = threadIdx.x; i < nmine; i += SKM_THREADS2) spre[i + 1] = sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x + i * sg.nwg2)];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (uint32_t i = 0; i < nmine; ++i) { const uint32_t n = spre[i + 1]; spre[i] = acc; acc += n; }
-        spre[nmine] = acc;
-    }
-    __syncthreads();
-    const uint32_t total = spre[nmine];
-    const int recw = COMPACT ? 2 : sg.recw;
-    for (uint32_t i = threadIdx.x; i < total; i += SKM_THREADS2) {
-        const uint32_t si = skm_search(spre, nmine, i);
-        const uint32_t seg = blockIdx.x + si * sg.nwg2;
-        const uint64_t *rec = sg.seg1 + (skm_seg1_first(sg, skm_seg1_slot(sg, c, seg)) + (i - spre[si])) * (uint64_t)recw;
-        if (COMPACT) {
-            typedef uint64_t u64x2a __attribute__((ext_vector_type(2), aligned(16)));
-            const u64x2a both = *(const u64x2a *)rec;
-            const uint32_t fine = skm_c_fine(both.y);
-            const uint32_t p = atomicAdd(&cur[fine], 1u);
-            if (p < sg.cap2) {
-                *(u64x2a *)(sg.seg2 + ((((uint64_t)c * sg.F2 + fine) * sg.nwg2 + blockIdx.x) * sg.cap2 + p) * 2ull) = both;
-            } else {                                         // (leaves in the loose list's classic form, position unknown)
-                uint64_t lw[3] = {both.x, skm_c_b1(both.y), 0ull};
-                skm_loose_push(sg, skm_header(0ull, skm_c_n(both.y), fine, skm_c_rev(both.y)), lw);
-            }
-            continue;
-        }
-        const uint64_t hdr = rec[0];
-        uint64_t bw[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? rec[1 + t] : 0ull;
-        const uint32_t fine = skm_hdr_fine(hdr);
-        const uint32_t p = atomicAdd(&cur[fine], 1u);
-        if (p < sg.cap2)
-            skm_store_record(sg.seg2 + ((((uint64_t)c * sg.F2 + fine) * sg.nwg2 + blockIdx.x) * sg.cap2 + p) * (uint64_t)recw, hdr, bw, sg.nbw);
-        else skm_loose_push(sg, hdr, bw);
-    }
-    __syncthreads();
-    for (uint32_t f = threadIdx.x; f < sg.F2; f += SKM_THREADS2)
-        sg.cnt2[((uint64_t)c * sg.F2 + f) * sg.nwg2 + blockIdx.x] = min(cur[f], sg.cap2);
-}
-
-// S2 with the scatter sorted in LDS first.  The plain kernel above stores every record where it falls: 64 lanes, 64
-// different cache lines per store instruction, 8-byte pieces of 24-byte records that straddle 32-byte sectors -- PMC:
-// 2.5 GB written for 1.36 GB of records, 68 % of the wave cycles stalled on the memory pipe.  Here a workgroup takes
-// SKM_S2_CHUNK records at a time, ranks them by fine bucket (LDS atomics: rank inside the chunk's share of the bucket),
-// lays them out bucket by bucket in LDS and copies that image out with consecutive lanes on consecutive words: a bucket's
-// records of one chunk leave as one contiguous run.  Used while a chunk holds at least ~2 records per bucket.
-#define SKM_S2_CHUNK 2048u
-#define SKM_S2_MAXF 1024u
-template <int RECW>
-__global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
-{
-    __shared__ uint32_t cur[SKM_S2_MAXF];            // records this workgroup has stored per fine bucket
-    __shared__ uint32_t hist[SKM_S2_MAXF];           // the chunk's records per bucket, then slot of sorted position 0 minus that position
-    __shared__ uint32_t off[SKM_S2_MAXF];            // sorted position of the bucket's first record of the chunk
-    __shared__ uint32_t spre[769];
-    __shared__ uint32_t wsum[SKM_THREADS2 / 64];
-    extern __shared__ __attribute__((aligned(16))) uint64_t img[];     // [SKM_S2_CHUNK][RECW]
-    const uint32_t c = blockIdx.y, F2 = sg.F2;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t f = threadIdx.x; f < F2; f += SKM_THREADS2) { cur[f] = 0; hist[f] = 0; }
-    const uint32_t nmine = (skm_seg1_count(sg) - blockIdx.x + sg.nwg2 - 1) / sg.nwg2;       // <= 768
-    for (uint32_t i = threadIdx.x; i < nmine; i += SKM_THREADS2) spre[i + 1] = sg.cnt1[skm_seg1_slot(sg, c, blockIdx.x + i * sg.nwg2)];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (uint32_t i = 0; i < nmine; ++i) { const uint32_t n = spre[i + 1]; spre[i] = acc; acc += n; }
-        spre[nmine] = acc;
-    }
-    __syncthreads();
-    const uint32_t total = spre[nmine];
-    constexpr uint32_t PER = SKM_S2_CHUNK / SKM_THREADS2;             // records per thread and chunk
-    const uint32_t fper = (F2 + SKM_THREADS2 - 1) / SKM_THREADS2;     // buckets per thread in the scan (1 or 2)
-    uint64_t *const out = sg.seg2 + ((uint64_t)c * F2 * sg.nwg2 + blockIdx.x) * sg.cap2 * RECW;      // + fine * nwg2 * cap2 * RECW
-    const uint64_t fstride = (uint64_t)sg.nwg2 * sg.cap2 * RECW;
-    // the records of the NEXT chunk are requested before this chunk is ranked, laid out and stored: a workgroup's chunk used to begin
-    // with a round trip to HBM that nothing covered (two workgroups per CU, five barriers per chunk)
-    uint64_t nh[PER], n0[PER], n1[PER], n2[PER];
-    auto request = [&](uint32_t c0) {
-        const uint32_t n = c0 < total ? min(SKM_S2_CHUNK, total - c0) : 0u;
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r) {
-            const uint32_t i = r * SKM_THREADS2 + threadIdx.x;
-            nh[r] = 0; n0[r] = 0; n1[r] = 0; n2[r] = 0;
-            if (i < n) {
-                const uint32_t gi = c0 + i, si = skm_search(spre, nmine, gi);
-                const uint32_t seg = blockIdx.x + si * sg.nwg2;
-                const uint64_t *rec = sg.seg1 + (skm_seg1_first(sg, skm_seg1_slot(sg, c, seg)) + (gi - spre[si])) * (uint64_t)RECW;
-                if (RECW == 2) {                                      // compact: the word that says the bucket is the second one
-                    typedef uint64_t u64x2a __attribute__((ext_vector_type(2), aligned(16)));
-                    const u64x2a both = *(const u64x2a *)rec;
-                    n0[r] = both.x; nh[r] = both.y;
-                } else {
-                    nh[r] = rec[0]; n0[r] = rec[1]; n1[r] = rec[2];
-                    if (RECW == 4) n2[r] = rec[3];
-                }
-            }
-        }
-    };
-    request(0);
-    for (uint32_t c0 = 0; c0 < total; c0 += SKM_S2_CHUNK) {
-        const uint32_t n = min(SKM_S2_CHUNK, total - c0);
-        uint64_t hdr[PER], w0[PER], w1[PER], w2[PER];
-        uint32_t rank[PER];
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r) { hdr[r] = nh[r]; w0[r] = n0[r]; w1[r] = n1[r]; w2[r] = n2[r]; rank[r] = 0; }
-        request(c0 + SKM_S2_CHUNK);
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r)
-            if (r * SKM_THREADS2 + threadIdx.x < n) rank[r] = atomicAdd(&hist[RECW == 2 ? skm_c_fine(hdr[r]) : skm_hdr_fine(hdr[r])], 1u);
-        __syncthreads();
-        // exclusive scan of the chunk's histogram; the bucket's run then starts at slot cur[f] of the private segment
-        {
-            uint32_t h[2] = {0, 0}, sum = 0;
-            for (uint32_t j = 0; j < fper; ++j) {
-                const uint32_t f = threadIdx.x * fper + j;
-                h[j] = f < F2 ? hist[f] : 0u;
-                sum += h[j];
-            }
-            uint32_t incl = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            if (lane == 63) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t before = incl - sum;
-            for (uint32_t wv = 0; wv < wave; ++wv) before += wsum[wv];
-            for (uint32_t j = 0; j < fper; ++j) {
-                const uint32_t f = threadIdx.x * fper + j;
-                if (f < F2) {
-                    off[f] = before;
-                    const uint32_t at = cur[f];
-                    cur[f] = at + h[j];
-                    hist[f] = at - before;              // slot = sorted position + this (mod 2^32)
-                    before += h[j];
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < PER; ++r) {
-            if (r * SKM_THREADS2 + threadIdx.x < n) {
-                uint64_t *dst = img + (uint64_t)(off[RECW == 2 ? skm_c_fine(hdr[r]) : skm_hdr_fine(hdr[r])] + rank[r]) * RECW;
-                if (RECW == 2) { dst[0] = w0[r]; dst[1] = hdr[r]; }
-                else { dst[0] = hdr[r]; dst[1] = w0[r]; dst[2] = w1[r]; }
-                if (RECW == 4) dst[3] = w2[r];
-            }
-        }
-        __syncthreads();
-        for (uint32_t wd = threadIdx.x; wd < n * RECW; wd += SKM_THREADS2) {
-            const uint32_t q = wd / RECW, part = wd - q * RECW;
-            const uint64_t h0 = img[(uint64_t)q * RECW + (RECW == 2 ? 1 : 0)];
-            const uint32_t f = RECW == 2 ? skm_c_fine(h0) : skm_hdr_fine(h0);
-            const uint32_t slot = q + hist[f];
-            if (slot < sg.cap2) out[(uint64_t)f * fstride + (uint64_t)slot * RECW + part] = img[wd];
-            else if (part == 0) {
-                if (RECW == 2) {                                      // a compact record leaves in the loose list's (classic) form, position unknown
-                    uint64_t bw[3] = {img[(uint64_t)q * RECW], skm_c_b1(h0), 0ull};
-                    skm_loose_push(sg, skm_header(0ull, skm_c_n(h0), f, skm_c_rev(h0)), bw);
-                } else {
-                    uint64_t bw[3] = {img[(uint64_t)q * RECW + 1], img[(uint64_t)q * RECW + 2], RECW == 4 ? img[(uint64_t)q * RECW + 3] : 0ull};
-                    skm_loose_push(sg, h0, bw);
-                }
-            }
-        }
-        __syncthreads();
-        for (uint32_t f = threadIdx.x; f < F2; f += SKM_THREADS2) hist[f] = 0;
-        // (the next chunk's atomics on hist come after its loads and after the barrier below at the latest: the loop's
-        // first barrier orders them behind this reset only if every thread passes it, so reset before a barrier)
-        __syncthreads();
-    }
-    for (uint32_t f = threadIdx.x; f < F2; f += SKM_THREADS2)
-        sg.cnt2[((uint64_t)c * F2 + f) * sg.nwg2 + blockIdx.x] = min(cur[f], sg.cap2);
-}
-
-// ---- LDS combining table -------------------------------------------------------------------------------
-// the step from a slot to the next one tried: an odd number taken from the key's hash (double hashing: two keys that meet in one slot
-// part ways at once, no clusters -- the wave waits for the lane with the longest chain)
-// (k_skm_count 3.23 -> 3.04 ms per sample of config 2 against linear probing, a step of 1)
-#define SKM_STEP_MASK 62u
-#define SKM_PROBE_STEP(h) ((((h) >> 20) & SKM_STEP_MASK) | 1u)
-// slot a hash starts at / the slot `step` further on, for tables of 2^n slots and of any other size (3072: the count's instances that
-// share their LDS with a table of records) -- there the top bits of the hash pick the slot, so the step comes from the low ones
-template <int TS>
-__device__ __forceinline__ uint32_t skm_slot0(uint32_t sh) { return (TS & (TS - 1)) == 0 ? sh & (uint32_t)(TS - 1) : __umulhi(sh, (uint32_t)TS); }
-template <int TS>
-__device__ __forceinline__ uint32_t skm_step_of(uint32_t sh) { return (TS & (TS - 1)) == 0 ? SKM_PROBE_STEP(sh) : (((sh >> 2) & 62u) | 1u); }
-template <int TS>
-__device__ __forceinline__ uint32_t skm_slot_next(uint32_t slot, uint32_t step)
-{
-    if ((TS & (TS - 1)) == 0) return (slot + step) & (uint32_t)(TS - 1);
-    slot += step;
-    return slot >= (uint32_t)TS ? slot - (uint32_t)TS : slot;
-}
-template <int KW, int TS>
-struct SkmTable {
-    unsigned long long key[KW][TS];
-};
-
-template <int KW, int TS>
-__device__ __forceinline__ void skm_table_clear(SkmTable<KW, TS> &tb)
-{
-    for (uint32_t i = threadIdx.x; i < TS; i += blockDim.x) {
-        tb.key[0][i] = SKM_EMPTY;
-        if (KW == 2) tb.key[KW - 1][i] = SKM_EMPTY;
-    }
-}
-
-// slot of the key, claiming a free slot if it is new; -1 when SKM_MAXPROBE slots are all taken by other keys.  With
-// two key words a slot is identified word by word: whoever sets word 0 (or finds it equal) goes on to set or
-// compare word 1, and moves to the next slot if another k-mer with the same first 32 bases got there first.
-template <int KW, int TS>
-__device__ __forceinline__ int skm_table_insert(SkmTable<KW, TS> &tb, const SkmKey<KW> &c)
-{
-    const uint32_t sh = skm_slot_hash<KW>(c);
-    uint32_t slot = skm_slot0<TS>(sh);
-    const uint32_t step = skm_step_of<TS>(sh);
-    for (int probe = 0; probe < SKM_MAXPROBE; ++probe) {
-        // (reading the slot first and swapping only into an empty one was measured 5 % slower: the read does not save
-        // the swap's round trip, it adds one for every new key)
-        const unsigned long long old0 = atomicCAS(&tb.key[0][slot], SKM_EMPTY, (unsigned long long)c.w[0]);
-        if (old0 == SKM_EMPTY || old0 == c.w[0]) {
-            if (KW == 1) return (int)slot;
-            const unsigned long long old1 = atomicCAS(&tb.key[KW - 1][slot], SKM_EMPTY, (unsigned long long)c.w[KW - 1]);
-            if (old1 == SKM_EMPTY || old1 == c.w[KW - 1]) return (int)slot;
-        }
-        slot = skm_slot_next<TS>(slot, step);
-    }
-    return -1;
-}
-
-template <int KW, int TS>
-__device__ __forceinline__ int skm_table_find(const SkmTable<KW, TS> &tb, const SkmKey<KW> &c)
-{
-    const uint32_t sh = skm_slot_hash<KW>(c);
-    uint32_t slot = skm_slot0<TS>(sh);
-    const uint32_t step = skm_step_of<TS>(sh);
-    for (int probe = 0; probe < SKM_MAXPROBE; ++probe) {
-        const unsigned long long k0 = tb.key[0][slot];
-        if (k0 == SKM_EMPTY) return -1;
-        if (k0 == c.w[0] && (KW == 1 || tb.key[KW - 1][slot] == c.w[KW - 1])) return (int)slot;
-        slot = skm_slot_next<TS>(slot, step);
-    }
-    return -1;
-}
-
-// count side of one distinct k-mer seen `count` times: filter, then T weighted items through `emit(table, bin, weight)`
-template <typename Emit>
-__device__ __forceinline__ uint32_t skm_count_kmer(uint64_t h, uint32_t count, const SketchDev *__restrict__ sk,
-                                                   const SketchDev *__restrict__ mask, const ConsumeFilter &f, int T, Emit emit)
-{
-    if (!consume_filter_pass(f, mask, h)) return 0;
-    uint32_t left = min(count, 255u);                  // no counter holds more than 255
-    // (tried: lane l starting with table l mod 4, so that one emit instruction spreads over the cursors of all tables instead
-    // of 64 lanes sharing the ~20 cursors of one -- 3.6 -> 4.2 ms: what costs is the number of distinct segments, i.e. cache
-    // lines, one store instruction touches, not the same-address LDS atomics; more coarse buckets cost the same way)
-    while (left) {
-        const uint32_t wgt = min(left, BIN_W_MAX);
-#pragma unroll
-        for (int t = 0; t < BIN_MAX_T; ++t)
-            if (t < T) emit(t, fastmod(h, sk->size[t], sk->magic[t]), wgt);
-        left -= wgt;
-    }
-    return count;
-}
-
-// every wave walks its share of the table and hands the occupied slots to `body` 64 at a time (all lanes busy):
-// occupied slots are queued in LDS and drained whenever a full wave of them is ready
-template <int TS, typename Body>
-__device__ __forceinline__ void skm_for_occupied(const unsigned long long *key0, uint16_t *queue_all, uint32_t queue_stride, Body body, const uint32_t *skip = nullptr)
-{
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
-    uint16_t *queue = queue_all + wave * queue_stride;               // >= 128 entries; wave-private, ordered by the fences below
-    const uint32_t per_wave = TS / nwaves;
-    const uint32_t s_end = (wave + 1) * per_wave;
-    uint32_t qn = 0;                                    // < 64 between iterations
-    for (uint32_t s0 = wave * per_wave;; s0 += 64) {
-        const bool last = s0 >= s_end;
-        if (!last) {
-            const uint32_t slot = s0 + lane;
-            const bool occ = key0[slot] != SKM_EMPTY && !(skip && ((skip[slot >> 5] >> (slot & 31u)) & 1u));      // skip: a bit per slot
-            const unsigned long long ballot = __ballot(occ);
-            if (occ) __hip_atomic_store(&queue[qn + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))], (uint16_t)slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            qn += (uint32_t)__popcll(ballot);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (qn >= 64 || (last && qn > 0)) {
-            const uint32_t take = min(qn, 64u);
-            qn -= take;
-            if (lane < take) body((uint32_t)__hip_atomic_load(&queue[qn + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (last) break;
-    }
-}
-
-// ---- balanced walk over the k-mer occurrences of a fine bucket ------------------------------------------------
-// Records hold 1..ncap k-mers, so a thread per record would leave most lanes waiting for the longest one, and a
-// thread per occurrence cuts every k-mer out of its record from scratch (round 2: 115 VALU instructions per
-// occurrence, the largest item of the count kernel).  The walk therefore deals UNITS: SKM_UNIT consecutive k-mers
-// of one record.  Each wave takes 64 records (one per lane, in registers), numbers their units with a prefix sum and
-// walks them 64 at a time: lane p of block t0 handles unit t0 + p, finds the record that owns it from a bit mask of
-// record starts (one LDS word pair per block, popcounts), fetches that record's words from the owning lane with
-// ds_bpermute, cuts the unit's first k-mer out, takes its reverse complement once and ROLLS both strands through
-// the unit's other k-mers (two shifts each).  Records average ~9 k-mers: units of 4 are 85 % full.
-#define SKM_UNIT 4
-
-__device__ __forceinline__ uint64_t skm_shfl64(uint64_t v, uint32_t src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src);
-    return (uint64_t)lo | ((uint64_t)hi << 32);
-}
-
-// bases j .. j + k - 1 of a record's base words
-template <int KW>
-__device__ __forceinline__ SkmKey<KW> skm_kmer_at(uint64_t b0, uint64_t b1, uint64_t b2, uint32_t j, int k)
-{
-    return skm_kmer_of<KW>(b0, b1, b2, j, k);
-}
-
-// occurrences that found no room in the LDS table leave as one-k-mer records (either strand of the k-mer): one atomic per wave
-template <int KW, bool WANT_POS>
-__device__ __forceinline__ void skm_walk_loose(const SkmGeom &sg, bool alone, const SkmKey<KW> &kmer, uint64_t hdr, uint32_t owner,
-                                               uint64_t pos0, uint32_t j0, uint32_t u, uint32_t lane, int recw)
-{
-    const unsigned long long need = __ballot(alone);
-    if (!need) return;
-    // (the count pass does not fetch the records' headers for the walk; here -- a wave in a few hundred -- it does,
-    // so that the loose record carries the occurrence's real position: a scan that goes by the count pass's
-    // distinct list evaluates these records as they are)
-    // (WANT_POS: pos0 is this occurrence's position already; else it is derived here from the owner's header, orientation included)
-    const uint64_t posu = WANT_POS ? pos0 : skm_hdr_pos_of(skm_shfl64(hdr, owner), j0 + u);
-    unsigned long long first = 0;
-    if (lane == 0) first = atomicAdd(&sg.ctr[SKM_CTR_LOOSE], (unsigned long long)__popcll(need));
-    first = skm_shfl64(first, 0);
-    if (alone) {
-        const unsigned long long idx = first + (unsigned long long)__popcll(need & ((1ull << lane) - 1ull));
-        uint64_t one[3] = {kmer.w[0], KW == 2 ? kmer.w[KW - 1] : 0ull, 0ull};
-        if (idx < sg.loose_cap) skm_store_record(sg.loose + idx * (uint64_t)recw, skm_header(posu, 1u, 0u), one, sg.nbw);
-        else sg.ctr[SKM_CTR_FAIL] = 1;
-    }
-}
-
-// body(k-mer, position of the occurrence) -> true if the occurrence could not be combined and must travel alone through the
-// loose list; WANT_POS = false skips fetching the header (count pass).  The records are oriented: a k-mer's key is the k-mer as
-// the record holds it.
-template <int KW, bool WANT_POS, int FK = 0, bool COMPACT = false, typename Body>
-__device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, uint32_t *sbits_all, Body body)
-{
-    static_assert(!COMPACT || (KW == 1 && !WANT_POS), "compact records: one-word keys, no positions");
-    constexpr uint32_t G = SKM_UNIT;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    uint32_t *sbits = sbits_all + wave * sg.sbw;       // sbw words: 64 records x ncap k-mers (units need fewer), + the word a 64-bit read may straddle into
-    const int k = FK ? FK : sg.k, recw = COMPACT ? 2 : (FK ? 1 + KW + 1 : sg.recw);        // FK: k (and with it the record width) known when compiled
-    // a compact record (16 bytes, one load) is taken apart into what the code below knows: a header without a position, two base words
-    auto load = [&](const uint64_t *rec, uint64_t &hdr, uint64_t &b0, uint64_t &b1, uint64_t &b2) {
-        if (COMPACT) {
-            typedef uint64_t u64x2a __attribute__((ext_vector_type(2), aligned(16)));
-            const u64x2a both = *(const u64x2a *)rec;
-            b0 = both.x; b1 = skm_c_b1(both.y); hdr = skm_header(0ull, skm_c_n(both.y), 0u, skm_c_rev(both.y));
-        } else {
-            hdr = rec[0]; b0 = rec[1]; b1 = rec[2];
-            if (KW == 2) b2 = rec[3];
-        }
-    };
-    // Which records a wave takes does not depend on how full the bucket's segments are: pair p = wave, wave + nwaves, ...
-    // is records [64 g, 64 g + 64) of segment s = p mod nwg2, g = p / nwg2.  The records are therefore requested together
-    // with the segment counts (which only mask them afterwards) instead of behind them, and the same addresses of the
-    const uint32_t *cnt2 = sg.cnt2 + (uint64_t)b * sg.nwg2;
-    uint32_t p = wave;
-    uint32_t g = p / sg.nwg2, sgm = p - g * sg.nwg2;
-    uint64_t hdr = 0, b0 = 0, b1 = 0, b2 = 0;
-    {
-        const uint32_t at = min(g * 64u + lane, sg.cap2 - 1u);
-        const uint64_t *rec = sg.seg2 + (((uint64_t)b * sg.nwg2 + sgm) * sg.cap2 + at) * (uint64_t)recw;
-        load(rec, hdr, b0, b1, b2);
-    }
-    uint32_t maxc = 0;
-    for (uint32_t s2 = 0; s2 < sg.nwg2; ++s2) maxc = max(maxc, cnt2[s2]);
-    for (;;) {
-        if (g * 64u >= maxc) break;
-        const uint32_t NR = cnt2[sgm], i = g * 64u + lane;      // (the name the code below knows the bound by)
-        const uint32_t nk = i < NR ? skm_hdr_n(hdr) : 0u;
-        const uint32_t nu = (nk + G - 1u) / G;          // units of this record
-        uint32_t incl = nu;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        const uint32_t total = __shfl(incl, 63), excl = incl - nu;
-        const uint32_t exnk = excl | (nk << 16);        // < 64 * ncap units: 16 bits are plenty
-        const uint32_t nwords = (total >> 5) + 2u;
-        for (uint32_t wd = lane; wd < nwords; wd += 64) sbits[wd] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (nu) atomicOr(&sbits[excl >> 5], 1u << (excl & 31));
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t before = 0;                            // records that start in front of this block
-        for (uint32_t t0 = 0; t0 < total; t0 += 64) {
-            // (relaxed wave-scope loads: a volatile access through the generic pointer became a system-scope FLAT load
-            // with its own s_waitcnt vmcnt(0), two in a row per block)
-            const uint64_t starts = (uint64_t)__hip_atomic_load(&sbits[t0 >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) |
-                                    ((uint64_t)__hip_atomic_load(&sbits[(t0 >> 5) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) << 32);
-            const uint32_t t = t0 + lane;
-            const uint32_t owner = (before + (uint32_t)__popcll(starts & ((2ull << lane) - 1ull)) - 1u) & 63u;
-            before += (uint32_t)__popcll(starts);
-            const uint32_t oe = (uint32_t)__shfl((int)exnk, (int)owner);
-            const uint64_t o0 = skm_shfl64(b0, owner), o1 = skm_shfl64(b1, owner);
-            const uint64_t o2 = KW == 2 ? skm_shfl64(b2, owner) : 0ull;
-            const uint64_t oh = WANT_POS ? skm_shfl64(hdr, owner) : 0ull;
-            const uint32_t j0 = t < total ? (t - (oe & 0xffffu)) * G : 0u;
-            const uint32_t cnt = t < total ? min(G, (oe >> 16) - j0) : 0u;     // k-mers of this unit: 1..G (0: no unit)
-            SkmKey<KW> fw = skm_kmer_of<KW>(o0, o1, o2, j0, k);
-            const uint32_t tail = (uint32_t)skm_window64(o0, o1, o2, j0 + (uint32_t)k);   // the bases that enter k-mers 1 .. G - 1
-            // read position of the unit's first k-mer and the step to the next: a reversed record's k-mer j stands at pos + n - 1 - j
-            uint64_t pos0 = 0;
-            int step = 1;
-            if (WANT_POS) {
-                const bool rv = skm_hdr_rev(oh) != 0u;
-                pos0 = skm_hdr_pos(oh) + (rv ? skm_hdr_n(oh) - 1u - j0 : j0);
-                step = rv ? -1 : 1;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < G; ++u) {
-                if (u) { SkmKey<KW> other = fw; skm_roll<KW>(fw, other, (tail >> (2u * (u - 1u))) & 3u, k); }      // (the other strand is dead code here)
-                const uint64_t posu = pos0 + (uint64_t)(int64_t)(step * (int)u);
-                bool alone = false;
-                if (u < cnt) alone = body(fw, posu);
-                skm_walk_loose<KW, WANT_POS>(sg, alone, fw, hdr, owner, posu, j0, u, lane, sg.lrecw);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                // the next group clears the mask
-        p += nwaves;
-        g = p / sg.nwg2; sgm = p - g * sg.nwg2;
-        if (g * 64u >= maxc) break;
-        if (g * 64u + lane < cnt2[sgm]) {
-            const uint64_t *rec = sg.seg2 + (((uint64_t)b * sg.nwg2 + sgm) * sg.cap2 + g * 64u + lane) * (uint64_t)recw;
-            load(rec, hdr, b0, b1, b2);
-        }
-    }
-}
-
-// ---- S3: count ------------------------------------------------------------------------------------------
-// dynamic LDS of the bucket kernels: [256] byte -> ASCII table, [T * C] bin cursors (count only), then the per-wave
-// scratch: record-start bits of the walk, reused as the queue of occupied slots
-__host__ __device__ inline uint32_t skm_wave_scratch_words(uint32_t sbw) { return sbw > 64u ? sbw : 64u; }
-
-// FK: the instance for the k everybody runs (kevlar's default, 31; the host checks k and the record width): shifts, masks and the
-// murmur tail become constants -- 3 % of the kernel.  FK = 0 reads k from the geometry.
-// waves per SIMD the two-word-key instances are compiled for (6: three workgroups per CU at 80 VGPRs, 13-19 of them spilled; 4: two
-// workgroups at up to 128 VGPRs, nothing spilled)
-#define SKM_K2_WAVES 6
-// The instances for a fixed k (FK != 0) take the two murmurs from the product tables (skm_key_hash_pl: P1 / P2, 4 KB of
-// dynamic LDS in place of the 1 KB ASCII table) and keep their occurrence counters as 16-bit halves of a word -- that is where the
-// 3 KB come from with three workgroups on a CU; the host launches them only for buckets that cannot hold 65536 occurrences
-// (skm_count_pl_fits), the instances with k at run time count in 32 bits.
-// slots of the k = 51 instances' table: their buckets are sized for 2048 slots (the scan kernels' tables), the count's own table may be
-// roomier -- fewer occurrences on the loose list, shorter probe chains -- as long as three workgroups fit a CU (2560: 52.7 KB each)
-#define SKM_TS51 2560
-// (k = 31: 4608 slots measured 1 % faster than 4096 -- and let a bucket's distinct list outgrow what the list scan takes, SKM_LIST_MAX:
-// scratch/fuzz_list.py seed 702, trial 149 lost 8 % of its hits; the table stays at 4096, the assertion below holds every instance to it)
-#define SKM_TS31 4096
-// entries of one bucket the scan from the distinct list takes (k_skm_novel_list): a bucket's list has at most as many entries as the
-// count kernel's LDS table has slots
-#define SKM_LIST_MAX 4096u
-// FORCE_LOOSE: the instances KV_SKM_FORCE_LOOSE runs (sg.force_loose); the others leave its test out of the occurrence loop (0.07 ms per sample)
-template <int KW, int TS, bool FORCE_LOOSE, int FK, bool COMPACT = false>
-__global__ __launch_bounds__(SKM_THREADS3, KW == 2 ? SKM_K2_WAVES : 6) void k_skm_count(SkmGeom sg, const SketchDev *__restrict__ sk,
-                                                           const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
-{
-    static_assert((uint32_t)TS <= SKM_LIST_MAX, "a bucket's distinct list (one entry per occupied slot) must fit what k_skm_novel_list takes");
-    constexpr bool PL = FK != 0;
-    __shared__ SkmTable<KW, TS> tb;
-    __shared__ uint32_t cnt[PL ? TS / 2 : TS];   // occurrences of the key in the same slot (PL: slot s in half s & 1 of word s >> 1)
-    __shared__ uint32_t next_bucket;
-    __shared__ uint32_t abl_cur, abl_b0, abl_prev;      // abundance list: entries appended so far, ... when the bucket began, the bucket
-    __shared__ uint32_t dl_cur, dl_b0;                  // distinct list: the same two
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    const uint32_t ns = (uint32_t)(g.T * g.C);
-    uint32_t *lut = dyn, *cur = dyn + (PL ? 1024 : 256), *scratch = cur + ((ns + 3u) & ~3u);
-    uint64_t *P1 = (uint64_t *)dyn, *P2 = P1 + 256;
-    for (uint32_t s = threadIdx.x; s < ns; s += SKM_THREADS3) cur[s] = 0;
-    if (threadIdx.x < 256) {
-        if (PL) { P1[threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C1); P2[threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C2); }
-        else lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    }
-    const HashParams hp = FK ? make_hash_params(FK, f.hp.hashfam) : f.hp;
-    uint64_t n_added = 0, n_distinct = 0;
-    const uint32_t cap1 = (uint32_t)g.cap1;
-    uint32_t *my_seg = g.gbuf1 + (uint64_t)blockIdx.x * g.cap1;          // + stream * seg_stride: this workgroup's segment of a stream
-    const uint64_t seg_stride = (uint64_t)g.nwgA * g.cap1;
-    auto emit = [&](int t, uint64_t bin, uint32_t wgt) {
-        const uint32_t slice = (uint32_t)(bin >> g.sbits);
-        const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-        const uint32_t sidx = (uint32_t)t * (uint32_t)g.C + c;
-        const uint32_t item = ((slice - c * (uint32_t)g.F) << g.sbits) | ((uint32_t)bin & ((1u << g.sbits) - 1u)) | ((wgt - 1u) << BIN_W_SHIFT);
-        const uint32_t pos = atomicAdd(&cur[sidx], 1u);
-        if (pos < cap1) my_seg[sidx * seg_stride + pos] = item;
-        else spill_item(g, t, bin, wgt);
-    };
-    // the table is emptied as it is read (below), so it is cleared only once; the next bucket's ticket is fetched
-    // while the current bucket is processed
-    skm_table_clear(tb);
-    for (uint32_t i = threadIdx.x; i < (PL ? TS / 2 : TS); i += SKM_THREADS3) cnt[i] = 0;
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt; abl_cur = 0; abl_b0 = 0; abl_prev = 0xffffffffu; dl_cur = 0; dl_b0 = 0; }
-    // where the finished bucket's entries of the abundance list lie (nothing if the workgroup's stretch ran out)
-    auto abl_close = [&]() {
-        if (sg.abl_keys && abl_prev != 0xffffffffu) {
-            const bool fits = abl_cur <= sg.abl_cap_wg;
-            sg.abl_bstart[abl_prev] = blockIdx.x * sg.abl_cap_wg + abl_b0;
-            sg.abl_bcount[abl_prev] = fits ? abl_cur - abl_b0 : 0u;
-        }
-        if (sg.dl_keys && abl_prev != 0xffffffffu) {
-            sg.dl_bstart[abl_prev] = blockIdx.x * sg.dl_cap_wg + dl_b0;
-            sg.dl_bcount[abl_prev] = dl_cur - dl_b0;                // (a stretch that ran out is reported through SKM_CTR_DL_RAN_OUT: the whole list is then dropped)
-        }
-    };
-    for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
-        __syncthreads();
-        const uint32_t b = next_bucket;
-        if (b >= sg.n_buckets) break;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            abl_close();
-            abl_prev = b; abl_b0 = abl_cur; dl_b0 = dl_cur;
-            if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else {
-                const unsigned long long ticket = atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull);
-                next_bucket = (uint32_t)ticket * sg.bpt;     // (a raised flag ends the pass: the caller redoes the batch)
-                // a batch that does not fit the LDS tables (low coverage per batch: nearly every k-mer distinct) is given up
-                // early: once 2 % of the buckets are done, more than 4 % of their k-mers outside the tables raise the flag
-                const unsigned long long done = ticket * sg.bpt;
-                if (done * 50ull >= sg.n_buckets) {
-                    const unsigned long long now = __hip_atomic_load(&sg.ctr[SKM_CTR_LOOSE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[SKM_CTR_LOOSE_S12];
-                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[SKM_CTR_FAIL] = 1;
-                }
-            }
-        }
-        // combine the occurrences of the bucket
-        skm_walk_bucket<KW, false, FK, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
-            // (KV_SKM_FORCE_LOOSE: one key in 64 is treated like a key that found its table full -- every occurrence travels alone;
-            // results stay exact, tests use it to put single k-mers on the loose list of a batch that otherwise fits)
-            const bool forced = FORCE_LOOSE && sg.force_loose && ((c.w[0] * 0x9e3779b97f4a7c15ull) >> 58) == 0;
-            const int slot = skm_cacheable<KW>(c) && !forced ? skm_table_insert(tb, c) : -1;
-            if (slot >= 0) {
-                if (PL) atomicAdd(&cnt[(uint32_t)slot >> 1], 1u << (((uint32_t)slot & 1u) * 16u));
-                else atomicAdd(&cnt[slot], 1u);
-            }
-            return slot < 0;         // table region full (or unstorable key): this occurrence travels alone
-        });
-        __syncthreads();
-        // every distinct k-mer once
-        skm_for_occupied<TS>(tb.key[0], (uint16_t *)scratch, skm_wave_scratch_words(sg.sbw) * 2u, [&](uint32_t slot) {
-            SkmKey<KW> c;
-            c.w[0] = tb.key[0][slot];
-            tb.key[0][slot] = SKM_EMPTY;
-            if (KW == 2) { c.w[KW - 1] = tb.key[KW - 1][slot]; tb.key[KW - 1][slot] = SKM_EMPTY; }
-            uint32_t seen;
-            if (PL) {               // (the other half of the word is another lane's, maybe at this very moment)
-                const uint32_t sh = (slot & 1u) * 16u;
-                seen = (cnt[slot >> 1] >> sh) & 0xffffu;
-                atomicSub(&cnt[slot >> 1], seen << sh);
-            } else {
-                seen = cnt[slot];
-                cnt[slot] = 0;
-            }
-            n_distinct += 1;
-            uint64_t h;
-            if constexpr (PL) h = skm_key_hash_pl<KW, FK>(c, P1, P2);
-            else h = skm_key_hash<KW>(c, lut, hp);
-            // distinct list: key and hash of every k-mer in here (the scan of this batch then neither combines nor hashes again)
-            if (sg.dl_keys) {
-                const unsigned long long here = __ballot(true);
-                const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)here) - 1u;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&dl_cur, (uint32_t)__popcll(here));
-                base = (uint32_t)__shfl((int)base, (int)leader);
-                const uint32_t at = base + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
-                if (at < sg.dl_cap_wg) {
-                    const uint64_t e = (uint64_t)blockIdx.x * sg.dl_cap_wg + at;
-                    sg.dl_keys[e * KW] = c.w[0];
-                    if (KW == 2) sg.dl_keys[e * KW + (KW - 1)] = c.w[KW - 1];
-                    sg.dl_hash[e] = h;
-                }
-            }
-            uint32_t added;
-            if (g.fast4 && !f.use_mask) {
-                // four tables below 2^31 bins: the quotient of h / size from the FP64 pipe (kv_fastmod.h), the remainder in 32 bits --
-                // h - q size lies in [-size, size), so its low word is the remainder or the remainder + 2^32 - size, told apart by bit 31 --
-                // and the items appended with 32-bit index arithmetic: ~95 lane-instructions per k-mer for the 222 of the general form
-                // (64-bit remainders, the sizes fetched from the sketch's descriptor, scalar registers spilled around them)
-                const bool pass = !f.use_band || (h >= f.band_lo && h < f.band_hi);
-                added = pass ? seen : 0u;
-                if (pass) {
-                    const double hd = kv_fastmod_hd(h);
-                    uint32_t bin[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) bin[t] = kv_fastmod32(h, hd, (uint32_t)g.tsize[t], g.tmagic[t]);
-                    uint32_t left = min(seen, 255u);
-                    const uint32_t omask = (1u << g.sbits) - 1u, stride32 = (uint32_t)seg_stride;
-                    while (left) {
-                        const uint32_t wgt = min(left, BIN_W_MAX), wbits = (wgt - 1u) << BIN_W_SHIFT;
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const uint32_t slice = bin[t] >> g.sbits;
-                            const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-                            const uint32_t sidx = (uint32_t)t * (uint32_t)g.C + c;
-                            const uint32_t item = ((slice - c * (uint32_t)g.F) << g.sbits) | (bin[t] & omask) | wbits;
-                            const uint32_t pos = atomicAdd(&cur[sidx], 1u);
-                            if (pos < cap1) my_seg[sidx * stride32 + pos] = item;
-                            else spill_item(g, t, (uint64_t)bin[t], wgt);
-                        }
-                        left -= wgt;
-                    }
-                }
-            } else {
-                added = skm_count_kmer(h, seen, sk, mask, f, g.T, emit);
-            }
-            n_added += added;
-            // abundance list: a k-mer this batch adds at least twice (the lanes of the wave that are in here vote)
-            if (sg.abl_keys) {
-                const bool want = added >= 2u;
-                const unsigned long long here = __ballot(true), vote = __ballot(want);
-                if (vote) {
-                    const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)here) - 1u;
-                    uint32_t base = 0;
-                    if (lane == leader) base = atomicAdd(&abl_cur, (uint32_t)__popcll(vote));
-                    base = (uint32_t)__shfl((int)base, (int)leader);
-                    const uint32_t at = base + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull));
-                    if (want && at < sg.abl_cap_wg) {
-                        const uint64_t e = (uint64_t)blockIdx.x * sg.abl_cap_wg + at;
-                        sg.abl_keys[e * KW] = c.w[0];
-                        if (KW == 2) sg.abl_keys[e * KW + (KW - 1)] = c.w[KW - 1];
-                        sg.abl_cnts[e] = (uint8_t)min(added, 255u);
-                    }
-                }
-            }
-        });
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        abl_close();
-        if (sg.dl_keys && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
-    }
-    for (uint32_t s = threadIdx.x; s < ns; s += SKM_THREADS3)
-        g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
-    n_added = wave_sum_u64(n_added);
-    n_distinct = wave_sum_u64(n_distinct);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[BIN_CTR_ADDED], (unsigned long long)n_added);
-    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[SKM_CTR_DISTINCT], (unsigned long long)n_distinct);
-}
-
-// loose records: every k-mer occurrence on its own, increments through the spill list (global atomics)
-template <int KW>
-__global__ __launch_bounds__(256) void k_skm_loose_count(SkmGeom sg, const SketchDev *__restrict__ sk,
-                                                         const SketchDev *__restrict__ mask, ConsumeFilter f, BinGeom g)
-{
-    __shared__ uint32_t lut[256];
-    if (sg.ctr[SKM_CTR_FAIL] != 0) return;                  // the pass was given up: the caller redoes the batch another way
-    lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    __syncthreads();
-    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
-    if (n > sg.loose_cap) n = sg.loose_cap;
-    const int k = sg.k, recw = sg.lrecw;
-    uint64_t n_added = 0;
-    // wave-uniform loops (every lane votes in spill_items_wave).  A wave takes 64 records at a time: the one-k-mer records
-    // (occurrences that missed a full LDS table: nearly all of them) are handled one per lane; a record with several k-mers
-    // (it missed its segment in S1 / S2) is spread over the lanes, one k-mer each, instead of holding 63 lanes up while one
-    // lane rolls through it
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint32_t lane = threadIdx.x & 63u;
-    auto count_one = [&](const SkmKey<KW> &fw, bool live) {
-        uint64_t h = 0;
-        bool pass = false;
-        if (live) {
-            h = skm_key_hash<KW>(skm_canonical<KW>(fw, skm_revcomp<KW>(fw, k)), lut, f.hp);
-            pass = consume_filter_pass(f, mask, h);
-        }
-        n_added += pass ? 1 : 0;
-        uint64_t bins[BIN_MAX_T];
-#pragma unroll
-        for (int t = 0; t < BIN_MAX_T; ++t) bins[t] = (pass && t < g.T) ? fastmod(h, sk->size[t], sk->magic[t]) : 0ull;
-        spill_items_wave(g, bins, 1u, pass);
-    };
-    // records a wave takes at a time: the records with several k-mers are handled one after the other (each a round trip to the spill
-    // counter), so a short list -- 40 k records at config 2 -- is dealt a few records to every wave, not 64 to one wave in seven
-    // (0.135 -> 0.0x ms per launch; a long list -- k = 51: millions of one-k-mer records -- keeps 64)
-    const uint64_t total_waves = (uint64_t)gridDim.x * (blockDim.x >> 6), wave_id = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint32_t per = (uint32_t)min((unsigned long long)64, max((unsigned long long)1, (n + total_waves - 1) / total_waves));
-    (void)stride;
-    for (uint64_t i0 = wave_id * per; i0 < n; i0 += total_waves * per) {
-        const uint64_t i = i0 + lane;
-        const bool have = lane < per && i < n;
-        const uint64_t *rec = sg.loose + (have ? i : 0) * (uint64_t)recw;
-        uint64_t bw[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bw[t] = (have && t < sg.nbw) ? rec[1 + t] : 0ull;
-        const uint32_t nk = have ? skm_hdr_n(rec[0]) : 0u;
-        count_one(skm_first_kmer<KW>(bw, k), nk == 1);
-        unsigned long long longer = __ballot(nk > 1);
-        while (longer) {
-            const uint32_t src = (uint32_t)__ffsll((long long)longer) - 1u;
-            longer &= longer - 1ull;
-            const uint64_t b0 = skm_shfl64(bw[0], src), b1 = skm_shfl64(bw[1], src), b2 = skm_shfl64(bw[2], src);
-            const uint32_t nk_src = (uint32_t)__shfl((int)nk, (int)src);
-            for (uint32_t j0 = 0; j0 < nk_src; j0 += 64) {
-                const uint32_t j = j0 + lane;
-                const bool live = j < nk_src;
-                count_one(skm_kmer_at<KW>(b0, b1, b2, live ? j : 0u, k), live);
-            }
-        }
-    }
-    n_added = wave_sum_u64(n_added);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[BIN_CTR_ADDED], (unsigned long long)n_added);
-}
-
-// ---- S3': route (read-sharded multi-GPU count) ---------------------------------------------------------------
-// Same walk as k_skm_count, but a distinct k-mer leaves as one (hash, count) item for the rank that owns the hash's
-// band instead of T bin items: what crosses xGMI shrinks by the shard's own coverage, and the owner adds each item
-// with one weighted saturating add per table (kv_consume_hashes_weighted).
-#define SKM_ROUTE_MAX_DEST 16
-// (out of line: a pair that misses its segment is rare in the kernels that call this from their drain, whose registers it must not cost)
-struct SkmOverflowSink { unsigned long long *ctr; uint64_t *ovf; uint8_t *ovf_dest; uint64_t ovf_cap; int ndest; };
-__device__ __attribute__((noinline)) void skm_route_overflow(SkmOverflowSink rs, uint32_t d, uint64_t h, uint64_t count)
-{
-    {
-        // the overflow list: one returning atomic for the lanes of the wave that are here together, not one each (the loose kernel sends
-        // every item this way: 4.5 M of them took 25 ms one by one at ~180 per microsecond), and one add per destination among them
-        const unsigned long long here = __ballot(true);
-        const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)here) - 1u;
-        unsigned long long o = 0;
-        if (lane == leader) o = atomicAdd(&rs.ctr[ROUTE_CTR_OVERFLOW], (unsigned long long)__popcll(here));
-        o = skm_shfl64(o, leader) + (unsigned long long)__popcll(here & ((1ull << lane) - 1ull));
-        const bool fits = o < rs.ovf_cap;
-        for (int dd = 0; dd < rs.ndest; ++dd) {
-            const unsigned long long same = __ballot(fits && d == (uint32_t)dd);
-            if (same && lane == (uint32_t)__ffsll((long long)same) - 1u) atomicAdd(&rs.ctr[ROUTE_CTR_DEST0 + dd], (unsigned long long)__popcll(same));
-        }
-        if (fits) {
-            *(ulonglong2 *)(rs.ovf + 2 * o) = make_ulonglong2(h, count);
-            rs.ovf_dest[o] = (uint8_t)d;
-        }
-    }
-}
-
-__device__ __forceinline__ void skm_route_item(const KvRouteSink &rs, const uint64_t *lo, uint32_t *cur, uint64_t h, uint64_t count)
-{
-    if (h == UINT64_MAX) return;                 // the top hash value belongs to no band (kv_shard.hip)
-    uint32_t d = 0;
-    for (int b = 1; b < rs.ndest; ++b) d += h >= lo[b] ? 1u : 0u;
-    const uint32_t pos = cur ? atomicAdd(&cur[d], 1u) : 0xffffffffu;
-    if (pos < rs.seg_cap) *(ulonglong2 *)(rs.seg + (((uint64_t)d * rs.nwg + blockIdx.x) * rs.seg_cap + pos) * 2) = make_ulonglong2(h, count);
-    else skm_route_overflow(SkmOverflowSink{rs.ctr, rs.ovf, rs.ovf_dest, rs.ovf_cap, rs.ndest}, d, h, count);
-}
-
-template <int KW, int TS, bool COMPACT = false>
-__global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_route(SkmGeom sg, HashParams hp, KvRouteSink rs)
-{
-    __shared__ SkmTable<KW, TS> tb;
-    __shared__ uint32_t cnt[TS];
-    __shared__ uint32_t next_bucket;
-    __shared__ uint32_t cur[SKM_ROUTE_MAX_DEST];
-    __shared__ uint64_t lo[SKM_ROUTE_MAX_DEST];
-    __shared__ uint32_t dl_cur, dl_b0, dl_prev;         // distinct list (sg.dl_keys != NULL: the owner will answer the scan from it, kv_skm_mex_scan_set)
-    __shared__ uint32_t dl_org, dl_lim;                 // where the workgroup's entries start and how many fit: its own stretch, or (sg.dl_chunk) the chunk it drew last
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *lut = dyn, *scratch = dyn + 256;
-    if (threadIdx.x < 256) lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    if (threadIdx.x < (uint32_t)rs.ndest) { cur[threadIdx.x] = 0; lo[threadIdx.x] = rs.bs * (uint64_t)threadIdx.x; }
-    const int k = sg.k;
-    uint64_t n_distinct = 0;
-    skm_table_clear(tb);
-    for (uint32_t i = threadIdx.x; i < TS; i += SKM_THREADS3) cnt[i] = 0;
-    if (threadIdx.x == 0) {
-        next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt; dl_cur = 0; dl_b0 = 0; dl_prev = 0xffffffffu;
-        dl_org = sg.dl_chunk ? 0u : blockIdx.x * sg.dl_cap_wg; dl_lim = sg.dl_chunk ? 0u : sg.dl_cap_wg;
-    }
-    auto dl_close = [&]() {
-        if (sg.dl_keys && dl_prev != 0xffffffffu) {
-            sg.dl_bstart[dl_prev] = dl_org + dl_b0;
-            sg.dl_bcount[dl_prev] = dl_cur - dl_b0;              // (a stretch that ran out is reported through SKM_CTR_DL_RAN_OUT: the whole list is then dropped)
-            if (sg.dl_chunk && dl_cur > dl_lim) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
-        }
-    };
-    // passes a bucket is combined in (see below), from its record count
-    auto passes_of = [&](uint32_t b) {
-        const uint32_t least = sg.passes > 1u ? sg.passes : 1u;
-        const uint32_t *cnt2 = sg.cnt2 + (uint64_t)b * sg.nwg2;
-        uint32_t nrec = 0;
-        for (uint32_t s2 = 0; s2 < sg.nwg2; ++s2) nrec += cnt2[s2];
-        // ~9.5 k-mers a record, a fifth of them distinct at sequencing coverage: 1.9 distinct k-mers per record, a pass's share under
-        // 0.65 of the table.  Any number of passes (the class of a k-mer is a range of its hash, not a bit field): powers of two made the
-        // average bucket of config 4 take 8 where 5 do.
-        const uint32_t per_pass = (uint32_t)TS * 13u / 20u;
-        const uint32_t want = (19u * nrec / 10u + per_pass - 1u) / per_pass;
-        return min(64u, max(least, want));
-    };
-    for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
-        __syncthreads();
-        const uint32_t b = next_bucket;
-        if (b >= sg.n_buckets) break;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            dl_close();
-            if (sg.dl_keys && sg.dl_chunk) {
-                // The pool (an owner whose share is too big for a stretch per workgroup with slack for the unevenness of their shares:
-                // config 4's 7.9 G occurrences, 1.5 G of them distinct).  A bucket's list is one stretch, and a pass leaves at most a table's
-                // worth of entries: a chunk that may not hold this bucket's is left as it is and the next one drawn.
-                const uint32_t need = passes_of(b) * (uint32_t)TS;
-                if (dl_cur + need > dl_lim) {
-                    const unsigned long long c = atomicAdd(&sg.ctr[SKM_CTR_POOL_CHUNKS], 1ull);
-                    if (c < sg.dl_nchunks && need <= sg.dl_chunk) { dl_org = (uint32_t)c * sg.dl_chunk; dl_lim = sg.dl_chunk; }
-                    else { dl_org = 0; dl_lim = 0; atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull); }          // the pool is empty (or the bucket beyond any chunk): no list
-                    dl_cur = 0;
-                }
-            }
-            dl_prev = b; dl_b0 = dl_cur;
-            if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_COUNT], 1ull) * sg.bpt;
-        }
-        // A sample too big for the bucket geometry (255 x 4096 buckets: beyond 8.5 G k-mers a bucket holds more distinct k-mers than the
-        // table has slots) is combined in passes: pass p walks the whole bucket and takes the k-mers whose hash says p -- the walk is paid
-        // once per pass, the inserts, the hashes and the pairs once in all (kv_skm_mex_route sets sg.passes)
-        // (how many: by the bucket's own size -- with 12-base minimizers a million buckets are far from even, a popular minimizer makes
-        // its bucket several times the average -- from its record count: ~9.5 k-mers a record, a fifth of them distinct at sequencing
-        // coverage, a pass's share under 0.7 of the table; sg.passes, the estimate from the average, is the least)
-        const uint32_t passes = passes_of(b);
-        for (uint32_t pass = 0; pass < passes; ++pass) {
-        if (pass) __syncthreads();                       // (the drain of the pass before empties the table)
-        skm_walk_bucket<KW, false, 0, COMPACT>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
-            if (!skm_cacheable<KW>(c)) return pass == 0u;                                           // (travels alone, once)
-            if (passes > 1u && __umulhi(skm_slot_hash<KW>(c) * 0x9E3779B1u, passes) != pass) return false;       // (bits the slot and the probe step do not come from)
-            const int slot = skm_table_insert(tb, c);
-            if (slot >= 0) atomicAdd(&cnt[slot], 1u);
-            return slot < 0;
-        });
-        __syncthreads();
-        skm_for_occupied<TS>(tb.key[0], (uint16_t *)scratch, skm_wave_scratch_words(sg.sbw) * 2u, [&](uint32_t slot) {
-            SkmKey<KW> c;
-            c.w[0] = tb.key[0][slot];
-            tb.key[0][slot] = SKM_EMPTY;
-            if (KW == 2) { c.w[KW - 1] = tb.key[KW - 1][slot]; tb.key[KW - 1][slot] = SKM_EMPTY; }
-            const uint32_t seen = cnt[slot];
-            cnt[slot] = 0;
-            n_distinct += 1;
-            const uint64_t h = skm_key_hash<KW>(c, lut, hp);
-            if (sg.dl_keys) {
-                const unsigned long long here = __ballot(true);
-                const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)here) - 1u;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&dl_cur, (uint32_t)__popcll(here));
-                base = (uint32_t)__shfl((int)base, (int)leader);
-                const uint32_t at = base + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
-                if (at < dl_lim) {
-                    const uint64_t e = (uint64_t)dl_org + at;
-                    sg.dl_keys[e * KW] = c.w[0];
-                    if (KW == 2) sg.dl_keys[e * KW + (KW - 1)] = c.w[KW - 1];
-                    sg.dl_hash[e] = h;
-                }
-            }
-            skm_route_item(rs, lo, cur, h, seen);
-        });
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        dl_close();
-        if (sg.dl_keys && !sg.dl_chunk && dl_cur > sg.dl_cap_wg) atomicAdd(&sg.ctr[SKM_CTR_DL_RAN_OUT], 1ull);
-    }
-    if (threadIdx.x < (uint32_t)rs.ndest)
-        rs.seg_count[(uint64_t)threadIdx.x * rs.nwg + blockIdx.x] = (uint32_t)min((uint64_t)cur[threadIdx.x], rs.seg_cap);
-    n_distinct = wave_sum_u64(n_distinct);
-    if ((threadIdx.x & 63) == 0 && n_distinct) atomicAdd(&sg.ctr[SKM_CTR_DISTINCT], (unsigned long long)n_distinct);
-}
-
-// loose records: one item of count 1 per k-mer occurrence, through the overflow list
-template <int KW>
-__global__ __launch_bounds__(256) void k_skm_loose_route(SkmGeom sg, HashParams hp, KvRouteSink rs)
-{
-    __shared__ uint32_t lut[256];
-    __shared__ uint64_t lo[SKM_ROUTE_MAX_DEST];
-    __shared__ uint32_t dcount[SKM_ROUTE_MAX_DEST];      // items of this workgroup per destination
-    __shared__ uint32_t wg_items, wg_cur;
-    __shared__ unsigned long long wg_base;
-    if (sg.ctr[SKM_CTR_FAIL] != 0) return;
-    lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    if (threadIdx.x < SKM_ROUTE_MAX_DEST) { lo[threadIdx.x] = rs.bs * (uint64_t)threadIdx.x; dcount[threadIdx.x] = 0; }
-    if (threadIdx.x == 0) { wg_items = 0; wg_cur = 0; }
-    __syncthreads();
-    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
-    if (n > sg.loose_cap) n = sg.loose_cap;
-    const int k = sg.k, recw = sg.lrecw;
-    // Every item here goes to the sink's overflow list.  Its slots are reserved ONCE per workgroup (the k-mers of the workgroup's records
-    // are counted first: one header each) and dealt out through an LDS cursor, the per-destination totals are kept in LDS and added once
-    // at the end: a returning device atomic per item -- then per wave -- made this kernel 25 and 10 ms for the 4.5 M loose k-mers of a
-    // 75 M-read sample's owner, against 11 ms for the combine itself.
-    {
-        uint32_t mine = 0;
-        for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-            mine += skm_hdr_n(sg.loose[i * (uint64_t)recw]);
-        if (mine) atomicAdd(&wg_items, mine);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) wg_base = wg_items ? atomicAdd(&rs.ctr[ROUTE_CTR_OVERFLOW], (unsigned long long)wg_items) : 0ull;
-    __syncthreads();
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t *rec = sg.loose + i * (uint64_t)recw;
-        uint64_t bw[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? rec[1 + t] : 0ull;
-        const uint32_t nk = skm_hdr_n(rec[0]);
-        SkmKey<KW> fw = skm_first_kmer<KW>(bw, k);
-        SkmKey<KW> rc = skm_revcomp<KW>(fw, k);
-        for (uint32_t j = 0; j < nk; ++j) {
-            if (j) skm_roll<KW>(fw, rc, skm_base_at(bw, j + (uint32_t)k - 1u), k);
-            const uint64_t h = skm_key_hash<KW>(skm_canonical<KW>(fw, rc), lut, hp);
-            const unsigned long long o = wg_base + atomicAdd(&wg_cur, 1u);
-            if (o >= rs.ovf_cap) continue;
-            uint32_t d = 0;
-            for (int b = 1; b < rs.ndest; ++b) d += h >= lo[b] ? 1u : 0u;
-            if (h == UINT64_MAX) d = 0xffu;             // (the top hash value belongs to no band: the slot stays, marked -- k_route_tail skips it)
-            else atomicAdd(&dcount[d], 1u);
-            *(ulonglong2 *)(rs.ovf + 2 * o) = make_ulonglong2(h, 1ull);
-            rs.ovf_dest[o] = (uint8_t)d;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)rs.ndest && dcount[threadIdx.x]) atomicAdd(&rs.ctr[ROUTE_CTR_DEST0 + threadIdx.x], (unsigned long long)dcount[threadIdx.x]);
-}
-
-// ---- S6: novel ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void skm_mark(const NovelParams &p, const ReadsDev &rd, uint64_t pos, uint64_t stride)
-{
-    const uint64_t read = pos / stride;
-    const uint64_t off = pos - read * stride;
-    if ((rd.flags[read] & 1) || read < p.first_read) return;     // the scan skips these reads (kevlar/novel.py:134-139)
-    const uint64_t bit = read * p.mask_stride + off;
-    atomicOr(&p.mask[bit >> 5], 1u << (bit & 31));
-}
-
-template <int KW, int TS>
-__global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
-{
-    __shared__ SkmTable<KW, TS> tb;
-    __shared__ uint32_t flag[TS / 32];           // bit per slot: the key is interesting
-    __shared__ uint32_t rej[TS / 32];            // bit per slot: a control's abundance list rejects the key (no probe needed)
-    __shared__ NovelShared ns;
-    __shared__ uint32_t next_bucket, any_hit;
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *lut = dyn, *scratch = dyn + 256;
-    if (threadIdx.x < 256) lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    load_descs(ns, p);
-    const int k = sg.k;
-    if (threadIdx.x == 0) next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
-    for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
-        __syncthreads();
-        const uint32_t b = next_bucket;
-        if (b >= sg.n_buckets) break;
-        skm_table_clear(tb);
-        if (threadIdx.x < TS / 32) { flag[threadIdx.x] = 0; rej[threadIdx.x] = 0; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else {
-                const unsigned long long ticket = atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull);
-                next_bucket = (uint32_t)ticket * sg.bpt;
-                // the count pass's early exit, for a scan that cut the batch itself: once 2 % of the buckets are done, more than
-                // 4 % of their k-mers outside the tables (a batch of low coverage: nearly every k-mer distinct) raise the flag --
-                // the caller then scans tile by tile, and remembers -- instead of pushing the whole batch through the loose list
-                const unsigned long long done = ticket * sg.bpt;
-                if (done * 50ull >= sg.n_buckets) {
-                    const unsigned long long now = __hip_atomic_load(&sg.ctr[SKM_CTR_LOOSE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), start = sg.ctr[SKM_CTR_LOOSE_S12];
-                    if (now > start && (now - start) * 25ull > done * sg.bucket_kmers) sg.ctr[SKM_CTR_FAIL] = 1;
-                }
-            }
-            any_hit = 0;
-        }
-        // collect the distinct k-mers
-        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t) {
-            const int slot = skm_cacheable<KW>(c) ? skm_table_insert(tb, c) : -1;
-            return slot < 0;
-        });
-        // the k-mers of this bucket that a control is known to hold more than ctrl_max times (KvAbundList): they go into the
-        // same table, marked; whichever of them the case sample has too is then skipped by the evaluation.  A full table
-        // only costs the shortcut for that key.
-        for (int a = 0; a < abls.n; ++a) {
-            const uint32_t e0 = abls.bstart[a][b], en = abls.bcount[a][b];
-            for (uint32_t i = threadIdx.x; i < en; i += SKM_THREADS3) {
-                if ((int)min((uint32_t)abls.cnts[a][e0 + i], abls.maxv[a]) <= abls.ctrl_max) continue;
-                SkmKey<KW> c;
-                c.w[0] = abls.keys[a][(uint64_t)(e0 + i) * KW];
-                if (KW == 2) c.w[KW - 1] = abls.keys[a][(uint64_t)(e0 + i) * KW + (KW - 1)];
-                const int slot = skm_table_insert(tb, c);
-                if (slot >= 0) atomicOr(&rej[slot >> 5], 1u << (slot & 31));
-            }
-        }
-        __syncthreads();
-        // evaluate each of them once
-        skm_for_occupied<TS>(tb.key[0], (uint16_t *)scratch, skm_wave_scratch_words(sg.sbw) * 2u, [&](uint32_t slot) {
-            SkmKey<KW> c;
-            c.w[0] = tb.key[0][slot];
-            if (KW == 2) c.w[KW - 1] = tb.key[KW - 1][slot];
-            const uint64_t h = skm_key_hash<KW>(c, lut, p.hp);
-            if (band_pass(p, h) && novel_test_fast(ns, p, h, nullptr, 0ull)) { atomicOr(&flag[slot >> 5], 1u << (slot & 31)); any_hit = 1; }
-        }, rej);            // (keys a control's list rejects are not queued: 25 M of 106 M at config 2, lanes that used to sit out their wave's hashes)
-        __syncthreads();
-        if (any_hit == 0) continue;
-        // mark every occurrence of an interesting k-mer (an occurrence whose key is absent went to the loose list)
-        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
-            if (!skm_cacheable<KW>(c)) return false;
-            const int slot = skm_table_find(tb, c);
-            if (slot >= 0 && ((flag[slot >> 5] >> (slot & 31)) & 1u)) skm_mark(p, rd, pos, sg.stride);
-            return false;
-        });
-    }
-}
-
-// bits[w] bit j = (tab[32 w + j] >= case_min), byte counters: the first probe of the list scan as a bit map (NovelParams::case0_bits)
-__global__ __launch_bounds__(256) void k_case_bits(const uint8_t *__restrict__ tab, uint64_t size, int case_min, uint32_t *__restrict__ bits)
-{
-    const uint64_t n_words = (size + 31) >> 5;
-    for (uint64_t w = blockIdx.x * 256ull + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * 256ull) {
-        uint32_t out = 0;
-        if (w * 32 + 32 <= size) {
-            const uint4 a = ((const uint4 *)tab)[2 * w], b = ((const uint4 *)tab)[2 * w + 1];
-            const uint32_t q[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) out |= ((int)((q[i] >> (8 * j)) & 0xffu) >= case_min ? 1u : 0u) << (4 * i + j);
-        } else {
-            for (uint64_t j = w * 32; j < size; ++j) out |= ((int)tab[j] >= case_min ? 1u : 0u) << (uint32_t)(j - w * 32);
-        }
-        bits[w] = out;
-    }
-}
-
-// The scan of a batch whose count pass left a distinct list (SkmGeom::dl_*): nothing is combined and nothing is hashed again.
-// Per bucket: (1) the controls' abundance-list entries that exceed ctrl_max go into one small LDS table (the k-mers no probe is
-// needed for); (2) every entry of the distinct list that is not in there gets ONE probe -- table 0 of the first case sample, where
-// a sequencing-error k-mer ends -- four entries per thread in flight and no barrier anywhere, and the few that pass are queued;
-// (3) the queue is dealt one candidate per thread for the rest of kmer_is_interesting() (a dozen dependent probes: paid once per
-// bucket, side by side, instead of once per wave and round); the interesting ones go into a second table, and (4) only if there
-// are any are the bucket's records walked, to mark their occurrences.  Occurrences that missed the count pass's LDS tables are in
-// the loose list already (k_skm_loose_novel evaluates them one by one).  A bucket's list has at most as many entries as the count
-// kernel's LDS table has slots.
-template <int KW, int TSM>
-__global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_novel_list(SkmGeom sg, ReadsDev rd, NovelParams p, SkmAblSet abls)
-{
-    constexpr uint32_t E = 4;                    // entries a thread has in flight (2 / 4 / 6 measured: 2.64 / 2.6-2.8 / 2.52 ms, within the spread between runs)
-    __shared__ SkmTable<KW, TSM> rtb;            // rejected by a control's list
-    __shared__ SkmTable<KW, TSM> itb;            // interesting
-    __shared__ NovelShared ns;
-    __shared__ uint16_t cand[SKM_LIST_MAX];      // entries (relative to the bucket's first) that passed the first probe
-    __shared__ uint32_t next_bucket, n_int, n_cand;
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *scratch = dyn;
-    load_descs(ns, p);
-    skm_table_clear(itb);
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt; n_int = 0; n_cand = 0; }
-    auto mark_pass = [&](uint32_t b) {
-        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
-            if (skm_cacheable<KW>(c) && skm_table_find(itb, c) >= 0) skm_mark(p, rd, pos, sg.stride);
-            return false;
-        });
-        __syncthreads();
-        skm_table_clear(itb);
-        if (threadIdx.x == 0) n_int = 0;
-        __syncthreads();
-    };
-    for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
-        __syncthreads();
-        const uint32_t b = next_bucket;
-        if (b >= sg.n_buckets) break;
-        skm_table_clear(rtb);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3 || __hip_atomic_load(&sg.ctr[SKM_CTR_FAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
-            n_cand = 0;
-        }
-        // the first list entries are requested before the controls' lists are worked in: they arrive meanwhile
-        const uint32_t e0 = sg.dl_bstart[b], en = min(sg.dl_bcount[b], SKM_LIST_MAX);
-        SkmKey<KW> c[E];
-        uint64_t h[E];
-        auto request = [&](uint32_t base) {
-#pragma unroll
-            for (uint32_t u = 0; u < E; ++u) {
-                const uint32_t i = base + u * SKM_THREADS3 + threadIdx.x;
-                const bool in = i < en;
-                c[u].w[0] = in ? sg.dl_keys[(uint64_t)(e0 + i) * KW] : SKM_EMPTY;
-                if (KW == 2) c[u].w[KW - 1] = in ? sg.dl_keys[(uint64_t)(e0 + i) * KW + (KW - 1)] : SKM_EMPTY;
-                h[u] = in ? sg.dl_hash[e0 + i] : 0ull;
-            }
-        };
-        request(0);
-        for (int a = 0; a < abls.n; ++a) {
-            const uint32_t a0 = abls.bstart[a][b], an = abls.bcount[a][b];
-            for (uint32_t i = threadIdx.x; i < an; i += SKM_THREADS3) {
-                if ((int)min((uint32_t)abls.cnts[a][a0 + i], abls.maxv[a]) <= abls.ctrl_max) continue;
-                SkmKey<KW> c;
-                c.w[0] = abls.keys[a][(uint64_t)(a0 + i) * KW];
-                if (KW == 2) c.w[KW - 1] = abls.keys[a][(uint64_t)(a0 + i) * KW + (KW - 1)];
-                (void)skm_table_insert(rtb, c);              // (a full table only costs the shortcut for that key)
-            }
-        }
-        __syncthreads();
-        for (uint32_t e0 = 0; e0 < en; e0 += E * SKM_THREADS3) {
-            if (e0) request(e0);
-            bool live[E];
-            uint32_t v[E];
-#pragma unroll
-            for (uint32_t u = 0; u < E; ++u) {
-                live[u] = e0 + u * SKM_THREADS3 + threadIdx.x < en && skm_table_find(rtb, c[u]) < 0 && band_pass(p, h[u]);
-                if (p.case0_bits) {
-                    const uint64_t bin = fastmod(h[u], ns.d[0].size, ns.d[0].magic);
-                    const __attribute__((address_space(1))) uint32_t *bits = (const __attribute__((address_space(1))) uint32_t *)p.case0_bits;
-                    v[u] = live[u] && ((bits[bin >> 5] >> (uint32_t)(bin & 31u)) & 1u) ? (uint32_t)p.case_min : 0u;
-                } else {
-                    v[u] = live[u] ? probe(ns, 0, 0, h[u]) : 0u;
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < E; ++u)
-                if (live[u] && (int)v[u] >= p.case_min) cand[atomicAdd(&n_cand, 1u)] = (uint16_t)(e0 + u * SKM_THREADS3 + threadIdx.x);
-        }
-        __syncthreads();
-        const uint32_t nc = n_cand;
-        for (uint32_t j0 = 0; j0 < nc; j0 += SKM_THREADS3) {
-            const uint32_t j = j0 + threadIdx.x;
-            if (j < nc) {
-                const uint32_t i = cand[j];
-                SkmKey<KW> c;
-                c.w[0] = sg.dl_keys[(uint64_t)(e0 + i) * KW];
-                if (KW == 2) c.w[KW - 1] = sg.dl_keys[(uint64_t)(e0 + i) * KW + (KW - 1)];
-                const uint64_t h = sg.dl_hash[e0 + i];
-                if (novel_test_wide(ns, p, h)) {
-                    if (skm_table_insert(itb, c) < 0) sg.ctr[SKM_CTR_FAIL] = 1;          // (cannot happen below half full; the caller then redoes the scan the other way)
-                    atomicAdd(&n_int, 1u);
-                    if (p.ab_keys) (void)ab_claim(p, h, p.ncase + p.nctrl);      // a place for its abundances (k_ab_fill), for the kernel that reports the hits
-                }
-            }
-            __syncthreads();
-            // a bucket with more interesting k-mers than a quarter of the table (a case sample without controls to speak of)
-            // marks in instalments
-            if (n_int > TSM / 4 && j0 + SKM_THREADS3 < nc) mark_pass(b);
-        }
-        if (n_int != 0) mark_pass(b);
-    }
-}
-
-// the abundances of the k-mers k_skm_novel_list claimed a slot for (a dozen probes each, side by side, off the scan's critical path:
-// inside the scan they were a chain of round trips in front of a workgroup barrier, 0.25 ms)
-__global__ __launch_bounds__(256) void k_ab_fill(NovelParams p)
-{
-    __shared__ NovelShared ns;
-    load_descs(ns, p);
-    __syncthreads();
-    const int S = p.ncase + p.nctrl;
-    // the slots that were claimed are on a list (ab_claim) -- some 10^5 of the table's 8 M at config 2, whose walk was 0.11 ms; a list
-    // that ran out of room sends the kernel over the whole table as before
-    const unsigned int listed = p.ab_list ? *p.ab_count : 0xffffffffu;
-    if (listed <= p.ab_list_cap) {
-        for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < listed; i += (uint64_t)gridDim.x * 256ull) {
-            const uint64_t slot = p.ab_list[i];
-            hit_abundances(ns, p, (uint64_t)p.ab_keys[slot], p.ab_vals + slot * (uint64_t)S);
-        }
-        return;
-    }
-    for (uint64_t slot = blockIdx.x * 256ull + threadIdx.x; slot <= p.ab_mask; slot += (uint64_t)gridDim.x * 256ull) {
-        const unsigned long long h = p.ab_keys[slot];
-        if (h != 0ull) hit_abundances(ns, p, (uint64_t)h, p.ab_vals + slot * (uint64_t)S);
-    }
-}
-
-template <int KW>
-__global__ __launch_bounds__(256) void k_skm_loose_novel(SkmGeom sg, ReadsDev rd, NovelParams p)
-{
-    __shared__ uint32_t lut[256];
-    __shared__ NovelShared ns;
-    lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    load_descs(ns, p);
-    __syncthreads();
-    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
-    if (n > sg.loose_cap) n = sg.loose_cap;
-    const int k = sg.k, recw = sg.lrecw;
-    const uint32_t lane = threadIdx.x & 63u;
-    auto test_one = [&](const SkmKey<KW> &fw, bool live, uint64_t pos) {
-        if (!live) return;
-        const uint64_t h = skm_key_hash<KW>(skm_canonical<KW>(fw, skm_revcomp<KW>(fw, k)), lut, p.hp);
-        if (band_pass(p, h) && novel_test_fast(ns, p, h, nullptr, 0ull)) skm_mark(p, rd, pos, sg.stride);
-    };
-    // as k_skm_loose_count deals the list: a few records to every wave, a one-k-mer record a lane, a longer record spread over the
-    // lanes k-mer by k-mer (a thread per record rolled through up to ncap k-mers, each a chain of table probes: 0.167 ms for the
-    // handful of records a config-2 scan finds here)
-    const uint64_t total_waves = (uint64_t)gridDim.x * (blockDim.x >> 6), wave_id = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint32_t per = (uint32_t)min((unsigned long long)64, max((unsigned long long)1, (n + total_waves - 1) / total_waves));
-    for (uint64_t i0 = wave_id * per; i0 < n; i0 += total_waves * per) {
-        const uint64_t i = i0 + lane;
-        const bool have = lane < per && i < n;
-        const uint64_t *rec = sg.loose + (have ? i : 0) * (uint64_t)recw;
-        uint64_t bw[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bw[t] = (have && t < sg.nbw) ? rec[1 + t] : 0ull;
-        const uint64_t hdr = have ? rec[0] : 0ull;
-        const uint32_t nk = have ? skm_hdr_n(hdr) : 0u;
-        test_one(skm_first_kmer<KW>(bw, k), nk == 1, skm_hdr_pos_of(hdr, 0u));
-        unsigned long long longer = __ballot(nk > 1);
-        while (longer) {
-            const uint32_t src = (uint32_t)__ffsll((long long)longer) - 1u;
-            longer &= longer - 1ull;
-            const uint64_t b0 = skm_shfl64(bw[0], src), b1 = skm_shfl64(bw[1], src), b2 = skm_shfl64(bw[2], src), h_src = skm_shfl64(hdr, src);
-            const uint32_t nk_src = (uint32_t)__shfl((int)nk, (int)src);
-            for (uint32_t j0 = 0; j0 < nk_src; j0 += 64) {
-                const uint32_t j = j0 + lane;
-                const bool live = j < nk_src;
-                test_one(skm_kmer_at<KW>(b0, b1, b2, live ? j : 0u, k), live, skm_hdr_pos_of(h_src, live ? j : 0u));
-            }
-        }
-    }
-}
-
-// ---- the scan answered by the owner of the minimizer buckets (minimizer-sharded exchange, kv_skm_mex_scan_set) ----------------
-// After kv_skm_mex_route(keep_scan) this rank holds every occurrence of the k-mers of its buckets -- from whichever shard, with the
-// global (read, offset) of each in the record headers -- and key + hash of every distinct one (the distinct list k_skm_route left).
-// Once the band owners' verdicts have been gathered into the set of interesting hashes, the hits are these: per bucket, the list
-// entries that are members go into a small LDS table with their slot of the set; only if there are any is the bucket walked, and every
-// occurrence of a member leaves as (read << 16 | offset, the S abundances the set carries) -- the form kv_hits_from_tagged sorts.
-// Hits are staged in LDS and appended with one update of the device-wide counter per flush (that counter takes ~90 updates per
-// microsecond however they are issued); a bucket with more hits than the stage holds appends the rest one by one.
-struct SetHitSink {
-    unsigned long long *tags;
-    uint8_t *abund;
-    unsigned long long *count;
-    uint64_t cap;
-};
-__device__ __forceinline__ void set_hit_store(const NovelParams &p, const SetHitSink &out, uint64_t at, unsigned long long tag, uint64_t slot)
-{
-    if (at >= out.cap) return;
-    const int S = p.ncase + p.nctrl;
-    out.tags[at] = tag;
-    for (int c = 0; c < S; ++c) out.abund[at * (uint64_t)S + c] = p.set_abund[slot * (uint64_t)S + c];
-}
-#define SKM_HIT_STAGE 1024u
-template <int KW, int TSM>
-__global__ __launch_bounds__(SKM_THREADS3, 6) void k_skm_set_hits(SkmGeom sg, NovelParams p, SetHitSink out)
-{
-    __shared__ SkmTable<KW, TSM> itb;            // the bucket's members of the set
-    __shared__ uint32_t islot[TSM];              // their slots of the set
-    __shared__ unsigned long long htag[SKM_HIT_STAGE];
-    __shared__ uint32_t hslot[SKM_HIT_STAGE];
-    __shared__ uint32_t next_bucket, n_int, n_hit;
-    __shared__ unsigned long long flush_base;
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
-    uint32_t *scratch = dyn;
-    skm_table_clear(itb);
-    if (threadIdx.x == 0) { next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt; n_int = 0; n_hit = 0; }
-    for (uint32_t taken = 0; taken < sg.quota3; ++taken) {
-        __syncthreads();
-        const uint32_t b = next_bucket;
-        if (b >= sg.n_buckets) break;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if ((b + 1u) & (sg.bpt - 1u)) next_bucket = b + 1u;
-            else if (taken + 1 >= sg.quota3) next_bucket = 0xffffffffu;
-            else next_bucket = (uint32_t)atomicAdd(&sg.ctr[SKM_CTR_TICKET_SCAN], 1ull) * sg.bpt;
-        }
-        const uint32_t e0 = sg.dl_bstart[b], en = sg.dl_bcount[b];
-        for (uint32_t i = threadIdx.x; i < en; i += SKM_THREADS3) {
-            const uint64_t h = sg.dl_hash[e0 + i];
-            const uint64_t slot = set_find(p, h);
-            if (slot == KV_SET_NONE) continue;
-            SkmKey<KW> c;
-            c.w[0] = sg.dl_keys[(uint64_t)(e0 + i) * KW];
-            if (KW == 2) c.w[KW - 1] = sg.dl_keys[(uint64_t)(e0 + i) * KW + (KW - 1)];
-            const int at = skm_table_insert(itb, c);
-            if (at < 0) { sg.ctr[SKM_CTR_FAIL] = 1; continue; }            // more members than the table takes: the caller scans the other way
-            islot[at] = (uint32_t)slot;
-            atomicAdd(&n_int, 1u);
-        }
-        __syncthreads();
-        if (n_int == 0) continue;
-        skm_walk_bucket<KW, true, 0, false>(sg, b, scratch, [&](const SkmKey<KW> &c, uint64_t pos) {
-            if (!skm_cacheable<KW>(c)) return false;
-            const int at = skm_table_find(itb, c);
-            if (at < 0) return false;
-            const uint64_t read = pos / sg.stride;
-            const unsigned long long tag = ((unsigned long long)read << 16) | (unsigned long long)(pos - read * sg.stride);
-            const uint32_t i = atomicAdd(&n_hit, 1u);
-            if (i < SKM_HIT_STAGE) { htag[i] = tag; hslot[i] = islot[at]; }
-            else set_hit_store(p, out, atomicAdd(out.count, 1ull), tag, islot[at]);
-            return false;
-        });
-        __syncthreads();
-        const uint32_t staged = min(n_hit, SKM_HIT_STAGE);
-        if (threadIdx.x == 0) flush_base = atomicAdd(out.count, (unsigned long long)staged);
-        skm_table_clear(itb);
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < staged; i += SKM_THREADS3) set_hit_store(p, out, flush_base + i, htag[i], hslot[i]);
-        if (threadIdx.x == 0) { n_int = 0; n_hit = 0; }
-    }
-}
-
-// the occurrences that travelled alone (records of the loose list: one k-mer each from the combine, whole records from the split)
-template <int KW>
-__global__ __launch_bounds__(256) void k_skm_loose_set_hits(SkmGeom sg, NovelParams p, SetHitSink out)
-{
-    __shared__ uint32_t lut[256];
-    lut[threadIdx.x] = skm_ascii4(threadIdx.x);
-    __syncthreads();
-    unsigned long long n = sg.ctr[SKM_CTR_LOOSE];
-    if (n > sg.loose_cap) n = sg.loose_cap;
-    const int k = sg.k, recw = sg.lrecw;
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t *rec = sg.loose + i * (uint64_t)recw;
-        uint64_t bw[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bw[t] = t < sg.nbw ? rec[1 + t] : 0ull;
-        const uint32_t nk = skm_hdr_n(rec[0]);
-        SkmKey<KW> fw = skm_first_kmer<KW>(bw, k);
-        SkmKey<KW> rc = skm_revcomp<KW>(fw, k);
-        for (uint32_t j = 0; j < nk; ++j) {
-            if (j) skm_roll<KW>(fw, rc, skm_base_at(bw, j + (uint32_t)k - 1u), k);
-            const uint64_t slot = set_find(p, skm_key_hash<KW>(skm_canonical<KW>(fw, rc), lut, p.hp));
-            if (slot == KV_SET_NONE) continue;
-            const uint64_t pos = skm_hdr_pos_of(rec[0], j), read = pos / sg.stride;
-            set_hit_store(p, out, atomicAdd(out.count, 1ull), ((unsigned long long)read << 16) | (unsigned long long)(pos - read * sg.stride), slot);
-        }
-    }
-}
-
-__global__ void k_skm_forward_flag(const unsigned long long *skm_ctr, unsigned long long *bin_ctr)
-{
-    if (skm_ctr[SKM_CTR_FAIL] != 0) bin_ctr[BIN_CTR_FAIL] = 1;
-}
-
-// hits per tile = set bits of the tile's range of the mask (what k_novel_mark counts while it marks)
-__global__ __launch_bounds__(64) void k_tile_hits(ReadsDev rd, NovelParams p)
-{
-    const TileDesc td = rd.tile[blockIdx.x];
-    uint64_t b0, b1;
-    if (td.seg) {
-        b0 = (uint64_t)td.first * p.mask_stride + td.seg_start;
-        b1 = min(b0 + (uint64_t)KV_SEG_BASES, ((uint64_t)td.first + 1) * p.mask_stride);
-    } else {
-        b0 = (uint64_t)td.first * p.mask_stride;
-        b1 = ((uint64_t)td.first + td.count) * p.mask_stride;
-    }
-    uint64_t n = 0;
-    for (uint64_t w = (b0 >> 5) + threadIdx.x; w < ((b1 + 31) >> 5); w += 64) {
-        uint32_t bits = p.mask[w];
-        const uint64_t wlo = w << 5;
-        if (wlo < b0) bits &= ~0u << (uint32_t)(b0 - wlo);
-        if (wlo + 32 > b1) bits &= b1 > wlo ? (~0u >> (uint32_t)(wlo + 32 - b1)) : 0u;
-        n += (uint32_t)__popc(bits);
-    }
-    n = wave_sum_u64(n);
-    if (threadIdx.x == 0) p.tile_count[blockIdx.x] = (uint32_t)n;
-}
 
 // ---- host ----------------------------------------------------------------------------------------------
 // Bump pointer over an arena, every part rounded up to 256 bytes.  Without a base it only adds up: a layout written once as a function

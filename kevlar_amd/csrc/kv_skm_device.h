@@ -67,7 +67,7 @@ KV_HD uint32_t skm_order32(uint32_t x)
 // plus a STRAND BIT -- 1 when the canonical form is the reverse complement, i.e. the m-mer stands in the read the other way round.
 // The minimum over a k-mer's window then carries the strand of the minimizer, which (round 5) decides which strand of the K-MER is
 // its key: the one on which its minimizer is canonical.  Both strands of a k-mer have the same m-mers with the strand bits flipped, so
-// they agree on that key without either of them computing the other strand (kv_skm.hip, "oriented records").  Where they do not
+// they agree on that key without either of them computing the other strand (kv_skm_emit_device.h, "oriented records").  Where they do not
 // agree -- the minimal value occurs on both strands of one window, or the minimizer is its own reverse complement -- a k-mer is kept
 // under two keys, which costs a little deduplication and nothing else: adds compose, kmer_is_interesting() is a function of the hash.
 KV_HD uint32_t skm_order_s(uint32_t f, uint32_t r)
@@ -91,7 +91,7 @@ KV_HD void skm_bucket_of(uint32_t minv, uint32_t C1, uint32_t fbits, uint32_t &c
     fine = fbits ? (uint32_t)prod >> (32 - fbits) : 0u;
 }
 
-// (bit 47, the top of n's byte: the record's bases are the REVERSE COMPLEMENT of the read's -- an oriented record, kv_skm.hip; its k-mer j
+// (bit 47, the top of n's byte: the record's bases are the REVERSE COMPLEMENT of the read's -- an oriented record, kv_skm_emit_device.h; its k-mer j
 // then stands at read position pos + n - 1 - j)
 KV_HD uint64_t skm_header(uint64_t pos, uint32_t n, uint32_t fine, uint32_t rev = 0u) { return pos | ((uint64_t)(n | (rev << 7)) << SKM_POS_BITS) | ((uint64_t)fine << 48); }
 KV_HD uint64_t skm_hdr_pos(uint64_t h) { return h & ((1ull << SKM_POS_BITS) - 1ull); }

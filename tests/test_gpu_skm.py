@@ -1,4 +1,4 @@
-"""The super-k-mer front end (kv_skm.hip): reads cut into minimizer-bucketed super-k-mers, every distinct k-mer
+"""The super-k-mer front end (kv_skm.hip and its kv_skm_*_device.h kernels): reads cut into minimizer-bucketed super-k-mers, every distinct k-mer
 of a bucket counted once with its multiplicity and evaluated once by the novel scan.  It must give the same
 table bytes, occupancy, k-mer totals and hits as the scalar oracle (which adds and evaluates k-mer by k-mer, as
 khmer / kevlar/novel.py:123-169 do) -- for every k it accepts, every storage, with bands and masks, on ragged,
