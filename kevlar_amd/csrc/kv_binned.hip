@@ -118,14 +118,20 @@ __device__ __forceinline__ void rings_flush(const Rings<ItemT> &rs, uint32_t ns,
 }
 
 // Stage B's flush between rounds: the flush phase of rings_flush is instruction-bound (PMC: ~600 VALU
-// wave-instructions per wave and round, 4/5 of them broadcasting per-burst parameters and looping), so here
-// every lane that owns a ready stream copies its own burst: 32 (or R) items as 16-byte vectors, LDS read ->
-// global store, all streams of the wave in parallel.  Bursts are multiples of 32 items and the ring skew is 8,
+// wave-instructions per wave and round, 4/5 of them broadcasting per-burst parameters and looping), and a lane
+// that copies its own burst writes every 64-byte sector with four store instructions, each of which touches as
+// many lines as it has lanes.  So every lane that owns a ready stream only DECIDES (items, ring slot, place in
+// the segment) and enters its lane number in the wave's list in LDS (ballot + mbcnt); then the wave serves the list
+// sixteen streams a pass, four adjacent lanes a stream: lane l fetches the burst of the owner list[l >> 2] with two
+// shuffles and copies quarter l & 3 of each of its sectors, one 16-byte LDS read and one 16-byte global store,
+// so that a sector leaves whole, in one instruction.  Bursts are multiples of 32 items and the ring skew is 8,
 // so vectors stay 16-byte aligned in LDS and in the segment (u16 and u32 items alike).  The rare misfits (segment
 // nearly full, ring overrun that left the base unaligned) are left to rings_flush.
+// stream_base, stream_stride: stream s' segment starts at item stream_base + s * stream_stride; ready: 64 bytes per wave.
 template <typename ItemT, typename Overflow>
-__device__ __forceinline__ void rings_flush_lanes(const Rings<ItemT> &rs, uint32_t ns, uint32_t &written, uint64_t seg_base,
-                                                  uint32_t cap, ItemT *gbuf, Overflow overflow)
+__device__ __forceinline__ void rings_flush_quads(const Rings<ItemT> &rs, uint32_t ns, uint32_t &written, uint64_t seg_base,
+                                                  uint64_t stream_base, uint64_t stream_stride, uint32_t cap, ItemT *gbuf,
+                                                  uint8_t *ready, Overflow overflow)
 {
     constexpr uint32_t VEC = 16u / sizeof(ItemT);        // items per 16-byte vector
     constexpr uint32_t QUANTUM = 64u / sizeof(ItemT);    // bursts are whole 64-byte sectors
@@ -134,6 +140,7 @@ __device__ __forceinline__ void rings_flush_lanes(const Rings<ItemT> &rs, uint32
     const uint32_t s0 = wave * per_wave, s_end = min(ns, s0 + per_wave);
     const uint32_t s = s0 + lane;
     bool misfit = false;
+    uint32_t burst = 0, pos = 0;      // burst: first ring slot | items << 16 (both at most R <= BIN_RING_MAX); pos: its place in the segment
     if (s < s_end) {
         const uint32_t base = rs.base[s];
         const uint32_t avail = rs.cnt[s] - base;
@@ -143,12 +150,31 @@ __device__ __forceinline__ void rings_flush_lanes(const Rings<ItemT> &rs, uint32
         if (n) {
             if ((base & 7u) || written + n > cap || (newbase & 7u)) misfit = true;
             else {
-                const ItemT *ring = rs.ring + s * rs.R;
-                ItemT *dst = gbuf + seg_base + written;
-                for (uint32_t v = 0; v < n; v += VEC)
-                    *(uint4 *)(dst + v) = *(const uint4 *)(ring + ((base + v + rs.skew * s) & (rs.R - 1)));
+                burst = ((base + rs.skew * s) & (rs.R - 1)) | n << 16;
+                pos = written;
                 written += n;
                 rs.base[s] = newbase;
+            }
+        }
+    }
+    const unsigned long long todo = __ballot(burst != 0);
+    if (todo) {
+        uint8_t *list = ready + wave * 64u;
+        if (burst) list[__builtin_amdgcn_mbcnt_hi((uint32_t)(todo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)todo, 0u))] = (uint8_t)lane;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t nready = (uint32_t)__popcll(todo);
+        const uint32_t quarter = (lane & 3u) * VEC;
+        for (uint32_t q0 = 0; q0 < nready; q0 += 16) {          // wave-uniform: the shuffles need every owner lane active
+            const uint32_t q = q0 + (lane >> 2);
+            const uint32_t owner = list[min(q, nready - 1u)];
+            const uint32_t b = (uint32_t)__shfl((int)burst, (int)owner), p = (uint32_t)__shfl((int)pos, (int)owner);
+            if (q < nready) {
+                const uint32_t r = s0 + owner, n = b >> 16, slot = b & 0xffffu;
+                const ItemT *ring = rs.ring + r * rs.R;
+                ItemT *dst = gbuf + stream_base + (uint64_t)r * stream_stride + p;
+                for (uint32_t v = quarter; v < n; v += QUANTUM)
+                    *(uint4 *)(dst + v) = *(const uint4 *)(ring + ((slot + v) & (rs.R - 1)));
             }
         }
     }
@@ -414,14 +440,16 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
     rs.ring = (Out *)smem;
     rs.cnt = (uint32_t *)(smem + (((size_t)F * rs.R * sizeof(Out) + 15) & ~(size_t)15));
     rs.base = rs.cnt + F;
+    uint8_t *ready = (uint8_t *)(rs.base + F);      // BIN_B_THREADS bytes: every wave's list of lanes with a burst to flush
     for (uint32_t i = threadIdx.x; i < F; i += BIN_B_THREADS) { rs.cnt[i] = 0; rs.base[i] = 0; }
     __syncthreads();
     uint32_t written = 0;
     uint64_t seg_base = 0;
+    const uint64_t stream_base = ((uint64_t)s * F * g.nwgB + blockIdx.x) * g.cap2, stream_stride = (uint64_t)g.nwgB * g.cap2;
     {
         const uint32_t nwaves = BIN_B_THREADS >> 6, per_wave = (F + nwaves - 1) / nwaves;
         const uint32_t mine = (threadIdx.x >> 6) * per_wave + (threadIdx.x & 63);
-        if ((threadIdx.x & 63) < per_wave && mine < F) seg_base = (((uint64_t)s * F + mine) * g.nwgB + blockIdx.x) * g.cap2;
+        if ((threadIdx.x & 63) < per_wave && mine < F) seg_base = stream_base + mine * stream_stride;
     }
     Out *gbuf2 = (Out *)g.gbuf2;
     constexpr uint32_t SB = BIN_SLICE_BITS, OFFMASK = (1u << SB) - 1u;
@@ -486,7 +514,7 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
                     if (!ring_append(rs, slice_of(items[j]), fine_of(items[j]))) spill_coarse(items[j]);
             }
             __syncthreads();
-            rings_flush_lanes(rs, F, written, seg_base, (uint32_t)g.cap2, gbuf2, overflow);
+            rings_flush_quads(rs, F, written, seg_base, stream_base, stream_stride, (uint32_t)g.cap2, gbuf2, ready, overflow);
             __syncthreads();
         }
     }
@@ -984,7 +1012,7 @@ int kv_bin_finish(kv_sketch *s, BinPlan &plan, bool added_from_ctr, uint64_t n_a
     {
         KvProfScope prof(plan.weighted ? "k_bin_split_w" : "k_bin_split");
         const size_t isz = plan.weighted ? 4 : 2;
-        const size_t lds = (((size_t)g.F * g.ringB * isz + 15) & ~(size_t)15) + (size_t)g.F * 2 * 4;
+        const size_t lds = (((size_t)g.F * g.ringB * isz + 15) & ~(size_t)15) + (size_t)g.F * 2 * 4 + BIN_B_THREADS;
         if (plan.weighted) {
             ensure_dynamic_lds((k_bin_split<true>), lds);
             hipLaunchKernelGGL((k_bin_split<true>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
