@@ -99,6 +99,13 @@ int kv_prof_enable(int on);
 int kv_prof_reset(void);
 int kv_prof_get(const char *kernel, double *ms, uint64_t *launches);
 int kv_prof_names(char *buf, size_t cap); /* comma separated list of kernel names seen     */
+/* kv_skm_last_instances: no reference call site; for tests.  The template instances of the super-k-mer kernels (DESIGN.md
+ * section 4.1: cut, split, count, scans, route and their loose-list companions) that the last call into that front end launched on
+ * the calling thread's stream, in launch order, comma separated and without blanks ("k_skm_emit_lane<1,8>,k_skm_split_sorted<3>,
+ * ...": a comma between angle brackets belongs to a name).  kv_prof_get says that a family ran, this says which instance a host
+ * planner chose.  Empty when that call launched none; KV_ERR_CAPACITY when the list and its terminating zero do not fit the
+ * `cap` bytes of `out`.                                                                                                       */
+int kv_skm_last_instances(char *out, uint64_t cap);
 
 /* ---- host-side helpers (no table access) --------------------------------------------- */
 /* khmer table sizing: the n largest primes below `target`, odd numbers downwards

@@ -33,6 +33,30 @@
 namespace {
 
 // ---- host ----------------------------------------------------------------------------------------------
+// A kernel instance together with its name.  SKM_INST(k_skm_emit<16>) yields the function pointer and the text of that very
+// expression, so the name cannot drift from the kernel; skm_launching() hands the pointer to the launch and notes the name in the
+// stream's list, which kv_skm_last_instances reports (tests/instances_common.py holds every instance to a case by that report).
+// Every entry point of this file that can launch a super-k-mer kernel empties the list first (skm_launched_begin).
+template <typename F> struct SkmInst { F *fn; const char *name; };
+template <typename F> SkmInst<F> skm_inst(F *fn, const char *name) { return SkmInst<F>{fn, name}; }
+#define SKM_INST(...) skm_inst(__VA_ARGS__, #__VA_ARGS__)
+struct SkmLaunched { std::mutex mu; std::string names; };
+KvPerStream<SkmLaunched> g_skm_launched;
+void skm_launched_begin(hipStream_t st)
+{
+    SkmLaunched &l = g_skm_launched.get(st);
+    std::lock_guard<std::mutex> lk(l.mu);
+    l.names.clear();
+}
+template <typename F> F *skm_launching(const SkmInst<F> &k, hipStream_t st)
+{
+    SkmLaunched &l = g_skm_launched.get(st);
+    std::lock_guard<std::mutex> lk(l.mu);
+    if (!l.names.empty()) l.names += ',';
+    for (const char *c = k.name; *c; ++c) if (*c != ' ') l.names += *c;
+    return k.fn;
+}
+
 // Bump pointer over an arena, every part rounded up to 256 bytes.  Without a base it only adds up: a layout written once as a function
 // of an SkmCarve gives the total for KvArena::need and then the pointers, and the two cannot drift apart.
 struct SkmCarve {
@@ -225,11 +249,10 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
         const uint32_t wpr = (reads->uni_len + 15u) / 16u;
         const size_t lds = (size_t)skm_lane_slice_words(wpr) * 4 * (SKM_LANE_THREADS / 64);
         const uint64_t n_groups = (reads->n_reads + 63) / 64;
-        void (*kernel)(ReadsDev, SkmGeom, uint32_t, uint32_t);
-        if (g.w == SKM_LANE_B) kernel = wpr <= 8 ? k_skm_emit_lane<1, 8> : k_skm_emit_lane<1, 16>;
-        else kernel = wpr <= 8 ? k_skm_emit_lane<2, 8> : k_skm_emit_lane<2, 16>;
-        kv_ensure_dynamic_lds((const void *)kernel, lds);
-        hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(SKM_LANE_THREADS), lds, st, reads_dev(reads), g, (uint32_t)n_groups, SKM_LANE_FLUSH_BLOCKS);
+        auto kernel = wpr <= 8 ? SKM_INST(k_skm_emit_lane<1, 8>) : SKM_INST(k_skm_emit_lane<1, 16>);
+        if (g.w != SKM_LANE_B) kernel = wpr <= 8 ? SKM_INST(k_skm_emit_lane<2, 8>) : SKM_INST(k_skm_emit_lane<2, 16>);
+        kv_ensure_dynamic_lds((const void *)kernel.fn, lds);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(g.nwg1), dim3(SKM_LANE_THREADS), lds, st, reads_dev(reads), g, (uint32_t)n_groups, SKM_LANE_FLUSH_BLOCKS);
         return;
     }
     if (const uint32_t R = skm_wave_plan(g, reads, &ch)) {
@@ -244,19 +267,16 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
         const uint32_t per_ticket = (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(SKM_MT_PER_TICKET, n_mt / (2 * waves)));
         const uint64_t per_wave = (uint64_t)g.quota1 * reads->uni_per_tile / R / nwaves + per_ticket;
         const uint32_t quota_mt = (uint32_t)std::min<uint64_t>(kv_round_up(per_wave, per_ticket), 0xfffffff0ull);
-        void (*kernel)(ReadsDev, SkmGeom, uint32_t, uint32_t, uint32_t, uint32_t);
-        if (threads == 1024)
-            kernel = ch == 16 ? k_skm_emit_wave<16, 1024> : k_skm_emit_wave<8, 1024>;
-        else
-            kernel = ch == 16 ? k_skm_emit_wave<16, 512> : k_skm_emit_wave<8, 512>;
-        kv_ensure_dynamic_lds((const void *)kernel, lds);
-        hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(threads), lds, st, reads_dev(reads), g, R, (uint32_t)n_mt, quota_mt, per_ticket);
+        auto kernel = ch == 16 ? SKM_INST(k_skm_emit_wave<16, 512>) : SKM_INST(k_skm_emit_wave<8, 512>);
+        if (threads == 1024) kernel = ch == 16 ? SKM_INST(k_skm_emit_wave<16, 1024>) : SKM_INST(k_skm_emit_wave<8, 1024>);
+        kv_ensure_dynamic_lds((const void *)kernel.fn, lds);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(g.nwg1), dim3(threads), lds, st, reads_dev(reads), g, R, (uint32_t)n_mt, quota_mt, per_ticket);
         return;
     }
     const size_t lds = ((size_t)g.np_max / 16 + KV_TILE_MAX_READS + 8 + (size_t)g.np_max + 96) * 4 + (((size_t)g.np_max + 96 + 1) & ~(size_t)1) * 2;
-    void (*kernel)(ReadsDev, uint32_t, SkmGeom) = g.w > 16 ? k_skm_emit<16> : k_skm_emit<8>;
-    kv_ensure_dynamic_lds((const void *)kernel, lds);
-    hipLaunchKernelGGL(kernel, dim3(g.nwg1), dim3(SKM_THREADS1), lds, st, reads_dev(reads), reads->n_tiles, g);
+    const auto kernel = g.w > 16 ? SKM_INST(k_skm_emit<16>) : SKM_INST(k_skm_emit<8>);
+    kv_ensure_dynamic_lds((const void *)kernel.fn, lds);
+    hipLaunchKernelGGL(skm_launching(kernel, st), dim3(g.nwg1), dim3(SKM_THREADS1), lds, st, reads_dev(reads), reads->n_tiles, g);
 }
 
 void skm_launch_split(const SkmGeom &g, hipStream_t st)
@@ -267,21 +287,21 @@ void skm_launch_split(const SkmGeom &g, hipStream_t st)
     const bool sorted = s2 ? strcmp(s2, "sorted") == 0 && g.F2 <= SKM_S2_MAXF : g.F2 <= SKM_S2_MAXF;
     if (sorted) {
         const size_t lds = (size_t)SKM_S2_CHUNK * g.recw * 8;
-        void (*kernel)(SkmGeom) = g.recw == 2 ? k_skm_split_sorted<2> : k_skm_split_sorted<3>;
-        if (g.recw > 3) kernel = k_skm_split_sorted<4>;
-        kv_ensure_dynamic_lds((const void *)kernel, lds);
-        hipLaunchKernelGGL(kernel, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
+        auto kernel = g.recw == 2 ? SKM_INST(k_skm_split_sorted<2>) : SKM_INST(k_skm_split_sorted<3>);
+        if (g.recw > 3) kernel = SKM_INST(k_skm_split_sorted<4>);
+        kv_ensure_dynamic_lds((const void *)kernel.fn, lds);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), lds, st, g);
     } else {
-        if (g.recw == 2) hipLaunchKernelGGL(k_skm_split<true>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), 0, st, g);
-        else hipLaunchKernelGGL(k_skm_split<false>, dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), 0, st, g);
+        const auto kernel = g.recw == 2 ? SKM_INST(k_skm_split<true>) : SKM_INST(k_skm_split<false>);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(g.nwg2, g.C1), dim3(SKM_THREADS2), 0, st, g);
     }
 }
 
 // a loose-list kernel, grid-stride over the list: its instance for one-word or two-word keys
 template <typename... A>
-void skm_launch_loose(void (*one)(SkmGeom, A...), void (*two)(SkmGeom, A...), hipStream_t st, const SkmGeom &g, typename std::common_type<A>::type... args)
+void skm_launch_loose(SkmInst<void(SkmGeom, A...)> one, SkmInst<void(SkmGeom, A...)> two, hipStream_t st, const SkmGeom &g, typename std::common_type<A>::type... args)
 {
-    hipLaunchKernelGGL(g.kw == 1 ? one : two, dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, args...);
+    hipLaunchKernelGGL(skm_launching(g.kw == 1 ? one : two, st), dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, args...);
 }
 
 // occurrences the bucket kernels sent through the loose list (they missed a full LDS table), from a host copy of the counters
@@ -529,6 +549,7 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
                    uint64_t n_kmers, int nbands, uint64_t *n_added)
 {
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     const int k = s->h.ksize;
@@ -607,23 +628,23 @@ int kv_consume_skm(kv_sketch *s, const kv_reads *reads, const ConsumeFilter &fil
         const uint32_t ns = (uint32_t)(plan.g.T * plan.g.C);
         // the fixed-k instances count a key's occurrences in 16 bits (k_skm_count, PL): only for buckets that cannot hold 65536 of them
         const bool fixed_k = !sg.force_loose && !kv_knob("KV_SKM_ANY_K") && (uint64_t)sg.nwg2 * sg.cap2 * (uint64_t)sg.ncap < 65536ull;
-        void (*kernel)(SkmGeom, const SketchDev *, const SketchDev *, ConsumeFilter, BinGeom) =
-            sg.kw == 1 ? (sg.force_loose ? k_skm_count<1, 4096, true, 0> : k_skm_count<1, 4096, false, 0>) : (sg.force_loose ? k_skm_count<2, 2048, true, 0> : k_skm_count<2, 2048, false, 0>);
+        auto kernel = sg.kw == 1 ? (sg.force_loose ? SKM_INST(k_skm_count<1, 4096, true, 0>) : SKM_INST(k_skm_count<1, 4096, false, 0>))
+                                 : (sg.force_loose ? SKM_INST(k_skm_count<2, 2048, true, 0>) : SKM_INST(k_skm_count<2, 2048, false, 0>));
         bool pl = false;         // a fixed-k instance: 4 KB of product tables where the others keep 1 KB of ASCII
-        if (sg.k == 31 && sg.recw == 3 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31>; pl = true; }
+        if (sg.k == 31 && sg.recw == 3 && fixed_k) { kernel = SKM_INST(k_skm_count<1, SKM_TS31, false, 31>); pl = true; }
         if (sg.compact) {       // 16-byte records (sg.recw == 2): their own instances
-            kernel = sg.force_loose ? k_skm_count<1, 4096, true, 0, true> : k_skm_count<1, 4096, false, 0, true>;
+            kernel = sg.force_loose ? SKM_INST(k_skm_count<1, 4096, true, 0, true>) : SKM_INST(k_skm_count<1, 4096, false, 0, true>);
             pl = false;
-            if (sg.k == 31 && fixed_k) { kernel = k_skm_count<1, SKM_TS31, false, 31, true>; pl = true; }
+            if (sg.k == 31 && fixed_k) { kernel = SKM_INST(k_skm_count<1, SKM_TS31, false, 31, true>); pl = true; }
         }
         // (BASELINE.json configs[4]: k = 51 -- two-word keys, three murmur blocks + a 3-byte tail)
-        if (sg.k == 51 && sg.recw == 4 && fixed_k) { kernel = k_skm_count<2, SKM_TS51, false, 51>; pl = true; }
+        if (sg.k == 51 && sg.recw == 4 && fixed_k) { kernel = SKM_INST(k_skm_count<2, SKM_TS51, false, 51>); pl = true; }
         const size_t lds = ((pl ? 1024 : 256) + ((ns + 3u) & ~3u) + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
-        hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, (const SketchDev *)s->d_desc, d_mask, filter, plan.g);
     }
     {
         KvProfScope prof("k_skm_loose_count");
-        skm_launch_loose(k_skm_loose_count<1>, k_skm_loose_count<2>, st, sg, s->d_desc, d_mask, filter, plan.g);
+        skm_launch_loose(SKM_INST(k_skm_loose_count<1>), SKM_INST(k_skm_loose_count<2>), st, sg, s->d_desc, d_mask, filter, plan.g);
     }
     KV_HIP(hipGetLastError());
     // a lost record (loose list overflow) must stop the apply stage, which looks at the partition's own flag
@@ -703,6 +724,7 @@ bool kv_skm_list_ready(const kv_reads *reads, int ksize)
 int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_kmers)
 {
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     const int k = p.hp.k;
     // the bucketed batch may sit in the arena of whichever stream counted it
     SkmIndex *idx = nullptr;
@@ -764,9 +786,8 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
         KvProfScope prof("k_skm_novel_list");
         idx->list.attach(sg);
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
-        void (*kernel)(SkmGeom, ReadsDev, NovelParams, SkmAblSet) =
-            sg.kw == 1 ? k_skm_novel_list<1, 2048> : k_skm_novel_list<2, 1024>;
-        hipLaunchKernelGGL(kernel, dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, pl, abls);
+        const auto kernel = sg.kw == 1 ? SKM_INST(k_skm_novel_list<1, 2048>) : SKM_INST(k_skm_novel_list<2, 1024>);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, pl, abls);
         if (p.ab_keys) hipLaunchKernelGGL(k_ab_fill, dim3(2048), dim3(256), 0, st, p);
         if (p.ab_list && kv_knob("KV_SKM_VERBOSE")) {
             unsigned int claimed = 0;
@@ -777,12 +798,12 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     } else {
         KvProfScope prof("k_skm_novel");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw)) * 4;
-        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_novel<1, 4096>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
-        else hipLaunchKernelGGL((k_skm_novel<2, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
+        const auto kernel = sg.kw == 1 ? SKM_INST(k_skm_novel<1, 4096>) : SKM_INST(k_skm_novel<2, 2048>);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, rd, p, abls);
     }
     {
         KvProfScope prof("k_skm_loose_novel");
-        skm_launch_loose(k_skm_loose_novel<1>, k_skm_loose_novel<2>, st, sg, rd, p);
+        skm_launch_loose(SKM_INST(k_skm_loose_novel<1>), SKM_INST(k_skm_loose_novel<2>), st, sg, rd, p);
     }
     kv_tile_hits_launch(reads, p, st);
     KV_HIP(hipGetLastError());
@@ -797,13 +818,14 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     return KV_OK;
 }
 
-static void skm_launch_route(void (*kernel)(SkmGeom, HashParams, KvRouteSink), const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st);
+static void skm_launch_route(SkmInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st);
 
 int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, int ndest,
                           int (*alloc)(void *ctx, uint32_t nwg, KvRouteSink *sink), void *ctx)
 {
     KV_REQUIRE(ndest >= 1 && ndest <= SKM_ROUTE_MAX_DEST, KV_ERR_ARG, "kv_skm_route_distinct: 1..%d destinations", SKM_ROUTE_MAX_DEST);
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     { const int rc = skm_build(idx, reads, ksize, n_kmers, st, idx.distinct_hint); if (rc != KV_OK) return rc; }
@@ -812,7 +834,7 @@ int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, in
     KvRouteSink rs;
     memset(&rs, 0, sizeof(rs));
     { const int rc = alloc(ctx, nwg3, &rs); if (rc != KV_OK) return rc; }
-    skm_launch_route(sg.kw == 1 ? k_skm_route<1, 4096> : k_skm_route<2, 2048>, sg, ksize, rs, st);
+    skm_launch_route(sg.kw == 1 ? SKM_INST(k_skm_route<1, 4096>) : SKM_INST(k_skm_route<2, 2048>), sg, ksize, rs, st);
     KV_HIP(hipGetLastError());
     unsigned long long sctr[SKM_CTR_DISTINCT + 1] = {0};
     KV_HIP(hipMemcpyAsync(sctr, sg.ctr, sizeof(sctr), hipMemcpyDeviceToHost, st));
@@ -832,16 +854,16 @@ int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, in
 }
 
 // the buckets' distinct k-mers through `kernel`, the instance of k_skm_route for the geometry, then the loose list's
-static void skm_launch_route(void (*kernel)(SkmGeom, HashParams, KvRouteSink), const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st)
+static void skm_launch_route(SkmInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st)
 {
     const HashParams hp = make_hash_params(k, HF_MURMUR);
     {
         KvProfScope prof("k_skm_route");
         const size_t lds = (256 + (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(g.sbw)) * 4;
-        hipLaunchKernelGGL(kernel, dim3(skm_nwg3(g)), dim3(SKM_THREADS3), lds, st, g, hp, rs);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(skm_nwg3(g)), dim3(SKM_THREADS3), lds, st, g, hp, rs);
     }
     KvProfScope prof("k_skm_loose_route");
-    skm_launch_loose(k_skm_loose_route<1>, k_skm_loose_route<2>, st, g, hp, rs);
+    skm_launch_loose(SKM_INST(k_skm_loose_route<1>), SKM_INST(k_skm_loose_route<2>), st, g, hp, rs);
 }
 
 // ---- minimizer-sharded exchange (kevlar_amd/shardrun.py) ------------------------------------------------
@@ -916,6 +938,7 @@ int kv_skm_mex_emit(const kv_reads *reads, const kv_mex_plan *plan, uint64_t rea
                     uint64_t *d_out, uint64_t out_cap_words, uint64_t *records_per_dest, int *packed)
 {
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
@@ -988,6 +1011,7 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
 {
     KV_REQUIRE(plan && my_dest >= 0 && my_dest < plan->ndest && n_src >= 1, KV_ERR_ARG, "kv_mex_route: bad argument");
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     idx.drop(SkmIndex::BATCH | SkmIndex::MEX_SCAN);
@@ -1096,7 +1120,7 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
             idx.dl_refused = std::min(idx.dl_refused, b_all);
         }
     }
-    skm_launch_route(g.compact ? k_skm_route<1, 4096, true> : g.kw == 1 ? k_skm_route<1, 4096> : k_skm_route<2, 2048>, g, plan->ksize, rs, st);
+    skm_launch_route(g.compact ? SKM_INST(k_skm_route<1, 4096, true>) : g.kw == 1 ? SKM_INST(k_skm_route<1, 4096>) : SKM_INST(k_skm_route<2, 2048>), g, plan->ksize, rs, st);
     KV_HIP(hipGetLastError());
     // the packing of the pairs (the caller's `after`) is queued behind the route kernels and everything is waited for once: its
     // kernels bound what they write by the output's capacity, so what the counters say can be judged afterwards
@@ -1135,6 +1159,7 @@ int kv_skm_mex_route(const kv_mex_plan *plan, int my_dest, const uint64_t *d_rec
 int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8_t *d_abund, uint64_t cap, uint64_t *n_hits)
 {
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     if (!idx.mex_scan_ready || idx.k != ksize) {
@@ -1151,9 +1176,9 @@ int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8
     {
         KvProfScope prof("k_skm_set_hits");
         const size_t lds = (size_t)(SKM_THREADS3 / 64) * skm_wave_scratch_words(sg.sbw) * 4;
-        if (sg.kw == 1) hipLaunchKernelGGL((k_skm_set_hits<1, 2048>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
-        else hipLaunchKernelGGL((k_skm_set_hits<2, 1024>), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
-        skm_launch_loose(k_skm_loose_set_hits<1>, k_skm_loose_set_hits<2>, st, sg, p, out);
+        const auto kernel = sg.kw == 1 ? SKM_INST(k_skm_set_hits<1, 2048>) : SKM_INST(k_skm_set_hits<2, 1024>);
+        hipLaunchKernelGGL(skm_launching(kernel, st), dim3(nwg3), dim3(SKM_THREADS3), lds, st, sg, p, out);
+        skm_launch_loose(SKM_INST(k_skm_loose_set_hits<1>), SKM_INST(k_skm_loose_set_hits<2>), st, sg, p, out);
     }
     KV_HIP(hipGetLastError());
     KvReadback back;
@@ -1176,6 +1201,7 @@ int kv_skm_mex_scan_set(const NovelParams &p, int ksize, uint64_t *d_tags, uint8
 int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32_t *d_cnt, uint64_t *d_out, uint64_t *records_per_dest)
 {
     hipStream_t st = kv_stream();
+    skm_launched_begin(st);
     SkmIndex &idx = skm_index_for(st);
     std::lock_guard<std::mutex> lk(idx.mu);
     const uint64_t n_seg = plan->cnt_entries;
@@ -1195,5 +1221,15 @@ int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32
     KV_HIP(rb_err);
     KV_HIP(rb.wait(st));
     for (int d = 0; d < plan->ndest; ++d) records_per_dest[d] = *bounds[d + 1] - *bounds[d];
+    return KV_OK;
+}
+
+// the instances the last call into this file launched on the calling thread's stream (include/kvsketch.h)
+extern "C" int kv_skm_last_instances(char *out, uint64_t cap)
+{
+    SkmLaunched &l = g_skm_launched.get(kv_stream());
+    std::lock_guard<std::mutex> lk(l.mu);
+    KV_REQUIRE(out && l.names.size() + 1 <= cap, KV_ERR_CAPACITY, "kv_skm_last_instances: buffer too small");
+    memcpy(out, l.names.c_str(), l.names.size() + 1);
     return KV_OK;
 }

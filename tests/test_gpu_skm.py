@@ -5,6 +5,7 @@ khmer / kevlar/novel.py:123-169 do) -- for every k it accepts, every storage, wi
 long and non-ACGT reads, on skewed input, and when its segments or LDS tables overflow into the loose list."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
@@ -13,6 +14,14 @@ pytestmark = pytest.mark.gpu
 
 KNOBS = ('KV_COUNT_PATH', 'KV_NOVEL_PATH', 'KV_SKM_BUCKET_KMERS', 'KV_SKM_CAP_PCT', 'KV_SKM_LOOSE_CAP', 'KV_SKM_NO_REUSE', 'KV_SKM_FORCE_LOOSE', 'KV_SKM_DL', 'KV_SKM_ANY_K',
          'KV_BIN_2BIT', 'KV_NOVEL_2BIT', 'KV_NOVEL_BITS')
+
+
+def instances():
+    """the super-k-mer kernel instances the last call launched, in launch order (kv_skm_last_instances)"""
+    from kevlar_amd import _lib
+    buf = ctypes.create_string_buffer(1024)
+    assert _lib.load().kv_skm_last_instances(buf, len(buf)) == 0
+    return re.split(r',(?![^<]*>)', buf.value.decode())          # (a name's own commas stand between its angle brackets)
 
 
 def launches(name):
@@ -113,9 +122,14 @@ def test_scratch_trim_between_count_and_scan(hk, ok, skm):
 
 @pytest.mark.parametrize('read_len,k', [(36, 31), (75, 25), (150, 31), (151, 51), (251, 31), (600, 31)])
 def test_skm_equal_length_reads_of_other_lengths(hk, ok, skm, read_len, k):
-    """batches of equal-length reads handed over as packed words (what the device ingest and the generators produce) take the
-    wave-per-group S1 kernel (k_skm_emit_wave): one packed word and one chunk of k-mer starts per lane, so the group size, the
-    padding of a read's last word and the chunks per read all follow the read length"""
+    """batches of equal-length reads handed over as packed words (what the device ingest and the generators produce): the layout is
+    arithmetic, and skm_launch_emit chooses S1 by k and the read length -- the lane-per-read cut (k_skm_emit_lane: k = 31 or 51, up to
+    224 bases) for (36, 31), (150, 31) and (151, 51); the wave-per-group kernel (k_skm_emit_wave: one packed word and one chunk of k-mer
+    starts per lane) for (75, 25) and (251, 31); the tile kernel (k_skm_emit) for (600, 31), where a wave would hold a single read.  The
+    group size, the padding of a read's last word and the chunks or blocks per read all follow the read length.
+    (tests/instances_common.py holds every instance of these families at the planners' edges.)"""
+    s1_family = {(36, 31): 'k_skm_emit_lane', (75, 25): 'k_skm_emit_wave', (150, 31): 'k_skm_emit_lane', (151, 51): 'k_skm_emit_lane',
+                 (251, 31): 'k_skm_emit_wave', (600, 31): 'k_skm_emit'}[(read_len, k)]
     from kevlar_amd import synth
     os.environ['KV_SKM_BUCKET_KMERS'] = '4096'
     os.environ['KV_SKM_DL'] = '1'
@@ -132,6 +146,7 @@ def test_skm_equal_length_reads_of_other_lengths(hk, ok, skm, read_len, k):
         batches = {s: hk.ReadBatch.from_packed(words[s], read_len) for s in names}
         for s in ('mother', 'father', 'proband'):
             assert dev[s].consume_batch(batches[s]) == n * (read_len - k + 1)
+            assert instances()[0].split('<')[0] == s1_family
             bases, offs = ok.concat_reads(reads[s])
             ok.consume_reads(ref[s], bases, offs, n)
             assert_same_tables(dev[s], ref[s])
