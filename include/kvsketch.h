@@ -536,6 +536,40 @@ int kv_align_batch(const char *tbases, const uint64_t *toffsets, uint64_t n_targ
                    uint32_t *runs, uint64_t capacity, uint64_t *n_runs);
 int kv_align_stats(uint64_t *stats_out);
 
+/* ---- from alignments to calls, the second half of `kevlar call` (kevlar/cigar.py:46-71, kevlar/varmap.py:49-54, 157-161,
+ * 231-317; kv_call.hip) ---------------------------------------------------------------------------------------------------
+ * The reference walks every aligned base of every match block for mismatches (varmap.py:245) and searches every call's window
+ * for every interesting k-mer of the contig and its reverse complement (varmap.py:309-317).  Here one batch of aligned jobs is
+ * scanned on the device and every job gets one fixed-size record; the host cuts alleles and windows by slicing (DESIGN.md
+ * section 11).
+ * Targets, queries and jobs are those of the alignment above.  With the reverse flag set the job reads the query as
+ * kevlar_amd.sequence.revcom gives it (the IUPAC codes complemented, lower case to upper, every other byte itself), reversed.
+ * The CIGAR of job k is run_counts[k] runs at runs[run_offsets[k] ..] as the alignment returns them (n_runs = the size of
+ * `runs`); any list of M / I / D runs of at least one base that consumes exactly both sequences is taken, each run a block.
+ * Query q carries the interesting k-mers ik_offsets[q] .. ik_offsets[q + 1] of `ikmers`, each an (offset, ksize) pair in the
+ * coordinates of the contig as given, whatever the strand.  ksize >= 1; mindist 0 switches the trimming off.
+ * records[KV_CALL_RECORD_WORDS * k ..] of job k:
+ *   [0]  1 when the tokenizer's end check folded the last block into the third-last (cigar.py:46-71), else 0
+ *   [1]  the class of the block list after the end check (varmap.py:49-54): KV_CALL_NONE / KV_CALL_SNV / KV_CALL_INDEL
+ *   [2 .. 8], [9 .. 15]  the scanned blocks: the match block of an snv (the second stays zero), or the left and the right flank
+ *        of an indel: length; mismatches trimmed as terminal (mm < mindist or length - mm < mindist); mismatches left; the
+ *        first four of those in block coordinates (0xFFFFFFFF where there is none).  A block shorter than ksize is not
+ *        scanned (varmap.py:243): its counts are 0.  Bytes compare as they are, case included.  A folded block is the
+ *        concatenation of its two segments, and positions are taken in that.
+ *   [16 .. 24]  the IKMERS number of the calls: [16] the indel's, [17 .. 20] the SNVs of the first block, [21 .. 24] of the second
+ *        (only where the block has 1 to 4 mismatches left; else 0).  The window is the reference's ALTWINDOW; an interesting
+ *        k-mer counts once when its bases or their reverse complement occur anywhere in it, duplicates in the list each time.
+ * An interesting k-mer that reaches past its contig or has no bases, runs that do not consume exactly both sequences, a run
+ * of length 0 or of another op, an empty sequence, an index out of range: KV_ERR_ARG before anything touches the device.     */
+#define KV_CALL_RECORD_WORDS 32
+#define KV_CALL_NONE 0
+#define KV_CALL_SNV 1
+#define KV_CALL_INDEL 2
+int kv_call_scan(const char *tbases, const uint64_t *toffsets, uint64_t n_targets, const char *qbases, const uint64_t *qoffsets,
+                 uint64_t n_queries, const uint32_t *jobs, uint64_t n_jobs, const uint64_t *run_offsets, const uint32_t *run_counts,
+                 const uint32_t *runs, uint64_t n_runs, const uint64_t *ik_offsets, const uint32_t *ikmers, int ksize, int mindist,
+                 uint32_t *records);
+
 #ifdef __cplusplus
 }
 #endif

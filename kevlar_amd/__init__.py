@@ -127,6 +127,9 @@ from kevlar_amd import reference  # noqa: E402
 from kevlar_amd import localize  # noqa: E402
 from kevlar_amd import alignment  # noqa: E402
 from kevlar_amd.alignment import contig_align as align  # noqa: E402
+from kevlar_amd import cigar  # noqa: E402
+from kevlar_amd import vcf  # noqa: E402
+from kevlar_amd import varmap  # noqa: E402       (kevlar_amd.call is imported by name: it is also the command `python -m kevlar_amd.call`)
 from kevlar_amd import cli  # noqa: E402
 
 

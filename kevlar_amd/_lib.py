@@ -147,6 +147,7 @@ SIGNATURES = {
     'kv_align_plan': (i32, [vp, vp, u64, u64, vp, vp, u64p]),
     'kv_align_batch': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, i32, i32, i32, i32, u64, vp, vp, vp, vp, u64, u64p]),
     'kv_align_stats': (i32, [vp]),
+    'kv_call_scan': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, i32, i32, vp]),
 }
 
 
