@@ -264,6 +264,9 @@ int kv_novel_scan(kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, i
  * batch after batch reads the hits of one scan while the next count runs.                                                          */
 int kv_hits_lazy(int on);
 int kv_hits_count(const kv_hits *h, uint64_t *n_hits, uint64_t *n_discarded_reads);
+/* the scan's building block on its own: d_base[i] = d_counts[0] + ... + d_counts[i - 1] for i = 0 .. n (n + 1 values, the total
+ * last), both DEVICE pointers; runs on the calling thread's stream and returns when it is done                              */
+int kv_excl_scan_u32(const uint32_t *d_counts, uint32_t n, uint64_t *d_base);
 /* copies hits sorted by (read, offset); abund has n_hits * (ncase+nctrl) entries          */
 int kv_hits_fetch(const kv_hits *h, uint32_t *read, uint32_t *offset, uint8_t *abund,
                   uint64_t cap_hits, uint32_t *discarded_reads, uint64_t cap_discarded);

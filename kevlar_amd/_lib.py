@@ -109,6 +109,7 @@ SIGNATURES = {
     'kv_add_hashes': (i32, [vp, u64p, u64, u8p]),
     'kv_novel_scan': (i32, [vpp, i32, vpp, i32, vp, u64, i32, i32, i32, i32, i32, i32, vp, u64, vpp]),
     'kv_hits_count': (i32, [vp, u64p, u64p]),
+    'kv_excl_scan_u32': (i32, [vp, u32, vp]),
     'kv_hits_fetch': (i32, [vp, u32p, u32p, u8p, u64, u32p, u64]),
     'kv_hits_view': (i32, [vp, ctypes.POINTER(u32p), ctypes.POINTER(u32p), ctypes.POINTER(u8p), ctypes.POINTER(u32p)]),
     'kv_hits_shadow': (i32, [vp, ctypes.POINTER(u32p), ctypes.POINTER(u32p), u64p]),

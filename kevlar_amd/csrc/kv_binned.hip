@@ -723,13 +723,8 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
             for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) l4[j] = tab[j];
         if (threadIdx.x < g.nwgB) seg_cnt[threadIdx.x] = myc;
         const uint32_t myv = (myc + VEC - 1) / VEC;
+        const uint32_t incl = wave_incl_scan(myv);
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        uint32_t incl = myv;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
         if (lane == 63) wsum[wave] = incl;
         if (threadIdx.x == THREADS - 1) { flag_sh = flag != 0 ? 1u : 0u; fresh_sh = 0; }
         __syncthreads();

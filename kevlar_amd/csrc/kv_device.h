@@ -2,6 +2,7 @@
 // LDS-staged ASCII, Barrett modulo, table access, tile staging.  Include inside a .hip file.
 #pragma once
 #include "kv_internal.h"
+#include "kv_scan_device.h"
 
 namespace {
 
@@ -222,13 +223,7 @@ struct ReadsDev {
 // exclusive prefix sums over <= 128 reads by wave 0 (two entries per lane)
 __device__ __forceinline__ uint32_t wave_excl_scan2(uint32_t a, uint32_t b, uint32_t &excl_b, uint32_t &total)
 {
-    const int lane = threadIdx.x & 63;
-    uint32_t s = a + b, incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
+    const uint32_t s = a + b, incl = wave_incl_scan(s);
     total = __shfl(incl, 63);
     const uint32_t excl_a = incl - s;
     excl_b = excl_a + a;

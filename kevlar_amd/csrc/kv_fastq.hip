@@ -6,7 +6,7 @@
 //
 //   file image (mmap) --H2D, compressed--> k_inflate (one wave per member) --> text in HBM
 //   k_count_lines   newlines per 16-KB chunk            \
-//   k_chunk_scan    exclusive scan of the chunk counts    > start of every line
+//   k_excl_scan_u32 exclusive scan of the chunk counts    > start of every line
 //   k_line_starts   byte offset of each line start      /
 //   k_records       four lines = one record: checks '@' / '+', start and length of the sequence line
 //   k_pack_text     2-bit packs the sequence lines into the kv_reads layout (same rules as k_pack_reads)
@@ -73,35 +73,6 @@ __global__ __launch_bounds__(FQ_THREADS) void k_count_lines(const uint8_t *__res
     if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// exclusive scan of n 32-bit counts into 64-bit bases, base[n] = total (single 1024-thread workgroup)
-__global__ __launch_bounds__(1024) void k_chunk_scan(const uint32_t *counts, uint32_t n, uint64_t *base)
-{
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t i0 = 0; i0 < n; i0 += 1024) {
-        const uint32_t i = i0 + threadIdx.x;
-        const uint64_t v = i < n ? counts[i] : 0;
-        uint64_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t up = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        if (i < n) base[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) base[n] = carry;
-}
-
 // line_start[l + 1] = offset behind the l-th newline (line_start[0] = 0 is set by the host); only the first
 // `max_lines` lines are recorded
 __global__ __launch_bounds__(FQ_THREADS) void k_line_starts(const uint8_t *__restrict__ text, uint64_t n, const uint64_t *__restrict__ base,
@@ -116,12 +87,7 @@ __global__ __launch_bounds__(FQ_THREADS) void k_line_starts(const uint8_t *__res
         const uint64_t at = c0 + i0 + threadIdx.x * 16u;
         uint32_t mask = newline_mask_at(text, at, n);
         const uint32_t c = (uint32_t)__popc(mask);
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += up;
-        }
+        const uint32_t incl = wave_incl_scan(c);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         uint32_t before = 0, all = 0;
@@ -462,7 +428,7 @@ int kv_fastq_device_next(KvFastqDevice *d, uint64_t max_reads, kv_reads **reads_
         {
             KvProfScope prof("k_count_lines");
             hipLaunchKernelGGL(k_count_lines, dim3(n_chunks), dim3(FQ_THREADS), 0, st, (const uint8_t *)text, (uint64_t)total, d_counts);
-            hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, (const uint32_t *)d_counts, n_chunks, d_base);
+            kv_excl_scan_launch(d_counts, n_chunks, d_base, st);
         }
         KV_HIP(hipGetLastError());
         KV_HIP(hipMemcpyAsync(&n_lines, d_base + n_chunks, 8, hipMemcpyDeviceToHost, st));

@@ -300,6 +300,8 @@ hipStream_t kv_stream();
 hipStream_t kv_stream_key(hipStream_t st);
 // table buffers of destroyed sketches kept for the next sketch (kv_host.hip) go back to the driver: called when an allocation fails
 void kv_table_cache_release();
+// exclusive scan of n 32-bit counts into n + 1 64-bit bases, d_base[n] = total: the one workgroup of kv_scan.hip, on `st`
+void kv_excl_scan_launch(const uint32_t *d_counts, uint32_t n, uint64_t *d_base, hipStream_t st);
 void kv_case_bits_launch(const uint8_t *d_table, uint64_t size, int case_min, uint32_t *d_bits, hipStream_t st);      // kv_skm.hip
 void kv_skm_scratch_release();       // kv_skm.hip: every stream's bucket arena, distinct list and bit map
 void kv_route_scratch_release();     // kv_shard.hip: every stream's pair sink

@@ -4,7 +4,7 @@
 //   k_novel_mark  one workgroup per tile: hash every k-mer, band filter, probe the control and
 //                 case sketches, and set bit (read * stride + offset) for each interesting k-mer;
 //                 per-tile hit counts on the side.  This is the whole cost of the scan.
-//   k_tile_scan   exclusive prefix sum of the tile hit counts (one workgroup).
+//   k_tile_scan   exclusive prefix sum of the tile hit counts (one workgroup: k_excl_scan_u32, kv_scan.hip).
 //   k_novel_emit_bits  a tile's hits are the set bits of its range of the mask: ranked with a prefix sum,
 //                 one hit per lane, k-mer rebuilt from the packed words, S abundances read.
 //                 (k_novel_emit, which stages the tile again, serves 2-bit-hash kinds and k > 64.)
@@ -13,6 +13,7 @@
 // them, and the bit mask doubles as the per-band mask that the multi-GPU merge all-reduces.
 #include <algorithm>
 #include <functional>
+#include <memory>
 
 #include "kv_internal.h"
 #include "kv_novel_device.h"
@@ -106,20 +107,9 @@ __global__ __launch_bounds__(NM2_THREADS, 6) void k_novel_mark_2bit(ReadsDev rd,
         unsigned long long cached = 0;
         if (cached_verdicts && have) {
             // (the set from the LOW bits of the hash: a band is a range of hashes, its k-mers share the top ones)
-            const unsigned long long *set = p.vcache + ((h & ((1ull << (61 - p.vcache_shift)) - 1ull)) << 3);
-            const ulonglong2 e0 = ((const ulonglong2 *)set)[0], e1 = ((const ulonglong2 *)set)[1];
-            const ulonglong2 e2 = ((const ulonglong2 *)set)[2], e3 = ((const ulonglong2 *)set)[3];
-            const unsigned long long e[8] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, e3.x, e3.y};
-            bool hit = false;
-            uint32_t way = (uint32_t)(h >> 40) & 7u, empty = 8;
-#pragma unroll
-            for (int w = 7; w >= 0; --w) {
-                hit |= e[w] == h;
-                if (e[w] == 0) empty = (uint32_t)w;
-            }
-            if (e[way] != 0 && empty < 8) way = empty;
-            slot = const_cast<unsigned long long *>(set) + way;
-            cached = hit ? h : ~h;
+            const VcacheProbe vp = vcache_set_probe(p.vcache + ((h & ((1ull << (61 - p.vcache_shift)) - 1ull)) << 3), h, (uint32_t)(h >> 40) & 7u);
+            slot = vp.slot;
+            cached = vp.cached;
         }
         if (have && novel_test_fast(ns, p, h, slot, cached)) atomicOr(&p.mask[bit >> 5], 1u << (bit & 31));
     };
@@ -176,7 +166,7 @@ __global__ __launch_bounds__(KV_TILE_THREADS) void k_novel_mark(ReadsDev rd, Nov
                 const uint32_t gread = read0 + c.r;
                 const uint32_t key = kmer_minimizer_key(rd.words + rd.woff[gread], sh.seg_start + c.i, p.hp.k, p.vcache_window);
                 const unsigned long long *set = p.vcache + ((uint64_t)(key & p.vcache_set_mask) << 3);
-                // plain loads: a stale line can only hide an entry (a miss), never invent one
+                // vcache_set_probe written out: through the helper the kernel's code was not the same (two SGPR pairs changed places)
                 const ulonglong2 e0 = ((const ulonglong2 *)set)[0], e1 = ((const ulonglong2 *)set)[1];
                 const ulonglong2 e2 = ((const ulonglong2 *)set)[2], e3 = ((const ulonglong2 *)set)[3];
                 const unsigned long long e[8] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, e3.x, e3.y};
@@ -218,59 +208,6 @@ __global__ __launch_bounds__(KV_TILE_THREADS) void k_novel_mark(ReadsDev rd, Nov
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&tile_hits, mine);
     __syncthreads();
     if (threadIdx.x == 0) p.tile_count[blockIdx.x] = tile_hits;
-}
-
-// exclusive scan of n 32-bit counts into 64-bit bases (single 1024-thread workgroup)
-__global__ __launch_bounds__(1024) void k_tile_scan(const uint32_t *counts, uint32_t n, uint64_t *base)
-{
-    // One workgroup; a wave takes 64 * PER consecutive counts per round, 64 at a time: consecutive lanes on consecutive counts, so a
-    // load is one 256-byte piece of memory and a store one of 512, and the wave's running total rides along from one 64 to the next.
-    // (A thread on PER consecutive counts -- eight 4-byte loads 32 bytes apart from its neighbour's, eight 8-byte stores 64 bytes apart --
-    // made every round ~7 us of single-CU memory pipe: 0.108 ms for the 117 k tiles of config 2.)  The next round's counts are
-    // requested before this round's barriers.
-    constexpr uint32_t PER = 8;
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t nxt[PER];
-    auto request = [&](uint32_t start) {
-        const uint32_t i0 = start + wave * 64u * PER + lane;
-#pragma unroll
-        for (uint32_t u = 0; u < PER; ++u) nxt[u] = i0 + u * 64u < n ? counts[i0 + u * 64u] : 0u;
-    };
-    request(0);
-    for (uint32_t start = 0; start < n; start += 1024 * PER) {
-        const uint32_t i0 = start + wave * 64u * PER + lane;
-        uint32_t c[PER];
-        uint64_t excl[PER];                             // exclusive prefix inside the wave's stretch
-        uint64_t run = 0;                               // total of the pieces in front (wave-uniform)
-#pragma unroll
-        for (uint32_t u = 0; u < PER; ++u) {
-            c[u] = nxt[u];
-            uint64_t incl = c[u];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint64_t up = __shfl_up(incl, d);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            excl[u] = run + incl - c[u];
-            run += __shfl(incl, 63);
-        }
-        if (start + 1024 * PER < n) request(start + 1024 * PER);
-        if (lane == 0) wsum[wave] = run;
-        __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-#pragma unroll
-        for (uint32_t u = 0; u < PER; ++u)
-            if (i0 + u * 64u < n) base[i0 + u * 64u] = before + excl[u];
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + run;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) base[n] = carry;
 }
 
 __global__ __launch_bounds__(KV_TILE_THREADS) void k_novel_emit(ReadsDev rd, NovelParams p)
@@ -361,12 +298,7 @@ __global__ __launch_bounds__(256) void k_novel_emit_bits(ReadsDev rd, NovelParam
             if (wlo + 32 > b1) bits &= b1 > wlo ? (~0u >> (uint32_t)(wlo + 32 - b1)) : 0u;   // ... of the next
         }
         const uint32_t c = (uint32_t)__popc(bits);
-        uint32_t incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const uint32_t incl = wave_incl_scan(c);
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();
         uint32_t before = 0, chunk_hits = 0;
@@ -505,8 +437,305 @@ int attach_vcache(NovelParams &p, kv_sketch *const *ctrls, int ncase, int nctrl,
     return KV_OK;
 }
 
+// NovelParams from the case and control sketches of a scan: every sketch ready, one k and one hash family, p.sk[] (cases first),
+// p.hp and the thresholds.  `who`: the entry point, for the error texts.
+int novel_params(NovelParams &p, const char *who, kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, int nctrl, int case_min, int ctrl_max)
+{
+    memset(&p, 0, sizeof(p));
+    int k = 0, fam = 0;
+    for (int c = 0; c < ncase + nctrl; ++c) {
+        const kv_sketch *s = c < ncase ? cases[c] : ctrls[c - ncase];
+        KV_REQUIRE(s, KV_ERR_ARG, "%s: null sketch", who);
+        { const int rc = kv_sketch_ready(s); if (rc != KV_OK) return rc; }
+        if (c == 0) { k = s->h.ksize; fam = s->h.hashfam; }
+        KV_REQUIRE(s->h.ksize == k && s->h.hashfam == fam, KV_ERR_ARG,
+                   "all sketches of one scan must share k and hash function");
+        p.sk[c] = s->d_desc;
+    }
+    p.hp = make_hash_params(k, fam);
+    p.ncase = ncase; p.nctrl = nctrl;
+    p.case_min = case_min; p.ctrl_max = ctrl_max;
+    return KV_OK;
+}
+
+// Equal-length reads of a murmur kind, 16 <= k <= 64: every k-mer can be hashed from its 2-bit form (k_novel_mark_2bit).
+// KV_NOVEL_PATH=tiles, or KV_NOVEL_2BIT=0, keeps the tile kernel; a set scan also heeds KV_SET_SCAN=skm (the bucketed scan).
+bool two_bit_mark(const kv_reads *reads, int fam, int k, bool set_scan)
+{
+    const char *forced = kv_knob("KV_NOVEL_PATH"), *nm2 = kv_knob("KV_NOVEL_2BIT"), *how = set_scan ? kv_knob("KV_SET_SCAN") : nullptr;
+    return fam == HF_MURMUR && k >= SKM_MIN_K && k <= SKM_MAX_K && reads->uni_len >= (uint32_t)k && reads->uni_per_tile != 0 &&
+           !(how && strcmp(how, "skm") == 0) && !(nm2 && atoi(nm2) == 0) && !(forced && strcmp(forced, "tiles") == 0);
+}
+
+// ---- scan_reads: mark -> count per tile -> emit in (read, offset) order, shared by kv_novel_scan and kv_novel_scan_set ----------
+// what its steps share
+struct Scan {
+    NovelParams &p;
+    const kv_reads *reads;
+    int fam, k, S;
+    uint64_t n_kmers;
+    hipStream_t st;
+    ScanArenas *arenas;
+};
+
+// a failed HIP call of the scan: its one error exit
+#define SCAN_HIP(call)                                                                      \
+    do {                                                                                    \
+        const hipError_t e__ = (call);                                                      \
+        if (e__ != hipSuccess) {                                                            \
+            kv_set_error("kv_novel_scan failed: %s", hipGetErrorString(e__));              \
+            return KV_ERR_HIP;                                                              \
+        }                                                                                   \
+    } while (0)
+#define SCAN_STEP(call)                                                                     \
+    do {                                                                                    \
+        const int rc__ = (call);                                                            \
+        if (rc__ != KV_OK) return rc__;                                                     \
+    } while (0)
+
+// the work arena: hit mask (unless the caller brought one, d_mask), first screen trip per read (--abund-screen), hits per tile and
+// their bases -- one after the other, each a multiple of 256 bytes; mask and trips cleared
+int scan_carve_work(Scan &s, uint32_t *d_mask, uint64_t mask_stride)
+{
+    NovelParams &p = s.p;
+    const uint64_t n_reads = s.reads->n_reads, n_tiles = s.reads->n_tiles;
+    const uint64_t min_stride = s.reads->max_len >= (uint32_t)s.k ? s.reads->max_len - (uint32_t)s.k + 1 : 1;
+    const uint64_t mask_words = d_mask ? 0 : (n_reads * min_stride + 31) / 32;
+    // one bit per (read, offset) with the stride of the longest read: a chromosome among a million reads
+    KV_REQUIRE(mask_words * 4 <= ((uint64_t)64 << 30), KV_ERR_CAPACITY,
+               "kv_novel_scan: %llu reads with a longest read of %u bases need a %llu GB hit mask; "
+               "scan long sequences in a batch of their own", (unsigned long long)n_reads, s.reads->max_len,
+               (unsigned long long)(mask_words * 4 >> 30));
+    const size_t b_mask = up256(mask_words * 4), b_trips = p.screen > 0 ? up256(n_reads * 4) : 0, b_tcount = up256(n_tiles * 4);
+    SCAN_HIP(s.arenas->work.need_exact(b_mask + b_trips + b_tcount + up256((n_tiles + 1) * 8) + 256));
+    unsigned char *base = (unsigned char *)s.arenas->work.p;
+    p.mask = d_mask ? d_mask : (uint32_t *)base;
+    p.mask_stride = d_mask ? mask_stride : min_stride;
+    if (!d_mask) SCAN_HIP(hipMemsetAsync(p.mask, 0, mask_words * 4, s.st));
+    if (p.screen > 0) {
+        p.disc_first = (uint32_t *)(base + b_mask);
+        SCAN_HIP(hipMemsetAsync(p.disc_first, 0xFF, n_reads * 4, s.st));
+    }
+    p.tile_count = (uint32_t *)(base + b_mask + b_trips);
+    p.tile_base = (const uint64_t *)(base + b_mask + b_trips + b_tcount);
+    return KV_OK;
+}
+
+// a scan by the distinct list its count left (k_skm_novel_list) keeps the abundances of the interesting k-mers for k_hit_abund:
+// p.ab_* in the abund arena, keys and count cleared.  No room: the scan does without.
+int scan_attach_abund(Scan &s)
+{
+    NovelParams &p = s.p;
+    // room for the abundances of the interesting k-mers (a k-mer in a few thousand is one): 1 / 64 of the k-mers in slots
+    uint64_t slots = 1u << 16;
+    while (slots < s.n_kmers / 64 && slots < (1ull << 24)) slots <<= 1;
+    const uint64_t list_cap = slots / 8;
+    if (s.arenas->abund.need_exact(up256(slots * 8) + up256(slots * (uint64_t)s.S) + up256(list_cap * 4) + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return KV_OK;
+    }
+    p.ab_keys = (unsigned long long *)s.arenas->abund.p;
+    p.ab_vals = (uint8_t *)s.arenas->abund.p + up256(slots * 8);
+    p.ab_mask = slots - 1;
+    p.ab_list = (uint32_t *)(p.ab_vals + up256(slots * (uint64_t)s.S));
+    p.ab_count = (unsigned int *)((unsigned char *)p.ab_list + up256(list_cap * 4));
+    p.ab_list_cap = (uint32_t)list_cap;
+    SCAN_HIP(hipMemsetAsync(p.ab_keys, 0, slots * 8, s.st));
+    SCAN_HIP(hipMemsetAsync(p.ab_count, 0, 4, s.st));
+    return KV_OK;
+}
+
+// the mask bit of every interesting k-mer and the hits per tile: over the super-k-mer buckets (use_skm), else from the 2-bit form,
+// else tile by tile.  Buckets that overflow leave true hits only, so the tile scan simply runs on top of the same mask.
+int scan_mark(Scan &s, bool use_skm, const std::function<int()> &prepare_tile_scan, bool *skm_overflowed)
+{
+    NovelParams &p = s.p;
+    const kv_reads *reads = s.reads;
+    if (use_skm) {
+        const int rc = kv_skm_novel_mark(reads, p, s.n_kmers);
+        if (rc == KV_OK) return KV_OK;
+        if (rc != KV_ERR_CAPACITY) return rc;
+        if (skm_overflowed) *skm_overflowed = true;
+        SCAN_STEP(prepare_tile_scan());
+    }
+    if (p.screen == 0 && two_bit_mark(reads, s.fam, s.k, false)) {
+        {
+            KvProfScope prof("k_novel_mark_2bit");
+            const uint64_t n_items = reads->n_reads * (((uint64_t)reads->uni_len - (uint64_t)s.k + 1 + NM2_CH - 1) / NM2_CH);
+            const unsigned grid = (unsigned)std::min<uint64_t>((n_items + NM2_THREADS - 1) / NM2_THREADS, 3u * (unsigned)kv_device_cus() * 4u);
+            if (s.k == 31 && !kv_knob("KV_SKM_ANY_K")) hipLaunchKernelGGL((k_novel_mark_2bit<1, 31>), dim3(grid), dim3(NM2_THREADS), 0, s.st, reads_dev(reads), p);
+            else if (s.k <= 32) hipLaunchKernelGGL(k_novel_mark_2bit<1>, dim3(grid), dim3(NM2_THREADS), 0, s.st, reads_dev(reads), p);
+            else hipLaunchKernelGGL(k_novel_mark_2bit<2>, dim3(grid), dim3(NM2_THREADS), 0, s.st, reads_dev(reads), p);
+        }
+        kv_tile_hits_launch(reads, p, s.st);
+    } else {
+        KvProfScope prof("k_novel_mark");
+        kv_ensure_dynamic_lds((const void *)k_novel_mark, reads->tile_lds_bytes);
+        hipLaunchKernelGGL(k_novel_mark, dim3(reads->n_tiles), dim3(KV_TILE_THREADS), reads->tile_lds_bytes, s.st, reads_dev(reads), p);
+    }
+    return KV_OK;
+}
+
+// where every tile's hits start in the output, and how many there are in all (the scan's first wait for the device)
+int scan_tile_bases(Scan &s, uint64_t *nhits)
+{
+    {
+        KvProfScope prof("k_tile_scan");
+        kv_excl_scan_launch(s.p.tile_count, s.reads->n_tiles, const_cast<uint64_t *>(s.p.tile_base), s.st);
+    }
+    SCAN_HIP(hipGetLastError());
+    SCAN_HIP(hipMemcpyAsync(nhits, s.p.tile_base + s.reads->n_tiles, 8, hipMemcpyDeviceToHost, s.st));
+    SCAN_HIP(hipStreamSynchronize(s.st));
+    return KV_OK;
+}
+
+// (read, offset, S abundances) of every hit into the hits arena, in mask order
+int scan_emit(Scan &s, uint64_t nhits)
+{
+    NovelParams &p = s.p;
+    const kv_reads *reads = s.reads;
+    SCAN_HIP(s.arenas->hits.need_exact(2 * up256(nhits * 4) + up256(nhits * (uint64_t)s.S)));
+    p.hit_read = (uint32_t *)s.arenas->hits.p;
+    p.hit_off = (uint32_t *)((unsigned char *)s.arenas->hits.p + up256(nhits * 4));
+    p.hit_abund = (uint8_t *)s.arenas->hits.p + 2 * up256(nhits * 4);
+    {
+        KvProfScope prof("k_novel_emit");
+        const bool from_bits = s.fam == HF_MURMUR && s.k <= 64;
+        const bool dense = from_bits && s.k >= SKM_MIN_K;
+        const unsigned grid_hits = (unsigned)std::min<uint64_t>((nhits + 255) / 256, 1u << 16);
+        if (dense && s.k <= 32) {
+            hipLaunchKernelGGL((k_novel_emit_bits<8, false>), dim3(reads->n_tiles), dim3(256), 0, s.st, reads_dev(reads), p);
+            hipLaunchKernelGGL(k_hit_abund<1>, dim3(grid_hits), dim3(256), 0, s.st, reads_dev(reads), p, nhits);
+        } else if (dense) {
+            hipLaunchKernelGGL((k_novel_emit_bits<16, false>), dim3(reads->n_tiles), dim3(256), 0, s.st, reads_dev(reads), p);
+            hipLaunchKernelGGL(k_hit_abund<2>, dim3(grid_hits), dim3(256), 0, s.st, reads_dev(reads), p, nhits);
+        } else if (from_bits) {                          // (k < SKM_MIN_K: one packed word's worth of window)
+            hipLaunchKernelGGL((k_novel_emit_bits<8, true>), dim3(reads->n_tiles), dim3(256), 0, s.st, reads_dev(reads), p);
+        } else {
+            kv_ensure_dynamic_lds((const void *)k_novel_emit, reads->tile_lds_bytes);
+            hipLaunchKernelGGL(k_novel_emit, dim3(reads->n_tiles), dim3(KV_TILE_THREADS), reads->tile_lds_bytes, s.st, reads_dev(reads), p);
+        }
+    }
+    SCAN_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+// kv_hits_lazy: the copies of a scan go to a copy stream of this stream's own, behind the scan's last kernel (kdone)
+int scan_copy_stream(Scan &s, kv_hits *hits)
+{
+    ScanArenas *a = s.arenas;
+    if (!a->copy_stream) {
+        // (lowest priority: the copies are blit kernels, and the count kernels they run beside should win the CUs)
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+        SCAN_HIP(hipStreamCreateWithPriority(&a->copy_stream, hipStreamNonBlocking, least));
+        SCAN_HIP(hipEventCreateWithFlags(&a->kdone, hipEventDisableTiming));
+        SCAN_HIP(hipEventCreateWithFlags(&a->copied, hipEventDisableTiming));
+    }
+    SCAN_HIP(hipEventCreateWithFlags(&hits->ready, hipEventDisableTiming));
+    SCAN_HIP(hipEventRecord(a->kdone, s.st));
+    SCAN_HIP(hipStreamWaitEvent(a->copy_stream, a->kdone, 0));
+    return KV_OK;
+}
+
+// the three hit arrays to the handle's pinned arrays on `cs`; lazy: the events a reader (ready) and the next scan (copied) wait for
+int scan_copy_hits(Scan &s, kv_hits *hits, uint64_t nhits, hipStream_t cs, bool lazy)
+{
+    const NovelParams &p = s.p;
+    SCAN_HIP(hipMemcpyAsync(hits->read.data(), p.hit_read, nhits * 4, hipMemcpyDeviceToHost, cs));
+    SCAN_HIP(hipMemcpyAsync(hits->offset.data(), p.hit_off, nhits * 4, hipMemcpyDeviceToHost, cs));
+    SCAN_HIP(hipMemcpyAsync(hits->abund.data(), p.hit_abund, nhits * (uint64_t)s.S, hipMemcpyDeviceToHost, cs));
+    if (lazy) {
+        SCAN_HIP(hipEventRecord(hits->ready, cs));
+        SCAN_HIP(hipEventRecord(s.arenas->copied, cs));
+    }
+    return KV_OK;
+}
+
+// The hits to the host.  Eager: the call returns when they have arrived.  kv_hits_lazy (and no abundance screen, whose bookkeeping
+// reads the hits on the host right away): the call returns when its KERNELS are done -- the sketches may change from then on -- while
+// the arrays travel on a copy stream; whoever reads the handle waits for them (kv_hits::wait).  25 MB of hits per scan of config 2
+// are half a millisecond of PCIe that the next count hides.
+int scan_deliver(Scan &s, kv_hits *hits, uint64_t nhits)
+{
+    SCAN_HIP(hits->read.resize(nhits));
+    SCAN_HIP(hits->offset.resize(nhits));
+    SCAN_HIP(hits->abund.resize(nhits * (uint64_t)s.S));
+    if (!(g_hits_lazy && !s.p.disc_first)) {
+        SCAN_STEP(scan_copy_hits(s, hits, nhits, s.st, false));
+        SCAN_HIP(hipStreamSynchronize(s.st));
+        return KV_OK;
+    }
+    SCAN_STEP(scan_copy_stream(s, hits));
+    const int rc = scan_copy_hits(s, hits, nhits, s.arenas->copy_stream, true);
+    if (rc != KV_OK) {
+        (void)hipStreamSynchronize(s.arenas->copy_stream);      // (nothing may be in flight into a handle that is about to be deleted)
+        return rc;
+    }
+    s.arenas->copy_pending = true;
+    SCAN_HIP(hipEventSynchronize(s.arenas->kdone));
+    return KV_OK;
+}
+
+// --abund-screen: a read with a k-mer that tripped the screen (first_trip[read] != ~0) is dropped with all of its hits
+// (novel.py:152-154,164); the interesting k-mers in front of that k-mer had already been tallied by the reference's loop
+// (novel.py:160-162), so they are kept aside for the "unique novel kmers" figure
+void apply_screen_discards(kv_hits *hits, const std::vector<uint32_t> &first_trip, int S)
+{
+    for (uint64_t i = 0; i < first_trip.size(); ++i)
+        if (first_trip[i] != 0xffffffffu) hits->discarded.push_back((uint32_t)i);
+    if (hits->discarded.empty()) return;
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < hits->read.size(); ++i) {
+        const uint32_t trip = first_trip[hits->read[i]];
+        if (trip != 0xffffffffu) {
+            if (hits->offset[i] < trip) { hits->shadow_read.push_back(hits->read[i]); hits->shadow_offset.push_back(hits->offset[i]); }
+            continue;
+        }
+        hits->read[w] = hits->read[i];
+        hits->offset[w] = hits->offset[i];
+        if (w != i) memmove(&hits->abund[w * (uint64_t)S], &hits->abund[i * (uint64_t)S], (size_t)S);
+        ++w;
+    }
+    hits->read.n = w; hits->offset.n = w; hits->abund.n = w * (uint64_t)S;   // shrink in place
+}
+
+// prepare_tile_scan: what the caller does to p before k-mers are evaluated one by one (the verdict cache); it runs before the tile
+// paths, and again after a super-k-mer overflow
 int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers, bool use_skm, const std::function<int()> &prepare_tile_scan,
-               uint32_t *d_mask, uint64_t mask_stride, kv_hits **out, bool *skm_overflowed = nullptr);
+               uint32_t *d_mask, uint64_t mask_stride, kv_hits **out, bool *skm_overflowed = nullptr)
+{
+    Scan s{p, reads, fam, p.hp.k, p.ncase + p.nctrl, n_kmers, kv_stream(), nullptr};
+    if (!use_skm) SCAN_STEP(prepare_tile_scan());
+
+    *out = nullptr;
+    std::unique_ptr<kv_hits> hits(new kv_hits());
+    hits->nsamples = s.S;
+    if (reads->n_tiles == 0) { *out = hits.release(); return KV_OK; }
+
+    s.arenas = &g_scan_arenas.get(s.st);
+    std::lock_guard<std::mutex> arena_lock(s.arenas->mu);
+    if (s.arenas->copy_pending) {                   // the previous scan's hits may still be leaving the buffers this one writes
+        s.arenas->copy_pending = false;
+        SCAN_HIP(hipStreamWaitEvent(s.st, s.arenas->copied, 0));
+    }
+    SCAN_STEP(scan_carve_work(s, d_mask, mask_stride));
+    if (use_skm && !p.set_keys && kv_skm_list_ready(reads, s.k)) SCAN_STEP(scan_attach_abund(s));
+    SCAN_STEP(scan_mark(s, use_skm, prepare_tile_scan, skm_overflowed));
+    uint64_t nhits = 0;
+    SCAN_STEP(scan_tile_bases(s, &nhits));
+    if (nhits) {
+        SCAN_STEP(scan_emit(s, nhits));
+        SCAN_STEP(scan_deliver(s, hits.get(), nhits));
+    }
+    if (p.disc_first) {
+        std::vector<uint32_t> first_trip(reads->n_reads);
+        SCAN_HIP(hipMemcpy(first_trip.data(), p.disc_first, reads->n_reads * 4, hipMemcpyDeviceToHost));
+        apply_screen_discards(hits.get(), first_trip, s.S);
+    }
+    *out = hits.release();
+    return KV_OK;
+}
 
 }  // namespace
 
@@ -521,22 +750,12 @@ extern "C" int kv_novel_scan(kv_sketch *const *cases, int ncase, kv_sketch *cons
     KV_REQUIRE(band_mode == KV_BAND_NONE || (nbands > 0 && band >= 0 && band < nbands), KV_ERR_ARG,
                "band %d out of range for %d bands", band, nbands);
     NovelParams p;
-    memset(&p, 0, sizeof(p));
-    const int k = cases[0]->h.ksize, fam = cases[0]->h.hashfam;
-    for (int c = 0; c < ncase + nctrl; ++c) {
-        const kv_sketch *s = c < ncase ? cases[c] : ctrls[c - ncase];
-        KV_REQUIRE(s, KV_ERR_ARG, "kv_novel_scan: null sketch");
-        { const int rc = kv_sketch_ready(s); if (rc != KV_OK) return rc; }
-        KV_REQUIRE(s->h.ksize == k && s->h.hashfam == fam, KV_ERR_ARG,
-                   "all sketches of one scan must share k and hash function");
-        p.sk[c] = s->d_desc;
-    }
+    { const int rc = novel_params(p, "kv_novel_scan", cases, ncase, ctrls, nctrl, case_min, ctrl_max); if (rc != KV_OK) return rc; }
+    const int k = p.hp.k, fam = p.hp.hashfam;
     const uint64_t min_stride = reads->max_len >= (uint32_t)k ? reads->max_len - (uint32_t)k + 1 : 1;
     if (d_mask) KV_REQUIRE(mask_stride >= min_stride, KV_ERR_ARG, "mask_stride %llu is smaller than the longest read's %llu k-mers",
                            (unsigned long long)mask_stride, (unsigned long long)min_stride);
-    p.hp = make_hash_params(k, fam);
-    p.ncase = ncase; p.nctrl = nctrl;
-    p.case_min = case_min; p.ctrl_max = ctrl_max; p.screen = screen_thresh > 0 ? screen_thresh : 0;
+    p.screen = screen_thresh > 0 ? screen_thresh : 0;
     p.band_mode = band_mode; p.nbands = nbands; p.band = band;
     if (band_mode == KV_BAND_RANGE) kv_band_bounds(nbands, band, &p.band_lo, &p.band_hi);
     p.first_read = first_read;
@@ -590,220 +809,6 @@ extern "C" int kv_novel_scan(kv_sketch *const *cases, int ncase, kv_sketch *cons
     if (skm_overflowed) cases[0]->skm_scan_off = true;
     return rc;
 }
-
-namespace {
-
-// mark -> count per tile -> emit in (read, offset) order: shared by kv_novel_scan and kv_novel_scan_set
-int scan_reads(NovelParams &p, const kv_reads *reads, int fam, uint64_t n_kmers, bool use_skm, const std::function<int()> &prepare_tile_scan,
-               uint32_t *d_mask, uint64_t mask_stride, kv_hits **out, bool *skm_overflowed)
-{
-    const int k = p.hp.k, S = p.ncase + p.nctrl;
-    const uint64_t min_stride = reads->max_len >= (uint32_t)k ? reads->max_len - (uint32_t)k + 1 : 1;
-    hipStream_t st = kv_stream();
-    if (!use_skm) { const int rc = prepare_tile_scan(); if (rc != KV_OK) return rc; }
-
-    kv_hits *hits = new kv_hits();
-    hits->nsamples = S;
-    *out = hits;
-    if (reads->n_tiles == 0) return KV_OK;
-
-    ScanArenas *arenas = &g_scan_arenas.get(st);
-    std::lock_guard<std::mutex> arena_lock(arenas->mu);
-    hipError_t e = hipSuccess;
-    if (arenas->copy_pending) {                     // the previous scan's hits may still be leaving the buffers this one writes
-        e = hipStreamWaitEvent(st, arenas->copied, 0);
-        arenas->copy_pending = false;
-    }
-    const uint64_t mask_words = d_mask ? 0 : (reads->n_reads * min_stride + 31) / 32;
-    if (mask_words * 4 > ((uint64_t)64 << 30)) {
-        // one bit per (read, offset) with the stride of the longest read: a chromosome among a million reads
-        kv_set_error("kv_novel_scan: %llu reads with a longest read of %u bases need a %llu GB hit mask; "
-                     "scan long sequences in a batch of their own", (unsigned long long)reads->n_reads, reads->max_len,
-                     (unsigned long long)(mask_words * 4 >> 30));
-        delete hits;
-        *out = nullptr;
-        return KV_ERR_CAPACITY;
-    }
-    const size_t b_mask = up256(mask_words * 4), b_flags = p.screen > 0 ? up256(reads->n_reads * 4) : 0;
-    const size_t b_tcount = up256((uint64_t)reads->n_tiles * 4), b_tbase = up256(((uint64_t)reads->n_tiles + 1) * 8);
-    e = arenas->work.need_exact(b_mask + b_flags + b_tcount + b_tbase + 256);
-    unsigned char *wp = (unsigned char *)arenas->work.p;
-    if (e == hipSuccess) {
-        if (d_mask) {
-            p.mask = d_mask; p.mask_stride = mask_stride;
-        } else {
-            p.mask_stride = min_stride;
-            p.mask = (uint32_t *)wp;
-            e = hipMemsetAsync(p.mask, 0, mask_words * 4, st);
-        }
-        wp += b_mask;
-    }
-    if (e == hipSuccess && p.screen > 0) {
-        p.disc_first = (uint32_t *)wp;
-        e = hipMemsetAsync(p.disc_first, 0xFF, reads->n_reads * 4, st);
-    }
-    wp += b_flags;
-    p.tile_count = (uint32_t *)wp; wp += b_tcount;
-    uint64_t *d_tbase_p = (uint64_t *)wp;
-    p.tile_base = d_tbase_p;
-    uint64_t nhits = 0;
-    bool marked_by_skm = use_skm;
-    p.ab_keys = nullptr; p.ab_vals = nullptr; p.ab_mask = 0; p.ab_list = nullptr; p.ab_count = nullptr; p.ab_list_cap = 0;
-    if (e == hipSuccess && use_skm && !p.set_keys && kv_skm_list_ready(reads, k)) {
-        // room for the abundances of the interesting k-mers (a k-mer in a few thousand is one): 1 / 64 of the k-mers in slots
-        uint64_t slots = 1u << 16;
-        while (slots < n_kmers / 64 && slots < (1ull << 24)) slots <<= 1;
-        const uint64_t list_cap = slots / 8;
-        if (arenas->abund.need_exact(up256(slots * 8) + up256(slots * (uint64_t)S) + up256(list_cap * 4) + 256) == hipSuccess) {
-            p.ab_keys = (unsigned long long *)arenas->abund.p;
-            p.ab_vals = (uint8_t *)arenas->abund.p + up256(slots * 8);
-            p.ab_mask = slots - 1;
-            p.ab_list = (uint32_t *)(p.ab_vals + up256(slots * (uint64_t)S));
-            p.ab_count = (unsigned int *)((unsigned char *)p.ab_list + up256(list_cap * 4));
-            p.ab_list_cap = (uint32_t)list_cap;
-            e = hipMemsetAsync(p.ab_keys, 0, slots * 8, st);
-            if (e == hipSuccess) e = hipMemsetAsync(p.ab_count, 0, 4, st);
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (e == hipSuccess && use_skm) {
-        const int rc = kv_skm_novel_mark(reads, p, n_kmers);
-        if (rc == KV_ERR_CAPACITY) {
-            // every bit set so far is a true hit, so the tile scan can simply run on top of the same mask
-            marked_by_skm = false;
-            if (skm_overflowed) *skm_overflowed = true;
-            const int rc2 = prepare_tile_scan();
-            if (rc2 != KV_OK) { delete hits; *out = nullptr; return rc2; }
-        } else if (rc != KV_OK) {
-            delete hits;
-            *out = nullptr;
-            return rc;
-        }
-    }
-    if (e == hipSuccess) {
-        // equal-length reads of a murmur kind, 16 <= k <= 64, no abundance screen: every k-mer hashed from its 2-bit form
-        // (k_novel_mark_2bit; KV_NOVEL_PATH=tiles, or KV_NOVEL_2BIT=0, keeps the tile kernel)
-        const char *forced = kv_knob("KV_NOVEL_PATH"), *nm2 = kv_knob("KV_NOVEL_2BIT");
-        const bool two_bit = !marked_by_skm && p.screen == 0 && fam == HF_MURMUR && k >= SKM_MIN_K && k <= SKM_MAX_K && reads->uni_len >= (uint32_t)k &&
-                             reads->uni_per_tile != 0 && !(forced && strcmp(forced, "tiles") == 0) && !(nm2 && atoi(nm2) == 0);
-        if (two_bit) {
-            {
-                KvProfScope prof("k_novel_mark_2bit");
-                const uint64_t n_items = reads->n_reads * (((uint64_t)reads->uni_len - (uint64_t)k + 1 + NM2_CH - 1) / NM2_CH);
-                const unsigned grid = (unsigned)std::min<uint64_t>((n_items + NM2_THREADS - 1) / NM2_THREADS, 3u * (unsigned)kv_device_cus() * 4u);
-                if (k == 31 && !kv_knob("KV_SKM_ANY_K")) hipLaunchKernelGGL((k_novel_mark_2bit<1, 31>), dim3(grid), dim3(NM2_THREADS), 0, st, reads_dev(reads), p);
-                else if (k <= 32) hipLaunchKernelGGL(k_novel_mark_2bit<1>, dim3(grid), dim3(NM2_THREADS), 0, st, reads_dev(reads), p);
-                else hipLaunchKernelGGL(k_novel_mark_2bit<2>, dim3(grid), dim3(NM2_THREADS), 0, st, reads_dev(reads), p);
-            }
-            kv_tile_hits_launch(reads, p, st);
-        } else if (!marked_by_skm) {
-            KvProfScope prof("k_novel_mark");
-            kv_ensure_dynamic_lds((const void *)k_novel_mark, reads->tile_lds_bytes);
-            hipLaunchKernelGGL(k_novel_mark, dim3(reads->n_tiles), dim3(KV_TILE_THREADS), reads->tile_lds_bytes, st, reads_dev(reads), p);
-        }
-        {
-            KvProfScope prof("k_tile_scan");
-            hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, p.tile_count, reads->n_tiles, d_tbase_p);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&nhits, d_tbase_p + reads->n_tiles, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && nhits) {
-        e = arenas->hits.need_exact(2 * up256(nhits * 4) + up256(nhits * (uint64_t)S));
-        p.hit_read = (uint32_t *)arenas->hits.p;
-        p.hit_off = (uint32_t *)((unsigned char *)arenas->hits.p + up256(nhits * 4));
-        p.hit_abund = (uint8_t *)arenas->hits.p + 2 * up256(nhits * 4);
-        if (e == hipSuccess) {
-            KvProfScope prof("k_novel_emit");
-            const bool from_bits = fam == HF_MURMUR && k <= 64;
-            const bool dense = from_bits && k >= SKM_MIN_K;
-            const unsigned grid_hits = (unsigned)std::min<uint64_t>((nhits + 255) / 256, 1u << 16);
-            if (dense && k <= 32) {
-                hipLaunchKernelGGL((k_novel_emit_bits<8, false>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
-                hipLaunchKernelGGL(k_hit_abund<1>, dim3(grid_hits), dim3(256), 0, st, reads_dev(reads), p, nhits);
-            } else if (dense) {
-                hipLaunchKernelGGL((k_novel_emit_bits<16, false>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
-                hipLaunchKernelGGL(k_hit_abund<2>, dim3(grid_hits), dim3(256), 0, st, reads_dev(reads), p, nhits);
-            } else if (from_bits) {                          // (k < SKM_MIN_K: one packed word's worth of window)
-                hipLaunchKernelGGL((k_novel_emit_bits<8, true>), dim3(reads->n_tiles), dim3(256), 0, st, reads_dev(reads), p);
-            } else {
-                kv_ensure_dynamic_lds((const void *)k_novel_emit, reads->tile_lds_bytes);
-                hipLaunchKernelGGL(k_novel_emit, dim3(reads->n_tiles), dim3(KV_TILE_THREADS), reads->tile_lds_bytes, st, reads_dev(reads), p);
-            }
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hits->read.resize(nhits);
-        if (e == hipSuccess) e = hits->offset.resize(nhits);
-        if (e == hipSuccess) e = hits->abund.resize(nhits * (uint64_t)S);
-        // kv_hits_lazy (and no abundance screen, whose bookkeeping reads the hits on the host right here): the call returns when its
-        // KERNELS are done -- the sketches may change from then on -- while the arrays travel on a copy stream; whoever reads the handle
-        // waits for them (kv_hits::wait).  25 MB of hits per scan of config 2 are half a millisecond of PCIe that the next count hides.
-        hipStream_t cs = st;
-        const bool lazy = g_hits_lazy && !p.disc_first;
-        if (lazy && e == hipSuccess) {
-            if (!arenas->copy_stream) {
-                // (lowest priority: the copies are blit kernels, and the count kernels they run beside should win the CUs)
-                int least = 0, greatest = 0;
-                (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-                e = hipStreamCreateWithPriority(&arenas->copy_stream, hipStreamNonBlocking, least);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&arenas->kdone, hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&arenas->copied, hipEventDisableTiming);
-            }
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&hits->ready, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(arenas->kdone, st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(arenas->copy_stream, arenas->kdone, 0);
-            cs = arenas->copy_stream;
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(hits->read.data(), p.hit_read, nhits * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(hits->offset.data(), p.hit_off, nhits * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(hits->abund.data(), p.hit_abund, nhits * (uint64_t)S, hipMemcpyDeviceToHost, cs);
-        if (lazy) {
-            if (e == hipSuccess) e = hipEventRecord(hits->ready, cs);
-            if (e == hipSuccess) e = hipEventRecord(arenas->copied, cs);
-            if (e == hipSuccess) arenas->copy_pending = true;
-            if (e == hipSuccess) e = hipEventSynchronize(arenas->kdone);
-            else (void)hipStreamSynchronize(cs);            // (nothing may be in flight into a handle that is about to be deleted)
-        } else if (e == hipSuccess) {
-            e = hipStreamSynchronize(st);
-        }
-    }
-    std::vector<uint32_t> first_trip;
-    if (e == hipSuccess && p.disc_first) {
-        first_trip.resize(reads->n_reads);
-        e = hipMemcpy(first_trip.data(), p.disc_first, reads->n_reads * 4, hipMemcpyDeviceToHost);
-        for (uint64_t i = 0; i < reads->n_reads; ++i)
-            if (first_trip[i] != 0xffffffffu) hits->discarded.push_back((uint32_t)i);
-    }
-    if (e != hipSuccess) {
-        delete hits;
-        *out = nullptr;
-        kv_set_error("kv_novel_scan failed: %s", hipGetErrorString(e));
-        return KV_ERR_HIP;
-    }
-    // a read dropped by the abundance screen loses all of its hits (novel.py:152-154,164); the interesting k-mers in
-    // front of the k-mer that tripped the screen had already been tallied by the reference's loop (novel.py:160-162),
-    // so they are kept aside for the "unique novel kmers" figure
-    if (!hits->discarded.empty()) {
-        uint64_t w = 0;
-        for (uint64_t i = 0; i < hits->read.size(); ++i) {
-            const uint32_t trip = first_trip[hits->read[i]];
-            if (trip != 0xffffffffu) {
-                if (hits->offset[i] < trip) { hits->shadow_read.push_back(hits->read[i]); hits->shadow_offset.push_back(hits->offset[i]); }
-                continue;
-            }
-            hits->read[w] = hits->read[i];
-            hits->offset[w] = hits->offset[i];
-            if (w != i) memmove(&hits->abund[w * (uint64_t)S], &hits->abund[i * (uint64_t)S], (size_t)S);
-            ++w;
-        }
-        hits->read.n = w; hits->offset.n = w; hits->abund.n = w * (uint64_t)S;   // shrink in place
-    }
-    return KV_OK;
-}
-
-}  // namespace
 
 extern "C" int kv_hits_lazy(int on)
 {
@@ -881,7 +886,6 @@ __global__ __launch_bounds__(256) void k_novel_list(NovelParams p, const uint64_
     __shared__ NovelShared ns;
     load_descs(ns, p);
     __syncthreads();
-    const int S = p.ncase + p.nctrl;
     struct Cand {
         uint64_t h, tag;
         unsigned long long *slot;
@@ -898,43 +902,19 @@ __global__ __launch_bounds__(256) void k_novel_list(NovelParams p, const uint64_
         if (c.live && p.vcache) {
             // no sequence here, so no minimizer: the set comes from the hash itself -- from its LOW bits: the hashes a band owner
             // receives are a range, they share the top ones --; 8 ways still lose fewer entries to conflicts than a direct-mapped slot
-            const unsigned long long *set = p.vcache + ((c.h & ((1ull << (61 - p.vcache_shift)) - 1ull)) << 3);
-            const ulonglong2 e0 = ((const ulonglong2 *)set)[0], e1 = ((const ulonglong2 *)set)[1];
-            const ulonglong2 e2 = ((const ulonglong2 *)set)[2], e3 = ((const ulonglong2 *)set)[3];
-            const unsigned long long e[8] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, e3.x, e3.y};
-            bool hit = false;
-            uint32_t way = (uint32_t)(c.h >> 7) & 7u, empty = 8;
-#pragma unroll
-            for (int w = 7; w >= 0; --w) {
-                hit |= e[w] == c.h;
-                if (e[w] == 0) empty = (uint32_t)w;
-            }
-            if (e[way] != 0 && empty < 8) way = empty;
-            c.slot = const_cast<unsigned long long *>(set) + way;
-            c.cached = hit ? c.h : ~c.h;
+            const VcacheProbe vp = vcache_set_probe(p.vcache + ((c.h & ((1ull << (61 - p.vcache_shift)) - 1ull)) << 3), c.h, (uint32_t)(c.h >> 7) & 7u);
+            c.slot = vp.slot;
+            c.cached = vp.cached;
         }
         return c;
     };
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t i0 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     Cand cur = fetch(i0);
-    const int lane = threadIdx.x & 63;
     for (uint64_t base = blockIdx.x * (uint64_t)blockDim.x; base < n; base += stride) {   // wave-uniform trip count
         const Cand nxt = fetch(base + threadIdx.x + stride);
         const bool interesting = cur.live && novel_test_fast(ns, p, cur.h, cur.slot, cur.cached);
-        const unsigned long long ballot = __ballot(interesting);
-        if (ballot) {
-            unsigned long long first = 0;
-            if (lane == 0) first = atomicAdd(hit_count, (unsigned long long)__popcll(ballot));
-            first = __shfl(first, 0);
-            if (interesting) {
-                const uint64_t pos = first + (uint64_t)__popcll(ballot & ((1ull << lane) - 1ull));
-                if (pos < cap) {
-                    hit_tag[pos] = want_hash ? cur.h : cur.tag;
-                    for (int c = 0; c < S; ++c) hit_abund[pos * (uint64_t)S + c] = (uint8_t)sketch_get(p.sk[c], cur.h);
-                }
-            }
-        }
+        novel_hit_append(p, interesting, cur.h, want_hash ? cur.h : cur.tag, hit_tag, hit_abund, hit_count, cap);
         cur = nxt;
     }
 }
@@ -950,8 +930,6 @@ __global__ __launch_bounds__(256) void k_novel_pairs(NovelParams p, const uint64
     __shared__ NovelShared ns;
     load_descs(ns, p);
     __syncthreads();
-    const int S = p.ncase + p.nctrl;
-    const int lane = threadIdx.x & 63;
     for (uint64_t base = (uint64_t)blockIdx.x * (E * 256u); base < n; base += (uint64_t)gridDim.x * (E * 256u)) {      // workgroup-uniform trip count
         uint64_t h[E];
         bool live[E];
@@ -978,18 +956,7 @@ __global__ __launch_bounds__(256) void k_novel_pairs(NovelParams p, const uint64
 #pragma unroll
         for (int u = 0; u < E; ++u) {
             const bool interesting = live[u] && (int)v[u] >= p.case_min && novel_test_fast(ns, p, h[u], nullptr, 0ull);
-            const unsigned long long ballot = __ballot(interesting);
-            if (!ballot) continue;
-            unsigned long long first = 0;
-            if (lane == 0) first = atomicAdd(hit_count, (unsigned long long)__popcll(ballot));
-            first = __shfl(first, 0);
-            if (interesting) {
-                const uint64_t pos = first + (uint64_t)__popcll(ballot & ((1ull << lane) - 1ull));
-                if (pos < cap) {
-                    hit_hash[pos] = h[u];
-                    for (int c = 0; c < S; ++c) hit_abund[pos * (uint64_t)S + c] = (uint8_t)sketch_get(p.sk[c], h[u]);
-                }
-            }
+            novel_hit_append(p, interesting, h[u], h[u], hit_hash, hit_abund, hit_count, cap);
         }
     }
 }
@@ -1035,19 +1002,7 @@ int scan_items(kv_sketch *const *cases, int ncase, kv_sketch *const *ctrls, int 
     *n_hits = 0;
     if (n_items == 0) return KV_OK;
     NovelParams p;
-    memset(&p, 0, sizeof(p));
-    const int k = cases[0]->h.ksize, fam = cases[0]->h.hashfam;
-    for (int c = 0; c < ncase + nctrl; ++c) {
-        const kv_sketch *s = c < ncase ? cases[c] : ctrls[c - ncase];
-        KV_REQUIRE(s, KV_ERR_ARG, "kv_novel_scan_hashes: null sketch");
-        { const int rc = kv_sketch_ready(s); if (rc != KV_OK) return rc; }
-        KV_REQUIRE(s->h.ksize == k && s->h.hashfam == fam, KV_ERR_ARG,
-                   "all sketches of one scan must share k and hash function");
-        p.sk[c] = s->d_desc;
-    }
-    p.hp = make_hash_params(k, fam);
-    p.ncase = ncase; p.nctrl = nctrl;
-    p.case_min = case_min; p.ctrl_max = ctrl_max;
+    { const int rc = novel_params(p, "kv_novel_scan_hashes", cases, ncase, ctrls, nctrl, case_min, ctrl_max); if (rc != KV_OK) return rc; }
     hipStream_t st = kv_stream();
     // pairs (want_hash): every k-mer once, no verdict cache, several first probes in flight (KV_NOVEL_PAIRS=0: the list kernel)
     const bool pairs = want_hash && !(kv_knob("KV_NOVEL_PAIRS") && atoi(kv_knob("KV_NOVEL_PAIRS")) == 0);
@@ -1174,9 +1129,6 @@ extern "C" int kv_novel_scan_set(const kv_reads *reads, int kind, int ksize, int
     // k-mer: from the 2-bit form of equal-length reads that is ~305 lane-instructions per occurrence (k_novel_mark_2bit), which is what
     // cutting, splitting and combining the shard costs per occurrence at 30x and more than it costs at a shard's 4-15x (measured per
     // rank of config 2: 3.1 -> 1.8 ms at N = 8).  KV_SET_SCAN=skm keeps the bucketed scan; other batches take it as before.
-    const char *how = kv_knob("KV_SET_SCAN"), *nm2 = kv_knob("KV_NOVEL_2BIT"), *forced = kv_knob("KV_NOVEL_PATH");
-    const bool two_bit = fam == HF_MURMUR && ksize >= SKM_MIN_K && ksize <= SKM_MAX_K && reads->uni_len >= (uint32_t)ksize && reads->uni_per_tile != 0 &&
-                         !(how && strcmp(how, "skm") == 0) && !(nm2 && atoi(nm2) == 0) && !(forced && strcmp(forced, "tiles") == 0);
-    const bool use_skm = !two_bit && kv_skm_eligible_kind(fam, ksize, reads, n_kmers, true);
+    const bool use_skm = !two_bit_mark(reads, fam, ksize, true) && kv_skm_eligible_kind(fam, ksize, reads, n_kmers, true);
     return scan_reads(p, reads, fam, n_kmers, use_skm, []() { return KV_OK; }, nullptr, 0, out);
 }

@@ -234,6 +234,49 @@ __device__ __forceinline__ bool novel_test_fast(const NovelShared &ns, const Nov
     return true;
 }
 
+// One 8-way set of the verdict cache (64 bytes, four 16-byte loads): cached = h if the set holds h, else ~h, and slot = where
+// novel_test_fast writes h once a control rejects it -- the way the caller names, or, if that one is taken, the first free way
+// (none free: the own way is overwritten).  Which set, and which way of it, are the caller's choice: they only set the hit rate.
+// (plain loads: a stale line can only hide an entry (a miss), never invent one; returned by value: with two reference
+// parameters k_novel_mark_2bit did not compile to the code it had)
+struct VcacheProbe { unsigned long long *slot; unsigned long long cached; };
+__device__ __forceinline__ VcacheProbe vcache_set_probe(const unsigned long long *set, uint64_t h, uint32_t own_way)
+{
+    const ulonglong2 e0 = ((const ulonglong2 *)set)[0], e1 = ((const ulonglong2 *)set)[1];
+    const ulonglong2 e2 = ((const ulonglong2 *)set)[2], e3 = ((const ulonglong2 *)set)[3];
+    const unsigned long long e[8] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, e3.x, e3.y};
+    bool hit = false;
+    uint32_t way = own_way, empty = 8;
+#pragma unroll
+    for (int w = 7; w >= 0; --w) {
+        hit |= e[w] == h;
+        if (e[w] == 0) empty = (uint32_t)w;
+    }
+    if (e[way] != 0 && empty < 8) way = empty;
+    VcacheProbe r;
+    r.slot = const_cast<unsigned long long *>(set) + way;
+    r.cached = hit ? h : ~h;
+    return r;
+}
+
+// The interesting lanes of a wave append their hits to a list: one atomicAdd per wave, a lane's place from its rank in the ballot,
+// then `tag` (the item's tag, or its hash) and the S abundances of h.  Hits past `cap` are counted but not stored.
+__device__ __forceinline__ void novel_hit_append(const NovelParams &p, bool interesting, uint64_t h, uint64_t tag, uint64_t *hit_tag,
+                                                 uint8_t *hit_abund, unsigned long long *hit_count, uint64_t cap)
+{
+    const unsigned long long ballot = __ballot(interesting);
+    if (!ballot) return;
+    const int lane = threadIdx.x & 63, S = p.ncase + p.nctrl;
+    unsigned long long first = 0;
+    if (lane == 0) first = atomicAdd(hit_count, (unsigned long long)__popcll(ballot));
+    first = __shfl(first, 0);
+    if (!interesting) return;
+    const uint64_t pos = first + (uint64_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (pos >= cap) return;
+    hit_tag[pos] = tag;
+    for (int c = 0; c < S; ++c) hit_abund[pos * (uint64_t)S + c] = (uint8_t)sketch_get(p.sk[c], h);
+}
+
 // The same predicate for the few k-mers that survive the first probe of the list scan (k_skm_novel_list): there the chain of
 // dependent probes novel_test_fast spends -- the case's other tables, then control after control -- is a round trip to HBM each in
 // front of a workgroup barrier, so the probes that decide nearly every k-mer are requested together: up to eight tables of the first

@@ -144,16 +144,10 @@ __global__ __launch_bounds__(ROUTE_MAX_WG) void k_route_scan(RouteParams p)
     __shared__ uint64_t wsum[ROUTE_MAX_WG / 64];
     const uint32_t d = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t v = threadIdx.x < p.nwg ? p.seg_count[(uint64_t)d * p.nwg + threadIdx.x] : 0;
-    uint64_t incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint64_t up = __shfl_up(incl, s);
-        if (lane >= (uint32_t)s) incl += up;
-    }
+    const uint64_t incl = wave_incl_scan(v);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
+    const uint64_t before = waves_before(wsum, wave);
     if (threadIdx.x < p.nwg) p.seg_off[(uint64_t)d * p.nwg + threadIdx.x] = before + incl - v;
     if (threadIdx.x == ROUTE_MAX_WG - 1) p.ctr[2 + d] = before + incl;
 }

@@ -316,16 +316,10 @@ __global__ __launch_bounds__(1024) void k_mex_scan_chunks(const uint32_t *cnt, u
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * 1024u + threadIdx.x;
     const uint64_t v = i < n ? (uint64_t)min(cnt[i], cap1) : 0ull;
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), d);
-        if (lane >= (uint32_t)d) incl += (uint64_t)lo | ((uint64_t)hi << 32);
-    }
+    const uint64_t incl = wave_incl_scan(v);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
+    const uint64_t before = waves_before(wsum, wave);
     if (i < n) off[i] = before + incl - v;
     if (threadIdx.x == 1023) part[blockIdx.x] = before + incl;
 }
@@ -340,16 +334,10 @@ __global__ __launch_bounds__(1024) void k_mex_scan_parts(uint64_t *part, uint64_
     for (uint64_t first = 0; first < n_parts; first += 1024) {
         const uint64_t i = first + threadIdx.x;
         const uint64_t v = i < n_parts ? part[i] : 0ull;
-        uint64_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), d);
-            if (lane >= (uint32_t)d) incl += (uint64_t)lo | ((uint64_t)hi << 32);
-        }
+        const uint64_t incl = wave_incl_scan(v);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
-        uint64_t before = carry_sh;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
+        const uint64_t before = waves_before(wsum, wave, (uint64_t)carry_sh);
         if (i < n_parts) part[i] = before + incl - v;
         __syncthreads();
         if (threadIdx.x == 1023) carry_sh = before + incl;

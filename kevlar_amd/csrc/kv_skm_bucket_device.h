@@ -290,7 +290,7 @@ __device__ __forceinline__ void skm_walk_bucket(const SkmGeom &sg, uint32_t b, u
         const uint32_t NR = cnt2[sgm], i = g * 64u + lane;      // (the name the code below knows the bound by)
         const uint32_t nk = i < NR ? skm_hdr_n(hdr) : 0u;
         const uint32_t nu = (nk + G - 1u) / G;          // units of this record
-        uint32_t incl = nu;
+        uint32_t incl = nu;                             // (wave_incl_scan of kv_scan_device.h written out: through the helper this kernel did not compile to the same code)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t up = __shfl_up(incl, d);

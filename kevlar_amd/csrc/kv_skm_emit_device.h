@@ -327,12 +327,7 @@ __global__ __launch_bounds__(SKM_THREADS1, 6) void k_skm_emit(ReadsDev rd, uint3
 #pragma unroll
         for (int round = 0; round < 3; ++round) {
             if ((uint32_t)round < nrounds) {
-                uint32_t v = (uint32_t)__popc(my_starts[round]);
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(v, d);
-                    if (lane >= d) v += up;
-                }
+                const uint32_t v = wave_incl_scan((uint32_t)__popc(my_starts[round]));
                 incl[round] = v;
                 if (lane == 63) sh.wtot[round][threadIdx.x >> 6] = v;
             }
@@ -517,7 +512,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : 6) void k_skm_emit_w
             const uint32_t nv = min((uint32_t)CH, nk - j);
             startmask = diff & ((2u << (nv - 1u)) - 1u);
         }
-        uint32_t incl = (uint32_t)__popc(startmask);
+        uint32_t incl = (uint32_t)__popc(startmask);     // (wave_incl_scan of kv_scan_device.h written out: through the helper this kernel did not compile to the same code)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t upv = __shfl_up(incl, d);
@@ -937,7 +932,7 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
                 h[j] = f < F2 ? hist[f] : 0u;
                 sum += h[j];
             }
-            uint32_t incl = sum;
+            uint32_t incl = sum;                        // (wave_incl_scan of kv_scan_device.h written out: through the helper this kernel did not compile to the same code)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const uint32_t up = __shfl_up(incl, d);
