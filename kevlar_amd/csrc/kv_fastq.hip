@@ -24,7 +24,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -287,6 +286,21 @@ struct KvFastqDevice {
     bool done = false;
 };
 
+static bool fq_stage_on()
+{
+    const char *stage_env = kv_knob("KV_STAGE");
+    return !(stage_env && atoi(stage_env) == 0);
+}
+
+// bytes [off, off + n) of the file to d_dst on the stream: big stretches through the pinned staging buffers (KV_STAGE=0: straight
+// from the mapping, as small ones go)
+static int fq_upload(KvFastqDevice *d, uint8_t *d_dst, uint64_t off, uint64_t n, hipStream_t st)
+{
+    const bool staged = n >= KV_STAGE_MIN_BYTES && fq_stage_on() && d->buf->stage.upload(d_dst, d->fd, off, n, st);
+    if (!staged) KV_HIP(hipMemcpyAsync(d_dst, d->image + off, n, hipMemcpyHostToDevice, st));
+    return KV_OK;
+}
+
 KvFastqDevice *kv_fastq_device_open(const char *path)
 {
     const int fd = open(path, O_RDONLY);
@@ -313,13 +327,10 @@ KvFastqDevice *kv_fastq_device_open(const char *path)
     if (!yes && !d->plain) {
         d->gz = kv_gunzip_open(d->image, d->image_size, &d->buf->gz);
         if (!d->gz) { kv_fastq_device_close(d); return nullptr; }
-        {
-            const char *stage_env = kv_knob("KV_STAGE");
-            if (!(stage_env && atoi(stage_env) == 0)) {
-                KvStager *stage = &d->buf->stage;
-                const int fd_ = d->fd;
-                kv_gunzip_set_uploader(d->gz, [stage, fd_](uint8_t *dst, uint64_t off, uint64_t n, hipStream_t st) { return stage->upload(dst, fd_, off, n, st); });
-            }
+        if (fq_stage_on()) {
+            KvStager *stage = &d->buf->stage;
+            const int fd_ = d->fd;
+            kv_gunzip_set_uploader(d->gz, [stage, fd_](uint8_t *dst, uint64_t off, uint64_t n, hipStream_t st) { return stage->upload(dst, fd_, off, n, st); });
         }
     }
     return d;
@@ -340,180 +351,237 @@ void kv_fastq_device_close(KvFastqDevice *d)
     delete d;
 }
 
+// ---- kv_fastq_device_next: select input -> text on the device -> count lines -> decide -> line starts and records -> deliver
+// what the steps of a batch share
+struct FqBatch {
+    KvFastqDevice *d;
+    hipStream_t st;
+    KvLap lap;                      // wall time of the steps of a batch on stderr
+    uint64_t max_reads, text_cap, want;
+    double per_read;
+    // this attempt's input: members [m0, m1) or bytes [b0, b0 + fresh) of the file, or a gunzip segment of `fresh` bytes of text
+    size_t m0 = 0, m1 = 0;
+    uint64_t b0 = 0, fresh = 0, total_in = 0;
+    bool final = false;             // the file ends with it
+    int nxt = 0;                    // the text buffer it is built in
+    uint8_t *text = nullptr;
+    uint32_t n_chunks = 0;
+    uint64_t *d_base = nullptr;     // lines in front of every chunk
+    unsigned long long total = 0, n_lines = 0;
+    FqBatch(KvFastqDevice *d_, hipStream_t st_, uint64_t max_reads_) : d(d_), st(st_), lap("[kv_ingest] ", 22, st_), max_reads(max_reads_)
+    {
+        const char *cap_env = kv_knob("KV_INGEST_TEXT_MB");            // tests shrink the batches
+        text_cap = (cap_env ? strtoull(cap_env, nullptr, 10) : 4096ull) << 20;
+        per_read = d->bytes_per_read > 0 ? d->bytes_per_read : 280.0;
+        want = std::min<uint64_t>((uint64_t)((double)max_reads * per_read * 1.02) + 65536, text_cap);
+    }
+};
+
+// members (or, for an uncompressed file, bytes; or a decoded gunzip segment) of this attempt
+static int fq_select(FqBatch &b)
+{
+    KvFastqDevice *d = b.d;
+    b.m0 = b.m1 = d->next_member;
+    b.fresh = 0;
+    b.b0 = d->next_byte;
+    bool gz_last = false;
+    if (d->gz) {
+        const uint64_t ask = b.want > d->carry_len + (1u << 20) ? b.want - d->carry_len : (1u << 20);
+        KV_STEP(kv_gunzip_decode(d->gz, ask + ask / 20, &b.fresh, &gz_last));
+    } else if (d->plain) {
+        b.fresh = std::min<uint64_t>(d->image_size - b.b0, b.want > d->carry_len + 65536 ? b.want - d->carry_len : 65536);
+    } else {
+        while (b.m1 < d->members.size() && (b.m1 == b.m0 || d->carry_len + b.fresh + d->members[b.m1].isize <= b.want)) b.fresh += d->members[b.m1++].isize;
+    }
+    b.lap(d->gz ? "gunzip: decode" : "select");
+    b.final = d->gz ? gz_last : d->plain ? b.b0 + b.fresh == d->image_size : b.m1 == d->members.size();
+    b.total_in = d->carry_len + b.fresh;
+    return KV_OK;
+}
+
+// the carried tail of the previous batch, then the fresh text behind it: uploaded, emitted by the gunzip decoder or inflated
+static int fq_text(FqBatch &b)
+{
+    KvFastqDevice *d = b.d;
+    hipStream_t st = b.st;
+    b.nxt = d->cur ^ 1;
+    KV_HIP(d->text[b.nxt].need(kv_round_up(b.total_in + 64, 4096)));
+    uint8_t *text = b.text = (uint8_t *)d->text[b.nxt].p;
+    if (d->carry_len) KV_HIP(hipMemcpyAsync(text, (const uint8_t *)d->text[d->cur].p + d->carry_at, d->carry_len, hipMemcpyDeviceToDevice, st));
+    if (d->plain && b.fresh) KV_STEP(fq_upload(d, text + d->carry_len, b.b0, b.fresh, st));
+    if (d->gz && b.fresh) KV_STEP(kv_gunzip_emit(d->gz, text + d->carry_len));
+    if (b.m1 > b.m0) {
+        const uint64_t c0 = d->members[b.m0].in_off, c1 = d->members[b.m1 - 1].in_off + d->members[b.m1 - 1].in_len;
+        // (a damaged member is read at most ~600 bytes past its end before k_inflate catches it: one dynamic block
+        // header, or one row of a stored block; the slack is zeroed so that what it decodes there is an error, not noise)
+        KV_HIP(d->buf->comp.need(kv_round_up(c1 - c0 + KV_INFLATE_SLACK, 4096)));
+        KV_STEP(fq_upload(d, (uint8_t *)d->buf->comp.p, c0, c1 - c0, st));
+        KV_HIP(hipMemsetAsync((uint8_t *)d->buf->comp.p + (c1 - c0), 0, KV_INFLATE_SLACK, st));
+        std::vector<uint64_t> text_off(b.m1 - b.m0);
+        uint64_t at = d->carry_len;
+        for (size_t i = b.m0; i < b.m1; ++i) { text_off[i - b.m0] = at; at += d->members[i].isize; }
+        KV_STEP(kv_bgzf_inflate((const uint8_t *)d->buf->comp.p, c0, d->members.data() + b.m0, b.m1 - b.m0, text_off.data(), text, d->buf->scratch));
+    }
+    b.lap("text on the device");
+    return KV_OK;
+}
+
+// newlines per chunk and in front of every chunk; the last line of a file gets its newline first
+static int fq_count_lines(FqBatch &b)
+{
+    hipStream_t st = b.st;
+    b.n_chunks = (uint32_t)((b.total_in + 1 + FQ_CHUNK - 1) / FQ_CHUNK);
+    KvCarve<3> scratch({(uint64_t)b.n_chunks * 4, ((uint64_t)b.n_chunks + 1) * 8, 256});
+    KV_HIP(scratch.from(b.d->buf->scratch));
+    uint32_t *d_counts = scratch.at<uint32_t>(0);
+    b.d_base = scratch.at<uint64_t>(1);
+    unsigned long long *d_ctr = scratch.at<unsigned long long>(2);
+    b.total = b.total_in;
+    if (b.final) {
+        hipLaunchKernelGGL(k_terminate, dim3(1), dim3(1), 0, st, b.text, b.total_in, d_ctr);
+        KV_HIP(hipMemcpyAsync(&b.total, d_ctr, 8, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipStreamSynchronize(st));
+    }
+    {
+        KvProfScope prof("k_count_lines");
+        hipLaunchKernelGGL(k_count_lines, dim3(b.n_chunks), dim3(FQ_THREADS), 0, st, (const uint8_t *)b.text, (uint64_t)b.total, d_counts);
+        kv_excl_scan_launch(d_counts, b.n_chunks, b.d_base, st);
+    }
+    KV_HIP(hipGetLastError());
+    KV_HIP(hipMemcpyAsync(&b.n_lines, b.d_base + b.n_chunks, 8, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipStreamSynchronize(st));
+    return KV_OK;
+}
+
+// what becomes of the text now that its lines are counted
+enum FqVerdict {
+    FQ_SERVE,          // its first n whole records are the batch (n = 0 with the file at its end: nothing but a blank tail)
+    FQ_MORE_GUNZIP,    // fewer records than asked for: the text waits as the carry and another gunzip segment joins it
+    FQ_MORE_INPUT,     // not one whole record: the members (bytes) go back and the budget doubles
+    FQ_END,            // blank lines behind the last record: the file is over
+    FQ_CUT_RECORD      // the file ends inside a record
+};
+static int fq_decide(const FqBatch &b, uint64_t n, FqVerdict *verdict)
+{
+    const KvFastqDevice *d = b.d;
+    *verdict = FQ_SERVE;
+    // the segment held fewer records than asked for (its size is a guess from the compression ratio so far) and the text budget is
+    // not spent
+    if (d->gz && !b.final && b.n_lines / 4 < b.max_reads && (b.total_in < b.text_cap || b.n_lines < 4)) *verdict = FQ_MORE_GUNZIP;
+    else if (n == 0 && !b.final) *verdict = FQ_MORE_INPUT;      // (huge records or a tiny budget)
+    else if (n == 0 && b.final && b.n_lines % 4 != 0) {
+        // blank lines behind the last record (a common way for a FASTQ file to end) are not a partial record: the few
+        // bytes are looked at on the host; only a genuinely cut record sends the file to the host parser
+        bool blank = b.total_in <= 4096;
+        if (blank) {
+            unsigned char tail[4096];
+            KV_HIP(hipMemcpyAsync(tail, b.text, b.total_in, hipMemcpyDeviceToHost, b.st));
+            KV_HIP(hipStreamSynchronize(b.st));
+            for (uint64_t i = 0; i < b.total_in && blank; ++i) blank = tail[i] == '\n' || tail[i] == '\r' || tail[i] == ' ' || tail[i] == '\t';
+        }
+        *verdict = blank ? FQ_END : FQ_CUT_RECORD;
+    }
+    return KV_OK;
+}
+
+// the start of every line of the first n records, each record checked and measured; the reader's state moves on to this batch
+static int fq_records(FqBatch &b, uint64_t n, uint64_t **d_seq_start, uint32_t **d_seq_len, std::vector<uint32_t> *lens)
+{
+    KvFastqDevice *d = b.d;
+    hipStream_t st = b.st;
+    KV_HIP(d->buf->lines.need(kv_round_up((4 * n + 2) * 8, 256)));
+    uint64_t *line_start = (uint64_t *)d->buf->lines.p;
+    KV_HIP(hipMemsetAsync(line_start, 0, 8, st));
+    KvCarve<3> recs({n * 8, n * 4, 256});
+    KV_HIP(recs.from(d->buf->recs));
+    *d_seq_start = recs.at<uint64_t>(0);
+    *d_seq_len = recs.at<uint32_t>(1);
+    unsigned long long *d_bad = recs.at<unsigned long long>(2);
+    KV_HIP(hipMemsetAsync(d_bad, 0xFF, 8, st));
+    {
+        KvProfScope prof("k_line_starts");
+        hipLaunchKernelGGL(k_line_starts, dim3(b.n_chunks), dim3(FQ_THREADS), 0, st, (const uint8_t *)b.text, (uint64_t)b.total, (const uint64_t *)b.d_base,
+                           (uint64_t)(4 * n), line_start);
+    }
+    {
+        KvProfScope prof("k_records");
+        hipLaunchKernelGGL(k_records, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, (const uint8_t *)b.text,
+                           (const uint64_t *)line_start, n, *d_seq_start, *d_seq_len, d_bad);
+    }
+    KV_HIP(hipGetLastError());
+    lens->resize(n);
+    unsigned long long bad = 0, consumed = 0;
+    KV_HIP(hipMemcpyAsync(lens->data(), *d_seq_len, n * 4, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(&consumed, line_start + 4 * n, 8, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipStreamSynchronize(st));
+    if (bad != ~0ull) {
+        kv_set_error("%s: record %llu of the batch is not four-line FASTQ", d->path.c_str(), bad);
+        return KV_ERR_TYPE;
+    }
+    d->carry_at = consumed;
+    d->carry_len = b.total - consumed;
+    if (b.final && d->carry_len == 0) d->done = true;
+    d->bytes_per_read = (double)consumed / (double)n;
+    d->d_line_start = line_start;
+    d->n_batch = n;
+    b.lap("lines and records");
+    return KV_OK;
+}
+
 int kv_fastq_device_next(KvFastqDevice *d, uint64_t max_reads, kv_reads **reads_out, uint64_t *n_out)
 {
     *n_out = 0;
     *reads_out = nullptr;
     if (d->done) return KV_OK;             // (the batch served last stays served: its records can still be fetched)
-    hipStream_t st = kv_stream();
-    const bool verbose = kv_knob("KV_INGEST_VERBOSE") != nullptr;   // wall time of the steps of a batch on stderr
-    auto t_mark = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!verbose) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[kv_ingest] %-22s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_mark).count());
-        t_mark = now;
-    };
-    const char *cap_env = kv_knob("KV_INGEST_TEXT_MB");            // tests shrink the batches
-    const uint64_t text_cap = (cap_env ? strtoull(cap_env, nullptr, 10) : 4096ull) << 20;
-    const double per_read = d->bytes_per_read > 0 ? d->bytes_per_read : 280.0;
-    uint64_t want = std::min<uint64_t>((uint64_t)((double)max_reads * per_read * 1.02) + 65536, text_cap);
+    FqBatch b(d, kv_stream(), max_reads);
     for (;;) {
-        // ---- members (or, for an uncompressed file, bytes) of this batch
-        const size_t m0 = d->next_member;
-        size_t m1 = m0;
-        uint64_t fresh = 0;
-        const uint64_t b0 = d->next_byte;
-        bool gz_last = false;
-        if (d->gz) {
-            const uint64_t ask = want > d->carry_len + (1u << 20) ? want - d->carry_len : (1u << 20);
-            const int rc = kv_gunzip_decode(d->gz, ask + ask / 20, &fresh, &gz_last);
-            if (rc != KV_OK) return rc;
-        } else if (d->plain) {
-            fresh = std::min<uint64_t>(d->image_size - b0, want > d->carry_len + 65536 ? want - d->carry_len : 65536);
-        } else {
-            while (m1 < d->members.size() && (m1 == m0 || d->carry_len + fresh + d->members[m1].isize <= want)) fresh += d->members[m1++].isize;
-        }
-        lap(d->gz ? "gunzip: decode" : "select");
-        const bool final = d->gz ? gz_last : d->plain ? b0 + fresh == d->image_size : m1 == d->members.size();
-        const uint64_t total_in = d->carry_len + fresh;
-        if (total_in == 0) { d->done = true; return KV_OK; }     // end of file: nothing of the previous batch has been touched
+        KV_STEP(fq_select(b));
+        if (b.total_in == 0) { d->done = true; return KV_OK; }     // end of file: nothing of the previous batch has been touched
         // (the batch served last -- its text buffer, its line starts, n_batch -- stays fetchable until a NEW batch with records
         // in it has been produced: a caller that kept it asks once more only to learn that the file has ended, and a file that
         // ends in blank lines gets here with a carry of a byte or two)
-        const int nxt = d->cur ^ 1;
-        KV_HIP(d->text[nxt].need(kv_round_up(total_in + 64, 4096)));
-        uint8_t *text = (uint8_t *)d->text[nxt].p;
-        if (d->carry_len) KV_HIP(hipMemcpyAsync(text, (const uint8_t *)d->text[d->cur].p + d->carry_at, d->carry_len, hipMemcpyDeviceToDevice, st));
-        if (d->plain && fresh) {
-            // big stretches through the pinned staging buffers (KV_STAGE=0: straight from the mapping, as small ones go)
-            const char *stage_env = kv_knob("KV_STAGE");
-            const bool staged = fresh >= (64u << 20) && !(stage_env && atoi(stage_env) == 0) && d->buf->stage.upload(text + d->carry_len, d->fd, b0, fresh, st);
-            if (!staged) KV_HIP(hipMemcpyAsync(text + d->carry_len, d->image + b0, fresh, hipMemcpyHostToDevice, st));
-        }
-        if (d->gz && fresh) { const int rc = kv_gunzip_emit(d->gz, text + d->carry_len); if (rc != KV_OK) return rc; }
-        if (m1 > m0) {
-            const uint64_t c0 = d->members[m0].in_off, c1 = d->members[m1 - 1].in_off + d->members[m1 - 1].in_len;
-            // (a damaged member is read at most ~600 bytes past its end before k_inflate catches it: one dynamic block
-            // header, or one row of a stored block; the slack is zeroed so that what it decodes there is an error, not noise)
-            KV_HIP(d->buf->comp.need(kv_round_up(c1 - c0 + KV_INFLATE_SLACK, 4096)));
-            {
-                const char *stage_env = kv_knob("KV_STAGE");
-                const bool staged = c1 - c0 >= (64u << 20) && !(stage_env && atoi(stage_env) == 0) && d->buf->stage.upload((uint8_t *)d->buf->comp.p, d->fd, c0, c1 - c0, st);
-                if (!staged) KV_HIP(hipMemcpyAsync(d->buf->comp.p, d->image + c0, c1 - c0, hipMemcpyHostToDevice, st));
-            }
-            KV_HIP(hipMemsetAsync((uint8_t *)d->buf->comp.p + (c1 - c0), 0, KV_INFLATE_SLACK, st));
-            std::vector<uint64_t> text_off(m1 - m0);
-            uint64_t at = d->carry_len;
-            for (size_t i = m0; i < m1; ++i) { text_off[i - m0] = at; at += d->members[i].isize; }
-            const int rc = kv_bgzf_inflate((const uint8_t *)d->buf->comp.p, c0, d->members.data() + m0, m1 - m0, text_off.data(), text, d->buf->scratch);
-            if (rc != KV_OK) return rc;
-        }
-        lap("text on the device");
-        // ---- lines
-        const uint32_t n_chunks = (uint32_t)((total_in + 1 + FQ_CHUNK - 1) / FQ_CHUNK);
-        const size_t b_counts = kv_round_up((uint64_t)n_chunks * 4, 256), b_base = kv_round_up(((uint64_t)n_chunks + 1) * 8, 256);
-        KV_HIP(d->buf->scratch.need(b_counts + b_base + 256));
-        uint32_t *d_counts = (uint32_t *)d->buf->scratch.p;
-        uint64_t *d_base = (uint64_t *)((unsigned char *)d->buf->scratch.p + b_counts);
-        unsigned long long *d_ctr = (unsigned long long *)((unsigned char *)d->buf->scratch.p + b_counts + b_base);
-        unsigned long long total = total_in;
-        if (final) {
-            hipLaunchKernelGGL(k_terminate, dim3(1), dim3(1), 0, st, text, total_in, d_ctr);
-            KV_HIP(hipMemcpyAsync(&total, d_ctr, 8, hipMemcpyDeviceToHost, st));
-            KV_HIP(hipStreamSynchronize(st));
-        }
-        unsigned long long n_lines = 0;
-        {
-            KvProfScope prof("k_count_lines");
-            hipLaunchKernelGGL(k_count_lines, dim3(n_chunks), dim3(FQ_THREADS), 0, st, (const uint8_t *)text, (uint64_t)total, d_counts);
-            kv_excl_scan_launch(d_counts, n_chunks, d_base, st);
-        }
-        KV_HIP(hipGetLastError());
-        KV_HIP(hipMemcpyAsync(&n_lines, d_base + n_chunks, 8, hipMemcpyDeviceToHost, st));
-        KV_HIP(hipStreamSynchronize(st));
-        uint64_t n = std::min<uint64_t>(n_lines / 4, max_reads);
-        if (d->gz && !final && n_lines / 4 < max_reads && (total_in < text_cap || n_lines < 4)) {
-            // the segment held fewer records than asked for (its size is a guess from the compression ratio so far) and the text
-            // budget is not spent: what has been inflated waits as the carry and another segment joins it
-            const uint64_t have = n_lines / 4;
-            const double each = have ? (double)total_in / (double)have : per_read;
+        KV_STEP(fq_text(b));
+        KV_STEP(fq_count_lines(b));
+        const uint64_t n = std::min<uint64_t>(b.n_lines / 4, max_reads);
+        FqVerdict verdict;
+        KV_STEP(fq_decide(b, n, &verdict));
+        switch (verdict) {
+        case FQ_MORE_GUNZIP: {
+            const uint64_t have = b.n_lines / 4;
+            const double each = have ? (double)b.total_in / (double)have : b.per_read;
             d->n_batch = 0;               // the other text buffer -- the previous batch's -- is written next
-            d->cur = nxt;
+            d->cur = b.nxt;
             d->carry_at = 0;
-            d->carry_len = total_in;
-            want = std::min<uint64_t>(total_in + (uint64_t)((double)(max_reads - have) * each * 1.05) + (1u << 20), std::max<uint64_t>(text_cap, total_in + (1u << 20)));
+            d->carry_len = b.total_in;
+            b.want = std::min<uint64_t>(b.total_in + (uint64_t)((double)(max_reads - have) * each * 1.05) + (1u << 20), std::max<uint64_t>(b.text_cap, b.total_in + (1u << 20)));
             continue;
         }
-        if (n == 0 && !final) {           // not one whole record yet (huge records or a tiny budget): take more members
-            d->next_member = m0;
-            d->next_byte = b0;
-            want = want * 2 + 65536;
+        case FQ_MORE_INPUT:
+            d->next_member = b.m0;
+            d->next_byte = b.b0;
+            b.want = b.want * 2 + 65536;
             continue;
-        }
-        if (n == 0 && final && n_lines % 4 != 0) {
-            // blank lines behind the last record (a common way for a FASTQ file to end) are not a partial record: the few
-            // bytes are looked at on the host; only a genuinely cut record sends the file to the host parser
-            bool blank = total_in <= 4096;
-            if (blank) {
-                unsigned char tail[4096];
-                KV_HIP(hipMemcpyAsync(tail, text, total_in, hipMemcpyDeviceToHost, st));
-                KV_HIP(hipStreamSynchronize(st));
-                for (uint64_t i = 0; i < total_in && blank; ++i) blank = tail[i] == '\n' || tail[i] == '\r' || tail[i] == ' ' || tail[i] == '\t';
-            }
-            if (!blank) {
-                kv_set_error("%s ends inside a FASTQ record", d->path.c_str());
-                return KV_ERR_TYPE;
-            }
+        case FQ_CUT_RECORD:
+            kv_set_error("%s ends inside a FASTQ record", d->path.c_str());
+            return KV_ERR_TYPE;
+        case FQ_END:
             d->done = true; d->carry_len = 0;
             return KV_OK;
+        case FQ_SERVE:
+            break;
         }
-        d->next_member = m1;
-        d->next_byte = b0 + (d->plain ? fresh : 0);
+        d->next_member = b.m1;
+        d->next_byte = b.b0 + (d->plain ? b.fresh : 0);
         if (n == 0) { d->done = true; d->carry_len = 0; return KV_OK; }      // blank tail: the previous batch is still the current one
-        d->cur = nxt;
+        d->cur = b.nxt;
         d->n_batch = 0;
-        // ---- line starts, records
-        KV_HIP(d->buf->lines.need(kv_round_up((4 * n + 2) * 8, 256)));
-        uint64_t *line_start = (uint64_t *)d->buf->lines.p;
-        KV_HIP(hipMemsetAsync(line_start, 0, 8, st));
-        KV_HIP(d->buf->recs.need(kv_round_up(n * 8, 256) + kv_round_up(n * 4, 256) + 256));
-        uint64_t *d_seq_start = (uint64_t *)d->buf->recs.p;
-        uint32_t *d_seq_len = (uint32_t *)((unsigned char *)d->buf->recs.p + kv_round_up(n * 8, 256));
-        unsigned long long *d_bad = (unsigned long long *)((unsigned char *)d->buf->recs.p + kv_round_up(n * 8, 256) + kv_round_up(n * 4, 256));
-        KV_HIP(hipMemsetAsync(d_bad, 0xFF, 8, st));
-        {
-            KvProfScope prof("k_line_starts");
-            hipLaunchKernelGGL(k_line_starts, dim3(n_chunks), dim3(FQ_THREADS), 0, st, (const uint8_t *)text, (uint64_t)total, (const uint64_t *)d_base,
-                               (uint64_t)(4 * n), line_start);
-        }
-        {
-            KvProfScope prof("k_records");
-            hipLaunchKernelGGL(k_records, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 8192)), dim3(256), 0, st, (const uint8_t *)text,
-                               (const uint64_t *)line_start, n, d_seq_start, d_seq_len, d_bad);
-        }
-        KV_HIP(hipGetLastError());
-        std::vector<uint32_t> lens(n);
-        unsigned long long bad = 0, consumed = 0;
-        KV_HIP(hipMemcpyAsync(lens.data(), d_seq_len, n * 4, hipMemcpyDeviceToHost, st));
-        KV_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
-        KV_HIP(hipMemcpyAsync(&consumed, line_start + 4 * n, 8, hipMemcpyDeviceToHost, st));
-        KV_HIP(hipStreamSynchronize(st));
-        if (bad != ~0ull) {
-            kv_set_error("%s: record %llu of the batch is not four-line FASTQ", d->path.c_str(), bad);
-            return KV_ERR_TYPE;
-        }
-        d->carry_at = consumed;
-        d->carry_len = total - consumed;
-        if (final && d->carry_len == 0) d->done = true;
-        d->bytes_per_read = (double)consumed / (double)n;
-        d->d_line_start = line_start;
-        d->n_batch = n;
-        lap("lines and records");
-        const int rc = kv_reads_from_device_text(text, d_seq_start, d_seq_len, lens.data(), n, reads_out);
-        if (rc != KV_OK) return rc;
-        lap("packed batch");
+        uint64_t *d_seq_start = nullptr;
+        uint32_t *d_seq_len = nullptr;
+        std::vector<uint32_t> lens;
+        KV_STEP(fq_records(b, n, &d_seq_start, &d_seq_len, &lens));
+        KV_STEP(kv_reads_from_device_text(b.text, d_seq_start, d_seq_len, lens.data(), n, reads_out));
+        b.lap("packed batch");
         *n_out = n;
         return KV_OK;
     }
@@ -536,11 +604,9 @@ int kv_fastq_device_fetch(KvFastqDevice *d, const uint64_t *idx, uint64_t n, std
     for (uint64_t i = 0; i < n; ++i)
         KV_REQUIRE(idx[i] < d->n_batch, KV_ERR_ARG, "record %llu is not in the current batch of %llu", (unsigned long long)idx[i], (unsigned long long)d->n_batch);
     hipStream_t st = kv_stream();
-    const size_t b_idx = kv_round_up(n * 8, 256), b_ext = kv_round_up(n * 16, 256);
-    KV_HIP(d->buf->fetch.need(2 * b_idx + b_ext));
-    uint64_t *d_idx = (uint64_t *)d->buf->fetch.p;
-    uint64_t *d_ext = (uint64_t *)((unsigned char *)d->buf->fetch.p + b_idx);
-    uint64_t *d_dst = (uint64_t *)((unsigned char *)d->buf->fetch.p + b_idx + b_ext);
+    KvCarve<3> fetch({n * 8, n * 16, n * 8});
+    KV_HIP(fetch.from(d->buf->fetch));
+    uint64_t *d_idx = fetch.at<uint64_t>(0), *d_ext = fetch.at<uint64_t>(1), *d_dst = fetch.at<uint64_t>(2);
     KV_HIP(hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_record_extents, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, (const uint64_t *)d->d_line_start,
                        (const uint64_t *)d_idx, n, d_ext);

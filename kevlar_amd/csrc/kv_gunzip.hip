@@ -26,6 +26,10 @@
 //   5. k_gz_crc     CRC-32 of the text in slices of 16 KB, cut at the member ends the decoders saw; the host joins the slices
 //                   of a member and compares with its trailer (ISIZE too).
 //
+// What the host decides between the launches -- the bytes a segment takes, which found starts become stretches, where long
+// ones are cut, the room of each, the chain rule of step 2 and the CRC ranges of step 5 -- is stated in kv_gunzip_plan.h,
+// plain C++ that tests/test_gunzip_plan.py runs without a GPU; this file holds the kernels and the steps that launch them.
+//
 // The file is taken a segment of compressed bytes at a time; the last tail, the running CRC and the exact bit position
 // travel to the next segment.  Concatenated members are followed inside k_gz_decode.  Tests compare with zlib byte for
 // byte.  Anything unexpected (no block found for megabytes, trailing garbage, corrupt codes, a CRC or length that does not
@@ -33,7 +37,6 @@
 // khmer.ReadParser's gzip stream (kevlar/__init__.py:125-128 opens every *.gz through it).
 #include <algorithm>
 #include <functional>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -42,6 +45,7 @@
 
 #include "kv_internal.h"
 #include "kv_inflate_device.h"
+#include "kv_gunzip_plan.h"       // GzJob, GzGuess, GzResult and the host arithmetic between the launches
 
 namespace {
 
@@ -50,34 +54,8 @@ namespace {
 #define GZ_NOTEXT 0x0100u            // a window position in front of the first byte of the text: no byte, no marker; a match that copies it is invalid
 #define GZ_FAST_LL 9                 // bits of the literal/length lookup table (9: 32 workgroups of LDS per CU)
 #define GZ_SLACK 2048u               // readable zero bytes behind the compressed buffer
-#define GZ_FIND_KEEP 4u                // block starts kept per chunk
 #define GZ_FIND_THREADS 256
 #define GZ_FIND_LIST 1024u           // survivors of the cheap test a chunk may have (more: the later ones are not looked at)
-
-enum { GZ_LANDED = 0, GZ_END = 1, GZ_BAD = 2, GZ_FULL = 3, GZ_SHORT = 4 };
-
-struct GzJob {
-    uint64_t start_bit;              // first symbol (or block header) to decode, relative to the compressed buffer
-    uint64_t target_idx;             // starts[target_idx]: the first start behind start_bit; the stretch stops ON the first start it meets
-    uint64_t out_off;                // symbols
-    uint64_t header_bit;             // header of the block start_bit lies in (== start_bit for a stretch that begins with a block)
-    uint32_t out_cap;
-    uint32_t pad;
-};
-struct GzGuess {
-    uint64_t header_bit;             // a found block start ...
-    uint64_t guess_bit;              // ... and a place inside that block near which a symbol boundary is wanted
-};
-struct GzResult {
-    uint64_t end_bit;
-    uint32_t n_out;
-    uint16_t status;
-    uint16_t members;                // member trailers the stretch passed,
-    uint32_t isize_sum;              // ... the sum of their ISIZE fields,
-    uint32_t trailer_at;             // ... how many symbols the stretch had produced at the first one
-    uint32_t trailer_crc;            // ... and the CRC-32 that one announces
-    uint32_t pad;
-};
 
 __device__ __forceinline__ void br_seek(BitReader &br, const uint32_t *words, uint64_t bit)
 {
@@ -827,17 +805,14 @@ struct KvGunzip {
     uint32_t isize_total = 0;         // of the members that have ended so far (mod 2^32, as the field is)
     uint32_t crc_run = 0;             // CRC-32 of the text of the member that is open at pos_bit
     bool crc_on = true;               // off: KV_GUNZIP_CRC=0, or a stretch passed more than one member end (their starts in the text are not recorded)
-    std::vector<std::pair<uint64_t, uint32_t>> pending_ends;      // of the pending segment: (text offset a member ends at, the CRC-32 its trailer holds)
 
     uint32_t chunk_bytes = 16384;
     KvGunzipArenas own, *a = &own;    // device buffers: the caller's (pooled across files) or this object's
     // the segment decoded by kv_gunzip_decode and not yet emitted
-    std::vector<uint64_t> v_off, v_base;
-    std::vector<uint32_t> v_n;
-    uint64_t pending_text = 0, pending_pos = 0;
-    uint32_t pending_isize = 0;
-    bool pending_done = false, pending = false, window_ready = false;
-    const uint64_t *d_off = nullptr, *d_base = nullptr;           // device copies of v_off / v_base / v_n
+    GzChain chain;                    // its accepted stretches, member ends, bytes of text, ISIZE sum, whether the stream ends with it
+    uint64_t pending_pos = 0;         // the bit in the file it ends on
+    bool pending = false, window_ready = false;
+    const uint64_t *d_off = nullptr, *d_base = nullptr;           // device copies of chain.v_off / v_base / v_n
     const uint32_t *d_n = nullptr;
     const uint16_t *d_tails = nullptr;                            // the resolved tails of the pending segment
     unsigned int *d_no_text = nullptr;                            // set by k_gz_resolve: a match of the pending segment copied what is in front of the text
@@ -876,271 +851,199 @@ void kv_gunzip_stats(const KvGunzip *g, uint64_t out[4])
     out[0] = g->stat_segments; out[1] = g->stat_jobs; out[2] = g->stat_dropped; out[3] = g->stat_repairs;
 }
 
-static int gz_run_jobs(const uint8_t *d_comp, uint64_t n_bytes, bool is_file_end, const GzJob *jobs, size_t n, GzJob *d_jobs,
-                       const unsigned long long *d_starts, const unsigned long long *d_headers, uint64_t terminal_bit, bool exact, GzResult *d_results, unsigned long long *d_ctr, uint16_t *d_syms,
-                       GzResult *results)
+// ---- kv_gunzip_decode: upload -> find -> cut -> plan and decode -> chain -> length check -> tails -> publish.  The arithmetic
+// between the launches (which starts exist, what is accepted, dropped or decoded again) is kv_gunzip_plan.h's.
+// what its steps share
+struct GzSegment {
+    KvGunzip *g;
+    hipStream_t st;
+    KvLap lap;
+    GzExtent x;                       // the compressed bytes of the segment
+    GzStarts s;                       // where its stretches begin
+    GzPlan plan;                      // the first launch's jobs ...
+    std::vector<GzResult> results;    // ... and what they answered
+    uint64_t max_guesses = 0;
+    uint8_t *d_comp = nullptr;
+    unsigned long long *d_cand = nullptr, *d_ctr = nullptr, *d_found = nullptr, *d_starts = nullptr, *d_headers = nullptr;
+    GzGuess *d_guesses = nullptr;
+    GzJob *d_jobs = nullptr;
+    GzResult *d_results = nullptr;
+    uint64_t *d_off = nullptr, *d_base = nullptr;
+    uint32_t *d_n = nullptr;
+    uint16_t *d_syms = nullptr;
+    GzSegment(KvGunzip *g_, hipStream_t st_) : g(g_), st(st_), lap("[kv_gunzip]   ", 20, st_) {}
+};
+
+static int gz_run_jobs(const GzSegment &seg, const GzJob *jobs, size_t n, GzResult *results)
 {
-    hipStream_t st = kv_stream();
-    KV_HIP(hipMemcpyAsync(d_jobs, jobs, n * sizeof(GzJob), hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemsetAsync(d_ctr, 0, 8, st));
+    hipStream_t st = seg.st;
+    KV_HIP(hipMemcpyAsync(seg.d_jobs, jobs, n * sizeof(GzJob), hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemsetAsync(seg.d_ctr, 0, 8, st));
     {
         KvProfScope prof("k_gz_decode");
         // the LDS window sets how many stretches a CU holds (1 K symbols: 32 = 8 waves per SIMD); a match that reaches further
         // back reads the symbols the wave itself stored to HBM, behind a workgroup-scope release
         const unsigned grid = (unsigned)std::min<uint64_t>(n, 32ull * (uint64_t)kv_device_cus());
-        hipLaunchKernelGGL((exact ? k_gz_decode<10, true> : k_gz_decode<10, false>), dim3(grid), dim3(64), 0, st, d_comp, n_bytes, is_file_end ? 1 : 0, (const GzJob *)d_jobs,
-                           (uint32_t)n, d_starts, d_headers, terminal_bit, d_syms, d_results, d_ctr);
+        hipLaunchKernelGGL((seg.plan.exact ? k_gz_decode<10, true> : k_gz_decode<10, false>), dim3(grid), dim3(64), 0, st, (const uint8_t *)seg.d_comp, seg.x.n_bytes,
+                           seg.x.is_file_end ? 1 : 0, (const GzJob *)seg.d_jobs, (uint32_t)n, (const unsigned long long *)seg.d_starts, (const unsigned long long *)seg.d_headers,
+                           seg.s.stop_rel, seg.d_syms, seg.d_results, seg.d_ctr);
     }
     KV_HIP(hipGetLastError());
-    KV_HIP(hipMemcpyAsync(results, d_results, n * sizeof(GzResult), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(results, seg.d_results, n * sizeof(GzResult), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     return KV_OK;
 }
 
-// Decode the next segment: about `want_text` bytes of text (at least one chunk).  *text_bytes = what kv_gunzip_emit will
-// deliver.  KV_ERR_TYPE: the stream is not something this decoder handles (the caller falls back to zlib).
-int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool *last)
+// the compressed bytes of the segment and the margin behind them -> comp, zeros behind them
+static int gz_upload(GzSegment &seg)
 {
-    *text_bytes = 0;
-    *last = g->done;
-    KV_REQUIRE(!g->pending, KV_ERR_ARG, "kv_gunzip_decode: the previous segment has not been emitted");
-    if (g->done) return KV_OK;
-    hipStream_t st = kv_stream();
-    const bool verbose = kv_knob("KV_INGEST_VERBOSE") != nullptr;
-    auto t_mark = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!verbose) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[kv_gunzip]   %-20s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_mark).count());
-        t_mark = now;
-    };
-    const uint32_t CH = g->chunk_bytes;
-    // consecutive pieces of an arena, each a multiple of 256 bytes
-    auto take = [](unsigned char *&at, uint64_t bytes) { unsigned char *piece = at; at += kv_round_up(bytes, 256); return piece; };
-    const uint64_t margin = 4ull << 20;
-    // ---- the compressed bytes of the segment, and behind them a margin in which the next segment's first block is looked for
-    const uint64_t first_byte = (g->pos_bit >> 3) & ~255ull;
-    const uint64_t seg = std::max<uint64_t>((uint64_t)((double)want_text / g->ratio), 4ull * CH);
-    const uint64_t seg_end = std::min<uint64_t>(kv_round_up(first_byte + seg, CH), g->size);
-    const uint64_t upto = std::min<uint64_t>(seg_end + margin, g->size);
-    const bool to_file_end = seg_end == g->size, is_file_end = upto == g->size;
-    const uint64_t n_bytes = upto - first_byte;
-    const uint32_t n_chunks = (uint32_t)((n_bytes + CH - 1) / CH);
-    KV_HIP(g->a->comp.need(kv_round_up((uint64_t)n_chunks * CH + 2 * GZ_SLACK, 4096)));
-    uint8_t *d_comp = (uint8_t *)g->a->comp.p;
+    KvGunzip *g = seg.g;
+    const GzExtent &x = seg.x;
+    const uint64_t padded = (uint64_t)x.n_chunks * g->chunk_bytes + 2 * GZ_SLACK;
+    KV_HIP(g->a->comp.need(kv_round_up(padded, 4096)));
+    seg.d_comp = (uint8_t *)g->a->comp.p;
     // (big stretches through the caller's pinned staging buffers if it has any: kv_gunzip_set_uploader)
-    if (!(g->upload && n_bytes >= (64u << 20) && g->upload(d_comp, first_byte, n_bytes, st)))
-        KV_HIP(hipMemcpyAsync(d_comp, g->image + first_byte, n_bytes, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemsetAsync(d_comp + n_bytes, 0, (uint64_t)n_chunks * CH + 2 * GZ_SLACK - n_bytes, st));
-    lap("upload");
-    const uint64_t b_cand = kv_round_up((uint64_t)n_chunks * GZ_FIND_KEEP * 8, 256);
-    const uint64_t max_guesses = (uint64_t)n_chunks * GZ_FIND_KEEP * 7 + 8;          // seven cuts per stretch at most
-    KV_HIP(g->a->small.need(b_cand + 256 + kv_round_up(max_guesses * sizeof(GzGuess), 256) + kv_round_up(max_guesses * 8, 256)));
-    unsigned char *small = (unsigned char *)g->a->small.p;
-    unsigned long long *d_cand = (unsigned long long *)take(small, b_cand);
-    unsigned long long *d_ctr = (unsigned long long *)take(small, 256);
-    GzGuess *d_guesses = (GzGuess *)take(small, max_guesses * sizeof(GzGuess));
-    unsigned long long *d_found = (unsigned long long *)take(small, max_guesses * 8);
+    if (!(g->upload && x.n_bytes >= KV_STAGE_MIN_BYTES && g->upload(seg.d_comp, x.first_byte, x.n_bytes, seg.st)))
+        KV_HIP(hipMemcpyAsync(seg.d_comp, g->image + x.first_byte, x.n_bytes, hipMemcpyHostToDevice, seg.st));
+    KV_HIP(hipMemsetAsync(seg.d_comp + x.n_bytes, 0, padded - x.n_bytes, seg.st));
+    seg.lap("upload");
+    return KV_OK;
+}
+
+// k_gz_find over every chunk; what it kept becomes the starts
+static int gz_find(GzSegment &seg)
+{
+    KvGunzip *g = seg.g;
+    const GzExtent &x = seg.x;
+    const uint64_t n_cand = (uint64_t)x.n_chunks * GZ_FIND_KEEP;
+    seg.max_guesses = n_cand * 7 + 8;                  // seven cuts per stretch at most
+    // candidates, counters, and the cuts' guesses and answers
+    KvCarve<4> small({n_cand * 8, 256, seg.max_guesses * sizeof(GzGuess), seg.max_guesses * 8});
+    KV_HIP(small.from(g->a->small));
+    seg.d_cand = small.at<unsigned long long>(0);
+    seg.d_ctr = small.at<unsigned long long>(1);
+    seg.d_guesses = small.at<GzGuess>(2);
+    seg.d_found = small.at<unsigned long long>(3);
     {
         KvProfScope prof("k_gz_find");
-        hipLaunchKernelGGL(k_gz_find, dim3(n_chunks), dim3(GZ_FIND_THREADS), CH + GZ_SLACK + 8, st, (const uint8_t *)d_comp, n_bytes, CH, n_chunks, d_cand);
+        hipLaunchKernelGGL(k_gz_find, dim3(x.n_chunks), dim3(GZ_FIND_THREADS), g->chunk_bytes + GZ_SLACK + 8, seg.st, (const uint8_t *)seg.d_comp, x.n_bytes, g->chunk_bytes,
+                           x.n_chunks, seg.d_cand);
     }
     KV_HIP(hipGetLastError());
-    std::vector<unsigned long long> cand((uint64_t)n_chunks * GZ_FIND_KEEP);
-    KV_HIP(hipMemcpyAsync(cand.data(), d_cand, (uint64_t)n_chunks * GZ_FIND_KEEP * 8, hipMemcpyDeviceToHost, st));
-    KV_HIP(hipStreamSynchronize(st));
-    lap("find");
-    // ---- stretches: from the exact position the last segment ended at, then from every found start up to the first one
-    // behind the segment
-    const uint64_t start_rel = g->pos_bit - first_byte * 8, seg_end_rel = (seg_end - first_byte) * 8;
-    std::vector<uint64_t> starts(1, start_rel);
-    bool have_terminal = false;
-    for (uint64_t c = 0; c < (uint64_t)n_chunks * GZ_FIND_KEEP && !have_terminal; ++c) {
-        if (cand[c] == ~0ull || cand[c] <= start_rel) continue;
-        starts.push_back(cand[c]);
-        if (!to_file_end && cand[c] >= seg_end_rel) have_terminal = true;
-    }
-    if (!to_file_end && !have_terminal && !is_file_end) {
-        kv_set_error("no DEFLATE block start within %llu MB behind byte %llu", (unsigned long long)(margin >> 20), (unsigned long long)seg_end);
+    std::vector<unsigned long long> cand(n_cand);
+    KV_HIP(hipMemcpyAsync(cand.data(), seg.d_cand, n_cand * 8, hipMemcpyDeviceToHost, seg.st));
+    KV_HIP(hipStreamSynchronize(seg.st));
+    seg.lap("find");
+    if (!gz_starts(x, cand.data(), n_cand, &seg.s)) {
+        kv_set_error("no DEFLATE block start within %llu MB behind byte %llu", (unsigned long long)(GZ_MARGIN >> 20), (unsigned long long)x.seg_end);
         return KV_ERR_TYPE;
-    }                                                  // (none before the end of the file: the last stretch runs to the end)
-    const uint64_t stop_rel = have_terminal ? starts.back() : ~0ull;             // reaching it ends the segment
-    // ---- long stretches are cut: symbol boundaries inside their first block, found by letting 64 decoders per cut fall
-    // into step (k_gz_sync)
-    std::vector<uint64_t> headers(starts);              // headers[i]: the block header stretch i takes its codes from
-    {
-        // only when the block starts alone leave the device short of work (fewer than 24 stretches per CU), and
-        // then as many pieces as make 32 per CU: every cut costs a header to parse, a tail to resolve and a decoder that
-        // looks for its target between symbols too (k_gz_decode<.., true>, ~15 % more instructions per symbol)
-        const uint64_t wanted = 32ull * (uint64_t)kv_device_cus();
-        // (bits of compressed data a piece should have; 0: no cutting)
-        const uint64_t piece = starts.size() * 4 >= wanted * 3 ? 0 : std::max<uint64_t>(4096ull * 8ull, (seg_end_rel - start_rel) / wanted);
-        std::vector<GzGuess> guesses;
-        const size_t n_blocks = have_terminal ? starts.size() - 1 : starts.size();
-        for (size_t j = 0; j < n_blocks && piece; ++j) {
-            const uint64_t next = j + 1 < starts.size() ? starts[j + 1] : n_bytes * 8;
-            const uint64_t span = next - starts[j];
-            const uint64_t cuts = std::min<uint64_t>(8, span / piece);
-            for (uint64_t i = 1; i < cuts; ++i) {
-                GzGuess gs;
-                gs.header_bit = starts[j];
-                gs.guess_bit = starts[j] + i * (span / cuts);
-                if (guesses.size() < max_guesses) guesses.push_back(gs);
-            }
-        }
-        if (!guesses.empty()) {
-            KV_HIP(hipMemcpyAsync(d_guesses, guesses.data(), guesses.size() * sizeof(GzGuess), hipMemcpyHostToDevice, st));
-            {
-                KvProfScope prof("k_gz_sync");
-                hipLaunchKernelGGL(k_gz_sync, dim3((unsigned)guesses.size()), dim3(64), 0, st, (const uint8_t *)d_comp, n_bytes, (const GzGuess *)d_guesses,
-                                   (uint32_t)guesses.size(), d_found);
-            }
-            KV_HIP(hipGetLastError());
-            std::vector<unsigned long long> found(guesses.size());
-            KV_HIP(hipMemcpyAsync(found.data(), d_found, guesses.size() * 8, hipMemcpyDeviceToHost, st));
-            KV_HIP(hipStreamSynchronize(st));
-            std::vector<std::pair<uint64_t, uint64_t>> all;             // (start, header)
-            for (size_t i = 0; i < starts.size(); ++i) all.emplace_back(starts[i], starts[i]);
-            for (size_t i = 0; i < guesses.size(); ++i) {
-                if (found[i] == ~0ull || found[i] <= guesses[i].header_bit || found[i] >= stop_rel) continue;
-                // (a boundary behind the next block start is of no use: the stretch before it stops at that start)
-                const auto nx = std::upper_bound(starts.begin(), starts.end(), guesses[i].header_bit);
-                if (nx != starts.end() && found[i] >= *nx) continue;
-                all.emplace_back(found[i], guesses[i].header_bit);
-                g->stat_cuts += 1;
-            }
-            std::sort(all.begin(), all.end());
-            starts.clear(); headers.clear();
-            for (const auto &a : all)
-                if (starts.empty() || a.first != starts.back()) { starts.push_back(a.first); headers.push_back(a.second); }
-        }
-        lap("cuts");
     }
-    const size_t n_first = have_terminal ? starts.size() - 1 : starts.size();
-    bool exact = false;                                 // does any stretch begin inside a block?
-    for (size_t i = 0; i < starts.size() && !exact; ++i) exact = headers[i] != starts[i];
-    const double factor = std::min(std::max(2.5 * g->ratio, 8.0), 64.0);
-    // symbols of room for a stretch of `bits` of compressed data
-    auto room = [factor](uint64_t bits) { return (uint32_t)std::min<uint64_t>((uint64_t)((double)(bits / 8 + 1) * factor) + 16384, 0x7ffffff0u); };
-    std::vector<GzJob> jobs(n_first);
-    uint64_t total_cap = 0;
-    for (size_t j = 0; j < n_first; ++j) {
-        // room: up to the next stretch that begins with a block (the starts inside this block may turn out not to be any, and
-        // the stretch then runs on over them)
-        size_t nb = j + 1;
-        while (nb < starts.size() && headers[nb] != starts[nb]) ++nb;
-        const uint64_t next = nb < starts.size() ? starts[nb] : n_bytes * 8;
-        jobs[j].start_bit = starts[j];
-        jobs[j].header_bit = headers[j];
-        jobs[j].target_idx = j + 1;                     // (starts[] on the device ends with ~0)
-        jobs[j].out_off = total_cap;
-        jobs[j].out_cap = room(next - starts[j]);
-        jobs[j].pad = 0;
-        total_cap += kv_round_up(jobs[j].out_cap, 64);
+    return KV_OK;
+}
+
+// long stretches are cut: symbol boundaries inside their first block, found by letting 64 decoders per cut fall into step
+static int gz_cut(GzSegment &seg)
+{
+    const std::vector<GzGuess> guesses = gz_cut_guesses(seg.x, seg.s, 32ull * (uint64_t)kv_device_cus(), seg.max_guesses);
+    if (!guesses.empty()) {
+        KV_HIP(hipMemcpyAsync(seg.d_guesses, guesses.data(), guesses.size() * sizeof(GzGuess), hipMemcpyHostToDevice, seg.st));
+        {
+            KvProfScope prof("k_gz_sync");
+            hipLaunchKernelGGL(k_gz_sync, dim3((unsigned)guesses.size()), dim3(64), 0, seg.st, (const uint8_t *)seg.d_comp, seg.x.n_bytes, (const GzGuess *)seg.d_guesses,
+                               (uint32_t)guesses.size(), seg.d_found);
+        }
+        KV_HIP(hipGetLastError());
+        std::vector<unsigned long long> found(guesses.size());
+        KV_HIP(hipMemcpyAsync(found.data(), seg.d_found, guesses.size() * 8, hipMemcpyDeviceToHost, seg.st));
+        KV_HIP(hipStreamSynchronize(seg.st));
+        seg.g->stat_cuts += gz_merge_cuts(&seg.s, guesses, found.data());
     }
-    const uint64_t repair_room = std::max<uint64_t>(256ull << 20, total_cap / 4);
-    const size_t max_jobs = n_first + 256;
-    KV_HIP(g->a->syms.need((total_cap + repair_room) * 2 + 256));
-    KV_HIP(g->a->meta.need(kv_round_up(max_jobs * sizeof(GzJob), 256) + kv_round_up(max_jobs * sizeof(GzResult), 256) + kv_round_up(max_jobs * 8, 256) * 2 +
-                        kv_round_up(max_jobs * 4, 256) + 2 * kv_round_up((starts.size() + 1) * 8, 256)));
-    unsigned char *meta = (unsigned char *)g->a->meta.p;
-    GzJob *d_jobs = (GzJob *)take(meta, max_jobs * sizeof(GzJob));
-    GzResult *d_results = (GzResult *)take(meta, max_jobs * sizeof(GzResult));
-    uint64_t *d_off = (uint64_t *)take(meta, max_jobs * 8);
-    uint64_t *d_base = (uint64_t *)take(meta, max_jobs * 8);
-    uint32_t *d_n = (uint32_t *)take(meta, max_jobs * 4);
-    unsigned long long *d_starts = (unsigned long long *)take(meta, (starts.size() + 1) * 8);
-    unsigned long long *d_headers = (unsigned long long *)take(meta, (starts.size() + 1) * 8);
+    seg.lap("cuts");
+    return KV_OK;
+}
+
+// room for every stretch, the starts on the device, and the first launch: one decoder per stretch
+static int gz_plan_and_decode(GzSegment &seg)
+{
+    KvGunzip *g = seg.g;
+    const size_t n_starts = seg.s.starts.size();
+    seg.plan = gz_plan_jobs(seg.s, seg.x.n_bytes, g->ratio);
+    const size_t n_first = seg.plan.jobs.size(), max_jobs = n_first + 256;
+    KV_HIP(g->a->syms.need((seg.plan.total_cap + seg.plan.repair_room) * 2 + 256));
+    seg.d_syms = (uint16_t *)g->a->syms.p;
+    KvCarve<7> meta({max_jobs * sizeof(GzJob), max_jobs * sizeof(GzResult), max_jobs * 8, max_jobs * 8, max_jobs * 4, (n_starts + 1) * 8, (n_starts + 1) * 8});
+    KV_HIP(meta.from(g->a->meta));
+    seg.d_jobs = meta.at<GzJob>(0);
+    seg.d_results = meta.at<GzResult>(1);
+    seg.d_off = meta.at<uint64_t>(2);
+    seg.d_base = meta.at<uint64_t>(3);
+    seg.d_n = meta.at<uint32_t>(4);
+    seg.d_starts = meta.at<unsigned long long>(5);
+    seg.d_headers = meta.at<unsigned long long>(6);
     {
-        std::vector<unsigned long long> with_end(starts.begin(), starts.end()), kinds(headers.begin(), headers.end());
+        std::vector<unsigned long long> with_end(seg.s.starts.begin(), seg.s.starts.end()), kinds(seg.s.headers.begin(), seg.s.headers.end());
         with_end.push_back(~0ull);
         kinds.push_back(~0ull);
-        KV_HIP(hipMemcpyAsync(d_starts, with_end.data(), with_end.size() * 8, hipMemcpyHostToDevice, st));
-        KV_HIP(hipMemcpyAsync(d_headers, kinds.data(), kinds.size() * 8, hipMemcpyHostToDevice, st));
-        KV_HIP(hipStreamSynchronize(st));               // (the vectors go out of scope)
+        KV_HIP(hipMemcpyAsync(seg.d_starts, with_end.data(), with_end.size() * 8, hipMemcpyHostToDevice, seg.st));
+        KV_HIP(hipMemcpyAsync(seg.d_headers, kinds.data(), kinds.size() * 8, hipMemcpyHostToDevice, seg.st));
+        KV_HIP(hipStreamSynchronize(seg.st));           // (the vectors go out of scope)
     }
-    uint16_t *d_syms = (uint16_t *)g->a->syms.p;
-    std::vector<GzResult> results(n_first);
-    { const int rc = gz_run_jobs(d_comp, n_bytes, is_file_end, jobs.data(), n_first, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, results.data()); if (rc != KV_OK) return rc; }
-    lap("jobs + decode");
-    // ---- the chain: stretch 0 starts at a known block; a later one counts iff a good stretch ends exactly on its start
-    g->v_off.clear(); g->v_n.clear(); g->v_base.clear(); g->pending_ends.clear();
-    bool crc_lost = false;
-    uint64_t repair_used = 0, text = 0, end_rel = 0;
-    uint32_t repairs = 0, isize_seg = 0;
-    bool ended = false;
-    GzJob cur_job = jobs[0];
-    GzResult cur = results[0];
-    auto accept = [&]() {                              // cur is part of the text
-        g->v_off.push_back(cur_job.out_off); g->v_n.push_back(cur.n_out); g->v_base.push_back(text);
-        if (cur.members >= 1) g->pending_ends.emplace_back(text + cur.trailer_at, cur.trailer_crc);
-        if (cur.members > 1) crc_lost = true;
-        text += cur.n_out;
-        isize_seg += cur.isize_sum;
-    };
-    for (;;) {
-        if (cur.status == GZ_FULL || (cur.status == GZ_LANDED && cur.end_bit < stop_rel && !std::binary_search(starts.begin() + 1, starts.end(), cur.end_bit))) {
-            // out of room, or the stretch ran over a false start and stopped at a block nobody began at: decode again, from
-            // this stretch's start (for room) or from where it stopped, as a stretch of its own
-            GzJob again;
-            if (cur.status == GZ_FULL) {
-                if (cur_job.out_off >= total_cap) repair_used = cur_job.out_off - total_cap;        // the failed attempt's room is free again
-                again = cur_job;
-                again.out_cap = (uint32_t)std::min<uint64_t>((uint64_t)cur_job.out_cap * 32, 0x7ffffff0u);
-            } else {
-                accept();
-                again.start_bit = cur.end_bit;
-                again.header_bit = cur.end_bit;
-                const auto nx = std::upper_bound(starts.begin() + 1, starts.end(), cur.end_bit);
-                again.target_idx = (uint64_t)(nx - starts.begin());
-                const uint64_t next = nx == starts.end() ? n_bytes * 8 : *nx;
-                again.out_cap = room(next - again.start_bit);
-            }
-            again.pad = 0;
-            again.out_off = total_cap + repair_used;
-            repair_used += kv_round_up(again.out_cap, 64);
-            if (++repairs > 200 || repair_used > repair_room || (cur.status == GZ_FULL && cur_job.out_cap >= 0x7ffffff0u)) {
-                kv_set_error("gzip stream at byte %llu: too many stretches needed decoding again", (unsigned long long)(first_byte + cur_job.start_bit / 8));
-                return KV_ERR_TYPE;
-            }
-            { const int rc = gz_run_jobs(d_comp, n_bytes, is_file_end, &again, 1, d_jobs, d_starts, d_headers, stop_rel, exact, d_results, d_ctr, d_syms, &cur); if (rc != KV_OK) return rc; }
-            cur_job = again;
-            continue;
-        }
-        if (cur.status == GZ_BAD || cur.status == GZ_SHORT) {
-            kv_set_error("gzip stream: %s near byte %llu", cur.status == GZ_BAD ? "invalid DEFLATE data" : "data end inside a block",
-                         (unsigned long long)(first_byte + cur.end_bit / 8));
-            return KV_ERR_TYPE;
-        }
-        accept();
-        end_rel = cur.end_bit;
-        if (cur.status == GZ_END) { ended = true; break; }
-        if (cur.end_bit >= stop_rel) break;
-        const size_t k = (size_t)(std::lower_bound(starts.begin() + 1, starts.end(), cur.end_bit) - starts.begin());     // exists: checked above
-        cur_job = jobs[k];
-        cur = results[k];
-    }
-    lap("chain");
-    if (ended && (uint32_t)(g->seen_text + text) != (uint32_t)(g->isize_total + isize_seg)) {
-        // (the CRC-32 is not computed; a stream damaged so that it still decodes to the right length goes through, as it would
-        // through any reader that does not check it)
-        kv_set_error("gzip stream: %llu bytes of text, but the member trailers announce another length (damaged file?)", (unsigned long long)(g->seen_text + text));
+    seg.results.resize(n_first);
+    KV_STEP(gz_run_jobs(seg, seg.plan.jobs.data(), n_first, seg.results.data()));
+    seg.lap("jobs + decode");
+    return KV_OK;
+}
+
+// the chain of results that is the text (gz_walk_chain), a stretch decoded again on the device where the rule asks for it
+static int gz_chain(GzSegment &seg)
+{
+    KvGunzip *g = seg.g;
+    g->chain = gz_walk_chain(seg.s, seg.x.n_bytes, seg.plan, seg.results.data(), [&seg](const GzJob &job, GzResult *out) { return gz_run_jobs(seg, &job, 1, out); });
+    const GzChain &c = g->chain;
+    const unsigned long long at_byte = seg.x.first_byte + c.fail_bit / 8;
+    switch (c.fail) {
+    case GZ_WALK_OK: break;
+    case GZ_WALK_DEVICE: return c.device_rc;
+    case GZ_WALK_REPAIRS: kv_set_error("gzip stream at byte %llu: too many stretches needed decoding again", at_byte); return KV_ERR_TYPE;
+    default:
+        kv_set_error("gzip stream: %s near byte %llu", c.fail == GZ_WALK_BAD ? "invalid DEFLATE data" : "data end inside a block", at_byte);
         return KV_ERR_TYPE;
     }
-    g->pending_isize = isize_seg;
-    if (crc_lost && g->crc_on) {
+    seg.lap("chain");
+    return KV_OK;
+}
+
+// a stream that ends here has the length its member trailers announce; the segment joins the statistics
+static int gz_length_check(GzSegment &seg)
+{
+    KvGunzip *g = seg.g;
+    const GzChain &c = g->chain;
+    if (c.ended && (uint32_t)(g->seen_text + c.text) != (uint32_t)(g->isize_total + c.isize_seg)) {
+        // (the CRC-32 is not computed; a stream damaged so that it still decodes to the right length goes through, as it would
+        // through any reader that does not check it)
+        kv_set_error("gzip stream: %llu bytes of text, but the member trailers announce another length (damaged file?)", (unsigned long long)(g->seen_text + c.text));
+        return KV_ERR_TYPE;
+    }
+    if (c.crc_lost && g->crc_on) {
         // one stretch ran over several member trailers: the per-member CRC-32 chain is broken from here on (only the ISIZE
         // sum is still checked at the end); say so once instead of going quiet
         g->crc_on = false;
         fprintf(stderr, "[kv_gunzip] many small gzip members in one stretch: CRC-32 of the members is not checked beyond this point (sizes are)\n");
     }
-    const size_t nv = g->v_off.size();
+    const size_t n_first = seg.plan.jobs.size();
     g->stat_segments += 1;
     g->stat_jobs += n_first;
-    g->stat_dropped += n_first + repairs - nv;
-    g->stat_repairs += repairs;
-    // ---- tails, resolved by pointer doubling
+    g->stat_dropped += n_first + c.repairs - c.v_off.size();
+    g->stat_repairs += c.repairs;
+    return KV_OK;
+}
+
+// the tails of the accepted stretches, resolved by pointer doubling
+static int gz_resolve_tails(GzSegment &seg)
+{
+    KvGunzip *g = seg.g;
+    hipStream_t st = seg.st;
+    const size_t nv = g->chain.v_off.size();
     if (!g->window_ready) {
         KV_HIP(g->a->window.need(GZ_WIN));
         KV_HIP(hipMemsetAsync(g->a->window.p, 0, GZ_WIN, st));         // nothing valid points in front of the first byte
@@ -1148,22 +1051,23 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
     }
     // two copies of the tails (source and destination of a round) and two lists of marker places, room for an eighth of all
     // places (with more markers than that -- DNA: zlib codes the bases as short matches all over the window, half of a tail is
-    // markers -- going over the whole tails moves fewer bytes than a list would)
+    // markers -- going over the whole tails moves fewer bytes than a list would), 256 bytes to spare
     const uint64_t tail_syms = (uint64_t)(nv + 1) * GZ_WIN;
     const uint64_t list_cap = nv + 1 <= (1u << 17) ? tail_syms / 8 : 0;
-    KV_HIP(g->a->tails.need(tail_syms * 2 * 2 + list_cap * 4 * 2 + 256));
-    uint16_t *t0 = (uint16_t *)g->a->tails.p, *t1 = t0 + tail_syms;
-    uint32_t *l0 = (uint32_t *)(t1 + tail_syms), *l1 = l0 + list_cap;
-    KV_HIP(hipMemcpyAsync(d_off, g->v_off.data(), nv * 8, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_base, g->v_base.data(), nv * 8, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_n, g->v_n.data(), nv * 4, hipMemcpyHostToDevice, st));
-    unsigned long long *d_markers = d_ctr + 1;
+    KvCarve<5> tails({tail_syms * 2, tail_syms * 2, list_cap * 4, list_cap * 4, 256});
+    KV_HIP(tails.from(g->a->tails));
+    uint16_t *t0 = tails.at<uint16_t>(0), *t1 = tails.at<uint16_t>(1);
+    uint32_t *l0 = tails.at<uint32_t>(2), *l1 = tails.at<uint32_t>(3);
+    KV_HIP(hipMemcpyAsync(seg.d_off, g->chain.v_off.data(), nv * 8, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(seg.d_base, g->chain.v_base.data(), nv * 8, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(seg.d_n, g->chain.v_n.data(), nv * 4, hipMemcpyHostToDevice, st));
+    unsigned long long *d_markers = seg.d_ctr + 1;
     unsigned long long markers = 0;
     KV_HIP(hipMemsetAsync(d_markers, 0, 16, st));      // ... and d_no_text behind it
-    g->d_no_text = (unsigned int *)(d_ctr + 2);
+    g->d_no_text = (unsigned int *)(seg.d_ctr + 2);
     {
         KvProfScope prof("k_gz_tails");
-        hipLaunchKernelGGL(k_gz_tails, dim3((unsigned)(nv + 1)), dim3(256), 0, st, (const uint16_t *)d_syms, (const uint64_t *)d_off, (const uint32_t *)d_n,
+        hipLaunchKernelGGL(k_gz_tails, dim3((unsigned)(nv + 1)), dim3(256), 0, st, (const uint16_t *)seg.d_syms, (const uint64_t *)seg.d_off, (const uint32_t *)seg.d_n,
                            (const uint8_t *)g->a->window.p, (uint32_t)std::min<uint64_t>(g->seen_text, GZ_WIN), t0, t1, l0, list_cap, d_markers);
     }
     KV_HIP(hipMemcpyAsync(&markers, d_markers, 8, hipMemcpyDeviceToHost, st));
@@ -1188,26 +1092,52 @@ int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool
         g->stat_rounds += 1;
     }
     KV_HIP(hipGetLastError());
-    lap("tails + scan");
+    seg.lap("tails + scan");
     g->d_tails = t0;                          // plain text now
-    g->d_off = d_off; g->d_base = d_base; g->d_n = d_n;
+    return KV_OK;
+}
+
+// the segment waits for kv_gunzip_emit; one without text is over here
+static int gz_publish(GzSegment &seg, uint64_t *text_bytes, bool *last)
+{
+    KvGunzip *g = seg.g;
+    const GzChain &c = g->chain;
+    g->d_off = seg.d_off; g->d_base = seg.d_base; g->d_n = seg.d_n;
     g->pending = true;
-    g->pending_text = text;
-    g->pending_pos = first_byte * 8 + end_rel;
-    g->pending_done = ended;
-    *text_bytes = text;
-    *last = ended;
-    if (text == 0) {                          // nothing to emit (an empty member at the end of the file)
+    g->pending_pos = seg.x.first_byte * 8 + c.end_rel;
+    *text_bytes = c.text;
+    *last = c.ended;
+    if (c.text == 0) {                        // nothing to emit (an empty member at the end of the file)
         g->pending = false;
-        g->isize_total += isize_seg;
-        for (const auto &end : g->pending_ends) {
+        g->isize_total += c.isize_seg;
+        for (const auto &end : c.ends) {
             if (g->crc_on && g->crc_run != end.second) { kv_set_error("gzip stream: CRC-32 of a member does not match its text (damaged file)"); return KV_ERR_TYPE; }
             g->crc_run = 0;
         }
         g->pos_bit = g->pending_pos;
-        g->done = ended;
+        g->done = c.ended;
     }
     return KV_OK;
+}
+
+// Decode the next segment: about `want_text` bytes of text (at least one chunk).  *text_bytes = what kv_gunzip_emit will
+// deliver.  KV_ERR_TYPE: the stream is not something this decoder handles (the caller falls back to zlib).
+int kv_gunzip_decode(KvGunzip *g, uint64_t want_text, uint64_t *text_bytes, bool *last)
+{
+    *text_bytes = 0;
+    *last = g->done;
+    KV_REQUIRE(!g->pending, KV_ERR_ARG, "kv_gunzip_decode: the previous segment has not been emitted");
+    if (g->done) return KV_OK;
+    GzSegment seg(g, kv_stream());
+    seg.x = gz_segment_extent(g->pos_bit, g->size, want_text, g->ratio, g->chunk_bytes);
+    KV_STEP(gz_upload(seg));
+    KV_STEP(gz_find(seg));
+    KV_STEP(gz_cut(seg));
+    KV_STEP(gz_plan_and_decode(seg));
+    KV_STEP(gz_chain(seg));
+    KV_STEP(gz_length_check(seg));
+    KV_STEP(gz_resolve_tails(seg));
+    return gz_publish(seg, text_bytes, last);
 }
 
 // The text of the decoded segment -> d_text (device, *text_bytes of kv_gunzip_decode), on the calling thread's stream.
@@ -1215,7 +1145,8 @@ int kv_gunzip_emit(KvGunzip *g, uint8_t *d_text)
 {
     KV_REQUIRE(g->pending, KV_ERR_ARG, "kv_gunzip_emit: nothing decoded");
     hipStream_t st = kv_stream();
-    const size_t nv = g->v_off.size();
+    const GzChain &c = g->chain;
+    const size_t nv = c.v_off.size();
     const uint16_t *tails = g->d_tails;
     {
         KvProfScope prof("k_gz_resolve");
@@ -1227,33 +1158,17 @@ int kv_gunzip_emit(KvGunzip *g, uint8_t *d_text)
     KV_HIP(hipMemcpyAsync(&no_text, g->d_no_text, 4, hipMemcpyDeviceToHost, st));
     if (!g->crc_on) KV_HIP(hipStreamSynchronize(st));            // (with the CRC on, kv_crc32_ranges waits for the stream)
     if (g->crc_on) {
-        // the text member by member (ends from the decoders), every member in slices of 16 KB: one thread each, joined here
-        std::vector<uint64_t> r_start;
-        std::vector<uint32_t> r_len;
-        std::vector<uint32_t> r_closes;                // index into pending_ends + 1 for the range that ends a member, else 0
-        uint64_t at = 0;
-        size_t e = 0;
-        while (at < g->pending_text || e < g->pending_ends.size()) {
-            const uint64_t stop = e < g->pending_ends.size() ? g->pending_ends[e].first : g->pending_text;
-            if (at == stop) {                          // a member that ends here without (more) text: an empty range closes it
-                if (e >= g->pending_ends.size()) break;
-                r_start.push_back(at); r_len.push_back(0); r_closes.push_back((uint32_t)++e);
-                continue;
-            }
-            const uint32_t n = (uint32_t)std::min<uint64_t>(stop - at, KV_CRC_SLICE);
-            r_start.push_back(at); r_len.push_back(n);
-            at += n;
-            r_closes.push_back(at == stop && e < g->pending_ends.size() ? (uint32_t)++e : 0u);
-        }
-        const size_t nr = r_start.size();
+        // the text member by member, every member in slices of 16 KB: one thread each, joined here
+        const GzCrcRanges r = gz_crc_ranges(c.text, c.ends, KV_CRC_SLICE);
+        const size_t nr = r.start.size();
         if (nr) {
             std::vector<uint32_t> crcs(nr);
-            { const int rc = kv_crc32_ranges(d_text, r_start.data(), r_len.data(), nr, crcs.data(), g->a->crc); if (rc != KV_OK) return rc; }
+            KV_STEP(kv_crc32_ranges(d_text, r.start.data(), r.len.data(), nr, crcs.data(), g->a->crc));
             uint32_t run = g->crc_run;
-            for (size_t r = 0; r < nr; ++r) {
-                run = kv_crc32_join(run, crcs[r], r_len[r]);
-                if (r_closes[r]) {
-                    if (run != g->pending_ends[r_closes[r] - 1].second) {
+            for (size_t i = 0; i < nr; ++i) {
+                run = kv_crc32_join(run, crcs[i], r.len[i]);
+                if (r.closes[i]) {
+                    if (run != c.ends[r.closes[i] - 1].second) {
                         kv_set_error("gzip stream: the CRC-32 of a member does not match its text (damaged file)");
                         return KV_ERR_TYPE;
                     }
@@ -1268,11 +1183,11 @@ int kv_gunzip_emit(KvGunzip *g, uint8_t *d_text)
         return KV_ERR_TYPE;
     }
     g->seen_comp += (g->pending_pos - g->pos_bit) / 8;
-    g->seen_text += g->pending_text;
-    g->isize_total += g->pending_isize;
+    g->seen_text += c.text;
+    g->isize_total += c.isize_seg;
     if (g->seen_comp > 0) g->ratio = std::max(1.0, (double)g->seen_text / (double)g->seen_comp);
     g->pos_bit = g->pending_pos;
-    g->done = g->pending_done;
+    g->done = c.ended;
     g->pending = false;
     return KV_OK;
 }

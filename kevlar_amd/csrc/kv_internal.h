@@ -8,6 +8,7 @@
 #include <cstring>
 #include <functional>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -295,6 +296,13 @@ void kv_thread_device();
         if (!(cond)) { kv_set_error(__VA_ARGS__); return (code); }                          \
     } while (0)
 
+// a step of a host function that returns a KV_* code: anything but KV_OK is the caller's result as well
+#define KV_STEP(call)                                                                       \
+    do {                                                                                    \
+        const int rc__ = (call);                                                            \
+        if (rc__ != KV_OK) return rc__;                                                     \
+    } while (0)
+
 hipStream_t kv_stream();
 // the key the per-stream scratch tables go by (kv_host.hip): a recycled slot for streams made by kv_stream_create, else the handle
 hipStream_t kv_stream_key(hipStream_t st);
@@ -317,6 +325,25 @@ struct KvProfScope {
     bool on;
     explicit KvProfScope(const char *n);
     ~KvProfScope();
+};
+
+// wall time of the steps of a call on stderr when KV_INGEST_VERBOSE is set: one line per lap, "<prefix><label, `width` wide> <ms> ms",
+// the stream drained first
+struct KvLap {
+    const char *prefix;
+    int width;
+    hipStream_t st;
+    bool on = kv_knob("KV_INGEST_VERBOSE") != nullptr;
+    std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
+    KvLap(const char *prefix_, int width_, hipStream_t st_) : prefix(prefix_), width(width_), st(st_) {}
+    void operator()(const char *what)
+    {
+        if (!on) return;
+        (void)hipStreamSynchronize(st);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s%-*s %8.2f ms\n", prefix, width, what, std::chrono::duration<double, std::milli>(now - mark).count());
+        mark = now;
+    }
 };
 
 // hipMalloc for the library: when the device is out of memory the table buffers kept for future sketches (up to KV_TABLE_CACHE_GB of
@@ -361,6 +388,8 @@ struct KvGunzipArenas {
 };
 // NULL unless the image starts with a gzip member header; arenas: buffers to work in (kept by the caller across files), or NULL
 KvGunzip *kv_gunzip_open(const uint8_t *image, uint64_t size, KvGunzipArenas *arenas);
+// uploads of at least this many bytes go through the FASTQ reader's pinned staging buffers (kv_fastq.hip; KV_STAGE=0: none do)
+#define KV_STAGE_MIN_BYTES (64u << 20)
 void kv_gunzip_set_uploader(KvGunzip *g, std::function<bool(uint8_t *, uint64_t, uint64_t, hipStream_t)> upload);
 void kv_gunzip_close(KvGunzip *g);
 bool kv_gunzip_done(const KvGunzip *g);

@@ -48,6 +48,27 @@ struct KvArena {
     }
 };
 
+// Consecutive pieces of an arena, each rounded up to a multiple of 256 bytes.  The pieces' sizes are listed once: the arena is
+// grown to their sum and at<T>(i) is where piece i begins, so the two cannot disagree.
+template <size_t N>
+struct KvCarve {
+    size_t off[N + 1];
+    unsigned char *base = nullptr;
+    KvCarve(const size_t (&bytes)[N])
+    {
+        off[0] = 0;
+        for (size_t i = 0; i < N; ++i) off[i + 1] = off[i] + (bytes[i] + 255) / 256 * 256;
+    }
+    size_t total() const { return off[N]; }
+    hipError_t from(KvArena &a)
+    {
+        const hipError_t e = a.need(total());
+        base = (unsigned char *)a.p;
+        return e;
+    }
+    template <typename T> T *at(size_t i) const { return (T *)(base + off[i]); }
+};
+
 // One T per stream, so host threads working on different streams do not share buffers; keyed by kv_stream_key (a stream made by
 // kv_stream_create finds the buffers of the stream that had its slot before).  References stay valid: entries are never erased.
 // The mutex guards the map alone; a T that two threads may reach at once brings its own lock.
