@@ -106,6 +106,16 @@ int kv_prof_names(char *buf, size_t cap); /* comma separated list of kernel name
  * planner chose.  Empty when that call launched none; KV_ERR_CAPACITY when the list and its terminating zero do not fit the
  * `cap` bytes of `out`.                                                                                                       */
 int kv_skm_last_instances(char *out, uint64_t cap);
+/* kv_bin_last_instances, kv_bin_last_plan: no reference call site; for tests.  The same report for the partitioned count (DESIGN.md
+ * section 2: k_bin_hash_2bit / k_bin_hash_direct / k_bin_list, k_bin_split, k_bin_apply, k_bin_spill): the instances the last
+ * partitioned count launched on the calling thread's stream -- whether it was fed by reads, by a hash list or by the super-k-mer
+ * count -- in launch order, same form and same KV_ERR_CAPACITY as kv_skm_last_instances; and the numbers of that count's plan,
+ * out[0..12] = T (tables), maxsl (most slices of 2^16 bins of any table), cmax (the bucket budget), F (slices per coarse bucket),
+ * C (coarse buckets in use), ringB (stage B's ring entries), threadsA (stage A's workgroup size), nwgA, nwgB (writers per coarse
+ * bucket / per slice), cap1, cap2 (items per private segment), weighted (0 | 1), fast4 (0 | 1).  n < 13: KV_ERR_CAPACITY.  All
+ * zero when the stream's last plan failed or none was made.                                                                    */
+int kv_bin_last_instances(char *out, uint64_t cap);
+int kv_bin_last_plan(uint64_t *out, uint64_t n);
 
 /* ---- host-side helpers (no table access) --------------------------------------------- */
 /* khmer table sizing: the n largest primes below `target`, odd numbers downwards

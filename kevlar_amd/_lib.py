@@ -56,6 +56,8 @@ SIGNATURES = {
     'kv_prof_get': (i32, [cstr, ctypes.POINTER(ctypes.c_double), u64p]),
     'kv_prof_names': (i32, [ctypes.c_char_p, ctypes.c_size_t]),
     'kv_skm_last_instances': (i32, [ctypes.c_char_p, u64]),
+    'kv_bin_last_instances': (i32, [ctypes.c_char_p, u64]),
+    'kv_bin_last_plan': (i32, [u64p, u64]),
     'kv_primes_below': (i32, [ctypes.c_double, i32, u64p, ctypes.POINTER(i32)]),
     'kv_hash_kmer': (i32, [i32, cstr, i32, u64p]),
     'kv_reverse_hash': (i32, [i32, u64, i32, ctypes.c_char_p]),

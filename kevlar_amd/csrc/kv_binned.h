@@ -83,11 +83,39 @@ __device__ __forceinline__ void spill_items_wave(const BinGeom &g, const uint64_
 }
 #endif
 
+// A kernel instance together with its name: KV_INST-style macros (SKM_INST in kv_skm.hip, BIN_INST in kv_binned.hip) hand
+// kv_inst a function pointer and the text of that very expression, so the name cannot drift from the kernel.  A launch takes its
+// pointer from a function that notes the name in its stream's KvLaunched, and an entry point reports that list (blanks removed,
+// comma separated; a comma between angle brackets belongs to a name).
+template <typename F> struct KvInst { F *fn; const char *name; };
+template <typename F> KvInst<F> kv_inst(F *fn, const char *name) { return KvInst<F>{fn, name}; }
+struct KvLaunched {
+    std::mutex mu;
+    std::string names;
+    void begin() { std::lock_guard<std::mutex> lk(mu); names.clear(); }
+    void note(const char *name)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!names.empty()) names += ',';
+        for (const char *c = name; *c; ++c) if (*c != ' ') names += *c;
+    }
+    // the list and its terminating zero into out[cap]; false when they do not fit
+    bool report(char *out, uint64_t cap)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!out || names.size() + 1 > cap) return false;
+        memcpy(out, names.c_str(), names.size() + 1);
+        return true;
+    }
+};
+
 bool kv_bin_two_bit(const kv_sketch *s, const kv_reads *reads);      // stage A can hash this batch from its 2-bit form (k_bin_hash_2bit)
 
 // Geometry + scratch for a count of at most `n_items_max` k-mers into `s` on the calling thread's stream.
 // work_units / threads: the stage-A front end's units of work and workgroup size (0 threads: pick by geometry);
 // nwgA_fixed != 0 pins the number of stage-A writers (the super-k-mer front end brings its own grid).
+// Every partitioned count begins here (kv_consume_binned's first step, and the super-k-mer count's before its S3): the stream's
+// list of launched k_bin_* instances is emptied, and the plan is kept for kv_bin_last_plan.
 int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, uint64_t work_units, uint32_t lds_front,
                 uint32_t nwgA_fixed, bool weighted, BinPlan *plan);
 // stages B, C, spill + bookkeeping (n_occupied, n_unique estimate); synchronises the stream.

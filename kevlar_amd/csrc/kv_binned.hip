@@ -860,6 +860,21 @@ namespace {
 template <typename K>
 void ensure_dynamic_lds(K kernel, size_t bytes) { kv_ensure_dynamic_lds((const void *)kernel, bytes); }
 
+// Which instance a launch site chose, by name (KvInst, kv_binned.h): BIN_INST(k_bin_apply<ST_BIT, true>) is the pointer and the text
+// of that very expression, bin_launching() hands the pointer to the launch and notes the name in the stream's list.  kv_bin_plan, the
+// first step of every partitioned count, empties the list and keeps its plan; kv_bin_last_instances and kv_bin_last_plan report both
+// (tests/bin_instances_common.py holds every instance and every edge of the planner's arithmetic to a case by them).
+template <typename F> KvInst<F> bin_inst(F *fn, const char *name) { return kv_inst(fn, name); }
+#define BIN_INST(...) bin_inst(__VA_ARGS__, #__VA_ARGS__)
+enum { BIN_PLAN_NUMBERS = 13 };
+struct BinLaunched { KvLaunched list; uint64_t plan[BIN_PLAN_NUMBERS] = {}; };
+KvPerStream<BinLaunched> g_bin_launched;
+template <typename F> F *bin_launching(const KvInst<F> &k, hipStream_t st)
+{
+    g_bin_launched.get(st).list.note(k.name);
+    return k.fn;
+}
+
 }  // namespace
 
 int kv_device_cus()
@@ -917,6 +932,9 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
 {
     hipStream_t st = kv_stream();
     KvArena &scratch = g_scratch.get(st);
+    BinLaunched &launched = g_bin_launched.get(st);
+    launched.list.begin();
+    { std::lock_guard<std::mutex> lk(launched.list.mu); memset(launched.plan, 0, sizeof(launched.plan)); }   // (a plan that fails leaves none)
     BinGeom &g = plan->g;
     memset(&g, 0, sizeof(g));
     plan->weighted = weighted;
@@ -995,6 +1013,13 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
         }
         g.fast4 = ok ? 1 : 0;
     }
+    {
+        // the order kv_bin_last_plan documents (include/kvsketch.h)
+        const uint64_t numbers[BIN_PLAN_NUMBERS] = {(uint64_t)g.T, maxsl, (uint64_t)cmax, (uint64_t)g.F, (uint64_t)g.C, g.ringB, threadsA, g.nwgA, g.nwgB,
+                                                    g.cap1, g.cap2, weighted ? 1u : 0u, (uint64_t)g.fast4};
+        std::lock_guard<std::mutex> lk(launched.list.mu);
+        memcpy(launched.plan, numbers, sizeof(numbers));
+    }
     KV_HIP(hipMemsetAsync(g.ctr, 0, b_ctr, st));   // every segment count is written by its owner: no other memset
     return KV_OK;
 }
@@ -1008,34 +1033,22 @@ int kv_bin_finish(kv_sketch *s, BinPlan &plan, bool added_from_ctr, uint64_t n_a
         KvProfScope prof(plan.weighted ? "k_bin_split_w" : "k_bin_split");
         const size_t isz = plan.weighted ? 4 : 2;
         const size_t lds = (((size_t)g.F * g.ringB * isz + 15) & ~(size_t)15) + (size_t)g.F * 2 * 4 + BIN_B_THREADS;
-        if (plan.weighted) {
-            ensure_dynamic_lds((k_bin_split<true>), lds);
-            hipLaunchKernelGGL((k_bin_split<true>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
-        } else {
-            ensure_dynamic_lds((k_bin_split<false>), lds);
-            hipLaunchKernelGGL((k_bin_split<false>), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
-        }
+        const auto kernel = plan.weighted ? BIN_INST(k_bin_split<true>) : BIN_INST(k_bin_split<false>);
+        ensure_dynamic_lds(kernel.fn, lds);
+        hipLaunchKernelGGL(bin_launching(kernel, st), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
     }
     {
         KvProfScope prof(plan.weighted ? "k_bin_apply_w" : "k_bin_apply");
         const dim3 gridC(plan.maxsl, (unsigned)g.T);
         const SketchDev *d = (const SketchDev *)s->d_desc;
-#define KV_LAUNCH_APPLY(ST_, W_) \
-        hipLaunchKernelGGL((k_bin_apply<ST_, W_>), gridC, dim3(BIN_C_THREADS), 0, st, d, g)
-#define KV_LAUNCH_APPLY_ST(W_)                                               \
-        do {                                                                  \
-            if (s->h.storage == ST_BYTE) KV_LAUNCH_APPLY(ST_BYTE, W_);        \
-            else if (s->h.storage == ST_NIBBLE) KV_LAUNCH_APPLY(ST_NIBBLE, W_); \
-            else KV_LAUNCH_APPLY(ST_BIT, W_);                                 \
-        } while (0)
-        if (plan.weighted) KV_LAUNCH_APPLY_ST(true);
-        else KV_LAUNCH_APPLY_ST(false);
-#undef KV_LAUNCH_APPLY_ST
-#undef KV_LAUNCH_APPLY
+        const int storage = s->h.storage;
+        auto kernel = storage == ST_BYTE ? BIN_INST(k_bin_apply<ST_BYTE, false>) : storage == ST_NIBBLE ? BIN_INST(k_bin_apply<ST_NIBBLE, false>) : BIN_INST(k_bin_apply<ST_BIT, false>);
+        if (plan.weighted) kernel = storage == ST_BYTE ? BIN_INST(k_bin_apply<ST_BYTE, true>) : storage == ST_NIBBLE ? BIN_INST(k_bin_apply<ST_NIBBLE, true>) : BIN_INST(k_bin_apply<ST_BIT, true>);
+        hipLaunchKernelGGL(bin_launching(kernel, st), gridC, dim3(BIN_C_THREADS), 0, st, d, g);
     }
     {
         KvProfScope prof("k_bin_spill");   // usually a handful of items; the kernels check the overflow flag themselves
-        hipLaunchKernelGGL(k_bin_spill, dim3(256), dim3(256), 0, st, (const SketchDev *)s->d_desc, g);
+        hipLaunchKernelGGL(bin_launching(BIN_INST(k_bin_spill), st), dim3(256), dim3(256), 0, st, (const SketchDev *)s->d_desc, g);
     }
     KV_HIP(hipGetLastError());
     unsigned long long ctr[4] = {0, 0, 0, 0};
@@ -1082,47 +1095,48 @@ int kv_consume_binned(kv_sketch *s, const kv_reads *reads, const uint64_t *d_lis
         if (rc != KV_OK) return rc;
     }
     BinGeom &g = plan.g;
-    const int cmax = plan.cmax;
+    const bool small = plan.cmax <= 32;            // 512-thread stage-A workgroups; else 1024 (plan.threadsA)
+    const unsigned threadsA = plan.threadsA;
     const SketchDev *d_mask = mask ? mask->d_desc : nullptr;
     if (two_bit) {
         KvProfScope prof("k_bin_hash_2bit");
         const SketchDev *d = (const SketchDev *)s->d_desc;
         const bool kw2 = s->h.ksize > 32;
         const bool k31 = !kw2 && s->h.ksize == 31 && !kv_knob("KV_SKM_ANY_K");
-        if (cmax <= 32 && k31) hipLaunchKernelGGL((k_bin_hash_2bit<512, 1, 31>), dim3(g.nwgA), dim3(512), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
-        else if (k31) hipLaunchKernelGGL((k_bin_hash_2bit<1024, 1, 31>), dim3(g.nwgA), dim3(1024), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
-        else if (cmax <= 32 && !kw2) hipLaunchKernelGGL((k_bin_hash_2bit<512, 1>), dim3(g.nwgA), dim3(512), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
-        else if (cmax <= 32) hipLaunchKernelGGL((k_bin_hash_2bit<512, 2>), dim3(g.nwgA), dim3(512), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
-        else if (!kw2) hipLaunchKernelGGL((k_bin_hash_2bit<1024, 1>), dim3(g.nwgA), dim3(1024), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
-        else hipLaunchKernelGGL((k_bin_hash_2bit<1024, 2>), dim3(g.nwgA), dim3(1024), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
+        auto kernel = k31 ? BIN_INST(k_bin_hash_2bit<512, 1, 31>) : !kw2 ? BIN_INST(k_bin_hash_2bit<512, 1>) : BIN_INST(k_bin_hash_2bit<512, 2>);
+        if (!small) kernel = k31 ? BIN_INST(k_bin_hash_2bit<1024, 1, 31>) : !kw2 ? BIN_INST(k_bin_hash_2bit<1024, 1>) : BIN_INST(k_bin_hash_2bit<1024, 2>);
+        hipLaunchKernelGGL(bin_launching(kernel, st), dim3(g.nwgA), dim3(threadsA), 0, st, reads_dev(reads), n_units2, d, d_mask, filter, g);
     } else if (reads) {
         KvProfScope prof("k_bin_hash_direct");
-        const unsigned grid = g.nwgA;
         const int k = s->h.ksize;
         const int nw = s->h.hashfam == HF_MURMUR ? (k <= 32 ? 8 : (k <= 64 ? 16 : 0)) : 0;
-#define KV_LAUNCH_BIN_DIRECT(THREADS_, NW_)                                                                       \
-        do {                                                                                                      \
-            ensure_dynamic_lds(k_bin_hash_direct<THREADS_, NW_>, (size_t)g.tile_lds);                             \
-            hipLaunchKernelGGL((k_bin_hash_direct<THREADS_, NW_>), dim3(grid), dim3(THREADS_), g.tile_lds, st,    \
-                               reads_dev(reads), reads->n_tiles, (const SketchDev *)s->d_desc, d_mask, filter, g); \
-        } while (0)
-        if (cmax <= 32) {
-            if (nw == 8) KV_LAUNCH_BIN_DIRECT(512, 8);
-            else if (nw == 16) KV_LAUNCH_BIN_DIRECT(512, 16);
-            else KV_LAUNCH_BIN_DIRECT(512, 0);
-        } else {
-            if (nw == 8) KV_LAUNCH_BIN_DIRECT(1024, 8);
-            else if (nw == 16) KV_LAUNCH_BIN_DIRECT(1024, 16);
-            else KV_LAUNCH_BIN_DIRECT(1024, 0);
-        }
-#undef KV_LAUNCH_BIN_DIRECT
+        auto kernel = nw == 8 ? BIN_INST(k_bin_hash_direct<512, 8>) : nw == 16 ? BIN_INST(k_bin_hash_direct<512, 16>) : BIN_INST(k_bin_hash_direct<512, 0>);
+        if (!small) kernel = nw == 8 ? BIN_INST(k_bin_hash_direct<1024, 8>) : nw == 16 ? BIN_INST(k_bin_hash_direct<1024, 16>) : BIN_INST(k_bin_hash_direct<1024, 0>);
+        ensure_dynamic_lds(kernel.fn, (size_t)g.tile_lds);
+        hipLaunchKernelGGL(bin_launching(kernel, st), dim3(g.nwgA), dim3(threadsA), g.tile_lds, st,
+                           reads_dev(reads), reads->n_tiles, (const SketchDev *)s->d_desc, d_mask, filter, g);
     } else {
         KvProfScope prof(weighted_list ? "k_bin_list_w" : "k_bin_list");
         const SketchDev *d = (const SketchDev *)s->d_desc;
-        if (cmax <= 32 && weighted_list) hipLaunchKernelGGL((k_bin_list<512, true>), dim3(g.nwgA), dim3(512), 0, st, d_list, n_kmers, list_stride, d, g);
-        else if (cmax <= 32) hipLaunchKernelGGL((k_bin_list<512, false>), dim3(g.nwgA), dim3(512), 0, st, d_list, n_kmers, list_stride, d, g);
-        else if (weighted_list) hipLaunchKernelGGL((k_bin_list<1024, true>), dim3(g.nwgA), dim3(1024), 0, st, d_list, n_kmers, list_stride, d, g);
-        else hipLaunchKernelGGL((k_bin_list<1024, false>), dim3(g.nwgA), dim3(1024), 0, st, d_list, n_kmers, list_stride, d, g);
+        auto kernel = weighted_list ? BIN_INST(k_bin_list<512, true>) : BIN_INST(k_bin_list<512, false>);
+        if (!small) kernel = weighted_list ? BIN_INST(k_bin_list<1024, true>) : BIN_INST(k_bin_list<1024, false>);
+        hipLaunchKernelGGL(bin_launching(kernel, st), dim3(g.nwgA), dim3(threadsA), 0, st, d_list, n_kmers, list_stride, d, g);
     }
     return kv_bin_finish(s, plan, reads != nullptr || weighted_list, n_kmers, n_added);
+}
+
+// the k_bin_* instances the last partitioned count launched on the calling thread's stream, and the numbers of its plan (include/kvsketch.h)
+extern "C" int kv_bin_last_instances(char *out, uint64_t cap)
+{
+    KV_REQUIRE(g_bin_launched.get(kv_stream()).list.report(out, cap), KV_ERR_CAPACITY, "kv_bin_last_instances: buffer too small");
+    return KV_OK;
+}
+
+extern "C" int kv_bin_last_plan(uint64_t *out, uint64_t n)
+{
+    KV_REQUIRE(out && n >= BIN_PLAN_NUMBERS, KV_ERR_CAPACITY, "kv_bin_last_plan: room for %d numbers needed", (int)BIN_PLAN_NUMBERS);
+    BinLaunched &l = g_bin_launched.get(kv_stream());
+    std::lock_guard<std::mutex> lk(l.list.mu);
+    memcpy(out, l.plan, sizeof(l.plan));
+    return KV_OK;
 }

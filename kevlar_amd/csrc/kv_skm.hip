@@ -36,24 +36,15 @@ namespace {
 // A kernel instance together with its name.  SKM_INST(k_skm_emit<16>) yields the function pointer and the text of that very
 // expression, so the name cannot drift from the kernel; skm_launching() hands the pointer to the launch and notes the name in the
 // stream's list, which kv_skm_last_instances reports (tests/instances_common.py holds every instance to a case by that report).
-// Every entry point of this file that can launch a super-k-mer kernel empties the list first (skm_launched_begin).
-template <typename F> struct SkmInst { F *fn; const char *name; };
-template <typename F> SkmInst<F> skm_inst(F *fn, const char *name) { return SkmInst<F>{fn, name}; }
+// Every entry point of this file that can launch a super-k-mer kernel empties the list first (skm_launched_begin).  (KvInst and
+// KvLaunched are kv_binned.h's: the partitioned count keeps the same books through BIN_INST.)
+template <typename F> KvInst<F> skm_inst(F *fn, const char *name) { return kv_inst(fn, name); }
 #define SKM_INST(...) skm_inst(__VA_ARGS__, #__VA_ARGS__)
-struct SkmLaunched { std::mutex mu; std::string names; };
-KvPerStream<SkmLaunched> g_skm_launched;
-void skm_launched_begin(hipStream_t st)
+KvPerStream<KvLaunched> g_skm_launched;
+void skm_launched_begin(hipStream_t st) { g_skm_launched.get(st).begin(); }
+template <typename F> F *skm_launching(const KvInst<F> &k, hipStream_t st)
 {
-    SkmLaunched &l = g_skm_launched.get(st);
-    std::lock_guard<std::mutex> lk(l.mu);
-    l.names.clear();
-}
-template <typename F> F *skm_launching(const SkmInst<F> &k, hipStream_t st)
-{
-    SkmLaunched &l = g_skm_launched.get(st);
-    std::lock_guard<std::mutex> lk(l.mu);
-    if (!l.names.empty()) l.names += ',';
-    for (const char *c = k.name; *c; ++c) if (*c != ' ') l.names += *c;
+    g_skm_launched.get(st).note(k.name);
     return k.fn;
 }
 
@@ -299,7 +290,7 @@ void skm_launch_split(const SkmGeom &g, hipStream_t st)
 
 // a loose-list kernel, grid-stride over the list: its instance for one-word or two-word keys
 template <typename... A>
-void skm_launch_loose(SkmInst<void(SkmGeom, A...)> one, SkmInst<void(SkmGeom, A...)> two, hipStream_t st, const SkmGeom &g, typename std::common_type<A>::type... args)
+void skm_launch_loose(KvInst<void(SkmGeom, A...)> one, KvInst<void(SkmGeom, A...)> two, hipStream_t st, const SkmGeom &g, typename std::common_type<A>::type... args)
 {
     hipLaunchKernelGGL(skm_launching(g.kw == 1 ? one : two, st), dim3(SKM_LOOSE_WGS), dim3(256), 0, st, g, args...);
 }
@@ -806,7 +797,7 @@ int kv_skm_novel_mark(const kv_reads *reads, const NovelParams &p, uint64_t n_km
     return KV_OK;
 }
 
-static void skm_launch_route(SkmInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st);
+static void skm_launch_route(KvInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st);
 
 int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, int ndest,
                           int (*alloc)(void *ctx, uint32_t nwg, KvRouteSink *sink), void *ctx)
@@ -842,7 +833,7 @@ int kv_skm_route_distinct(const kv_reads *reads, int ksize, uint64_t n_kmers, in
 }
 
 // the buckets' distinct k-mers through `kernel`, the instance of k_skm_route for the geometry, then the loose list's
-static void skm_launch_route(SkmInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st)
+static void skm_launch_route(KvInst<void(SkmGeom, HashParams, KvRouteSink)> kernel, const SkmGeom &g, int k, const KvRouteSink &rs, hipStream_t st)
 {
     const HashParams hp = make_hash_params(k, HF_MURMUR);
     {
@@ -1215,9 +1206,6 @@ int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32
 // the instances the last call into this file launched on the calling thread's stream (include/kvsketch.h)
 extern "C" int kv_skm_last_instances(char *out, uint64_t cap)
 {
-    SkmLaunched &l = g_skm_launched.get(kv_stream());
-    std::lock_guard<std::mutex> lk(l.mu);
-    KV_REQUIRE(out && l.names.size() + 1 <= cap, KV_ERR_CAPACITY, "kv_skm_last_instances: buffer too small");
-    memcpy(out, l.names.c_str(), l.names.size() + 1);
+    KV_REQUIRE(g_skm_launched.get(kv_stream()).report(out, cap), KV_ERR_CAPACITY, "kv_skm_last_instances: buffer too small");
     return KV_OK;
 }
