@@ -583,6 +583,50 @@ int kv_call_scan(const char *tbases, const uint64_t *toffsets, uint64_t n_target
                  const uint32_t *runs, uint64_t n_runs, const uint64_t *ik_offsets, const uint32_t *ikmers, int ksize, int mindist,
                  uint32_t *records);
 
+/* ---- `kevlar simlike`: the abundances, filters and likelihoods of a batch of calls (kevlar/simlike.py:22-191, 278-300;
+ * kv_simlike.hip) ----------------------------------------------------------------------------------------------------------
+ * The reference asks every sketch for the counts of every window, one window and one sketch at a time, and does the rest in
+ * per-k-mer Python.  Here one launch scores a batch: every call gets one fixed-size record, three doubles and its lists
+ * (DESIGN.md section 12).
+ * samples[0] is the case, samples[1 ..] the controls: 3 to KV_MAX_SAMPLES sketches of any kind and storage; refr is the sketch of
+ * the reference genome.  All of them have k = ksize; a graph (two-bit hash) kind among them needs ksize <= 32.  Call c has the
+ * alternate-allele window alt[alt_offsets[c] .. alt_offsets[c + 1]) and the reference-allele window ref[ref_offsets[c] ..
+ * ref_offsets[c + 1]), both of at least ksize bases.  A k-mer is hashed as kv_hash_kmers hashes it: the bytes as they are, the
+ * complement of anything outside ACGT being N, so every count is what kv_hash_kmers + kv_get_hashes give for the same bytes.
+ * With nk(c) = the k-mers of call c's alt window and base(c) = the sum of nk over the calls in front of it:
+ *   counts[nsamples * base(c) + s * nk(c) ..]  sample s's counts of the alt window's k-mers that the genome does not hold (refr
+ *        count 0), in window order; with dropoutliers, of these the ones less than 20 away from their mean (the exact integer sum
+ *        over the length, in double; an empty list stays empty)
+ *   refr_abunds[base(c) ..]  windows of equal length: refr's counts of the ref window's k-mers at the positions kept by the genome
+ *        test (dropoutliers does not touch them); else nothing (KV_SIMLIKE_NO_REFR), the list counting as one "none" per entry
+ *        of the case's final list.  A count of 0 reads as "none" as well (kevlar/simlike.py:116).
+ *   Every list has room for nk(c) entries; behind its length the room is zero.
+ * records[KV_SIMLIKE_RECORD_WORDS * c ..]:
+ *   [0 .. KV_MAX_SAMPLES - 1]  the final length of every sample's list (0 from nsamples on)
+ *   [KV_MAX_SAMPLES]      the length of the refr-abundance list
+ *   [KV_MAX_SAMPLES + 1]  DROPPED: nk(c) minus the final length of the case's list
+ *   [KV_MAX_SAMPLES + 2]  flags: KV_SIMLIKE_PASSENGER no case count >= casemin; KV_SIMLIKE_CASE_ABUND caseabundlow > 0 and that many
+ *        case counts < casemin on end; KV_SIMLIKE_CTRL_ABUND ctrlabundhigh > 0 and a control with more than that many counts >
+ *        ctrlmax; KV_SIMLIKE_MISMATCH the list of control 1 or of control 2 is not as long as the refr-abundance list (the
+ *        reference's assertion, simlike.py:136-137): the likelihoods of that call are 0 and mean nothing; KV_SIMLIKE_NO_REFR
+ *   [KV_MAX_SAMPLES + 3]  nk(c)
+ * likelihoods[3 * c ..] = LLDN, LLFP, LLIH (simlike.py:135-191) for mean mu, standard deviation sigma and error rate epsilon;
+ *   lists are paired by position up to the shorter one; the binomial coefficient of a non-integer mu * copies is that of the
+ *   floors, through lgamma.
+ * Null arguments, fewer than 3 or more than KV_MAX_SAMPLES samples, a sketch of another k, a graph kind with ksize > 32, a window
+ * shorter than ksize, offsets that decrease, epsilon outside (0, 1), sigma <= 0, mu < 0 or any of the three not finite:
+ * KV_ERR_ARG before anything touches the device, the outputs untouched.                                                       */
+#define KV_SIMLIKE_RECORD_WORDS 20
+#define KV_SIMLIKE_PASSENGER 1u
+#define KV_SIMLIKE_CASE_ABUND 2u
+#define KV_SIMLIKE_CTRL_ABUND 4u
+#define KV_SIMLIKE_MISMATCH 8u
+#define KV_SIMLIKE_NO_REFR 16u
+int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sketch *refr, const char *alt, const uint64_t *alt_offsets,
+                     const char *ref, const uint64_t *ref_offsets, uint64_t n_calls, int ksize, double mu, double sigma, double epsilon,
+                     int casemin, int ctrlmax, int caseabundlow, int ctrlabundhigh, int dropoutliers, uint32_t *records,
+                     double *likelihoods, uint8_t *counts, uint8_t *refr_abunds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ vpp = ctypes.POINTER(ctypes.c_void_p)
 i32 = ctypes.c_int
 u32 = ctypes.c_uint32
 u64 = ctypes.c_uint64
+f64 = ctypes.c_double
 cstr = ctypes.c_char_p
 
 
@@ -151,6 +152,7 @@ SIGNATURES = {
     'kv_align_batch': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, i32, i32, i32, i32, u64, vp, vp, vp, vp, u64, u64p]),
     'kv_align_stats': (i32, [vp]),
     'kv_call_scan': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, i32, i32, vp]),
+    'kv_simlike_score': (i32, [vpp, i32, vp, vp, vp, vp, vp, u64, i32, f64, f64, f64, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
 }
 
 

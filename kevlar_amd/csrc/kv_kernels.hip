@@ -111,52 +111,6 @@ __global__ void k_add_hashes_weighted(const SketchDev *__restrict__ sk, const ui
     }
 }
 
-// MurmurHash3_x64_128 (low word) of k characters produced one at a time by `at(j)`
-template <typename At>
-__device__ uint64_t murmur_chars(At at, int k)
-{
-    uint64_t h1 = 0, h2 = 0;
-    const int nblocks = k / 16, rem = k & 15;
-    for (int b = 0; b < nblocks; ++b) {
-        uint64_t k1 = 0, k2 = 0;
-        for (int j = 7; j >= 0; --j) {
-            k1 = (k1 << 8) | at(16 * b + j);
-            k2 = (k2 << 8) | at(16 * b + 8 + j);
-        }
-        mm_block(h1, h2, k1, k2);
-    }
-    uint64_t k1 = 0, k2 = 0;
-    for (int j = rem - 1; j >= 8; --j) k2 = (k2 << 8) | at(16 * nblocks + j);
-    if (rem > 8) { k2 *= MM_C2; k2 = rotl64(k2, 33); k2 *= MM_C1; h2 ^= k2; }
-    for (int j = (rem > 8 ? 8 : rem) - 1; j >= 0; --j) k1 = (k1 << 8) | at(16 * nblocks + j);
-    if (rem > 0) { k1 *= MM_C1; k1 = rotl64(k1, 31); k1 *= MM_C2; h1 ^= k1; }
-    return mm_final(h1, h2, k);
-}
-
-// khmer's hash of a k-mer given as characters at(j) (forward) and rc(j) (reverse complement)
-template <typename Fwd, typename Rev>
-__device__ __forceinline__ uint64_t kmer_hash_chars(Fwd fwd, Rev rev, int k, int hashfam)
-{
-    if (hashfam == HF_TWOBIT) {
-        uint64_t f = 0, r = 0;
-        for (int j = 0; j < k; ++j) {
-            uint32_t x = (fwd(j) >> 1) & 3u;
-            x ^= ((x ^ (x >> 1)) & 1u) * 3u;
-            f = (f << 2) | x;
-            uint32_t y = (rev(j) >> 1) & 3u;
-            y ^= ((y ^ (y >> 1)) & 1u) * 3u;
-            r = (r << 2) | y;
-        }
-        return f < r ? f : r;
-    }
-    return murmur_chars(fwd, k) ^ murmur_chars(rev, k);
-}
-
-__device__ __forceinline__ uint32_t complement_char(uint32_t c)
-{
-    return c == 'A' ? 'T' : (c == 'C' ? 'G' : (c == 'G' ? 'C' : (c == 'T' ? 'A' : 'N')));
-}
-
 __global__ void k_hash_kmers(const uint8_t *kmers, int k, uint64_t n, int hashfam, uint64_t *out)
 {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
