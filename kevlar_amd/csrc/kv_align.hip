@@ -12,29 +12,14 @@
 // so a step's store is ALN_STRIP contiguous bytes.  The traceback (lane 0 of the same wave, right after the last strip) computes
 // the same address.  It writes its runs back to front into a scratch list, claims room in the caller's pool with one atomic
 // add and the wave copies the runs there in forward order.
-#include <algorithm>
-#include <numeric>
-#include <vector>
-
+// Host half: what a batch must satisfy is in kv_seq_jobs.h, the order of the jobs, the launches and every job's place in a launch's
+// working memory in kv_align_plan.h (both free of HIP and tested without a device); kv_align_batch is the list of the steps.
 #include "kv_device.h"
+#include "kv_align_plan.h"      // AlignJob, ALN_LANES / ALN_COLS / ALN_STRIP, aln_z_bytes, aln_layout
 
 namespace {
 
-#define ALN_LANES 64
-#define ALN_COLS 4
-#define ALN_STRIP (ALN_LANES * ALN_COLS)
-#define ALN_MAX_LEN (1u << 22)          // per sequence: e * len stays far inside int32
-
-static_assert(ALN_STRIP == KV_ALIGN_STRIP, "include/kvsketch.h states the strip width");
 static_assert(ALN_COLS == 4, "a lane's direction bytes of one row are one 32-bit word");
-
-struct AlignJob {
-    uint64_t toff, qoff;        // first byte of the target / the query in the concatenated texts
-    uint64_t zoff;              // bytes, into the launch's z region (a multiple of ALN_STRIP)
-    uint64_t bndoff;            // int2 entries: two boundary buffers of tlen each
-    uint64_t tmpoff;            // uint32 entries: tlen + qlen runs at most
-    uint32_t tlen, qlen, rev, index;
-};
 
 struct AlignParams {
     const AlignJob *jobs;
@@ -224,11 +209,6 @@ __global__ __launch_bounds__(ALN_LANES) void k_align(AlignParams p)
     }
 }
 
-inline uint64_t aln_z_bytes(uint64_t tlen, uint64_t qlen)
-{
-    return (qlen + ALN_STRIP - 1) / ALN_STRIP * (tlen + ALN_LANES - 1) * ALN_STRIP;
-}
-
 unsigned long long g_align_stats[4] = {0, 0, 0, 0};    // of the last kv_align_batch: launches, fill ticks, traceback ticks, cells
 
 }  // namespace
@@ -236,8 +216,8 @@ unsigned long long g_align_stats[4] = {0, 0, 0, 0};    // of the last kv_align_b
 extern "C" int kv_align_z_bytes(uint32_t tlen, uint32_t qlen, uint64_t *bytes)
 {
     KV_REQUIRE(bytes, KV_ERR_ARG, "kv_align_z_bytes: null argument");
-    KV_REQUIRE(tlen >= 1 && qlen >= 1 && tlen <= ALN_MAX_LEN && qlen <= ALN_MAX_LEN, KV_ERR_ARG,
-               "alignment of a %u-base target and a %u-base query: lengths must be 1..%u", tlen, qlen, ALN_MAX_LEN);
+    KV_REQUIRE(tlen >= 1 && qlen >= 1 && tlen <= KV_SEQ_MAX_LEN && qlen <= KV_SEQ_MAX_LEN, KV_ERR_ARG,
+               "alignment of a %u-base target and a %u-base query: lengths must be 1..%u", tlen, qlen, KV_SEQ_MAX_LEN);
     *bytes = aln_z_bytes(tlen, qlen);
     return KV_OK;
 }
@@ -248,28 +228,16 @@ extern "C" int kv_align_plan(const uint32_t *tlens, const uint32_t *qlens, uint6
     KV_REQUIRE(n_launches && (n_jobs == 0 || (tlens && qlens && order && launch_ends)), KV_ERR_ARG, "kv_align_plan: null argument");
     KV_REQUIRE(n_jobs < 0x7FFFFFFFull, KV_ERR_ARG, "kv_align_plan: %llu jobs", (unsigned long long)n_jobs);
     *n_launches = 0;
+    std::vector<KvSeqJob> table(n_jobs);
     for (uint64_t k = 0; k < n_jobs; ++k) {
-        KV_REQUIRE(tlens[k] >= 1 && qlens[k] >= 1, KV_ERR_ARG, "alignment job %llu has an empty sequence", (unsigned long long)k);
-        KV_REQUIRE(tlens[k] <= ALN_MAX_LEN && qlens[k] <= ALN_MAX_LEN, KV_ERR_ARG, "alignment job %llu: sequences of %u and %u bases (at most %u)",
-                   (unsigned long long)k, tlens[k], qlens[k], ALN_MAX_LEN);
-        KV_REQUIRE(aln_z_bytes(tlens[k], qlens[k]) <= z_budget, KV_ERR_CAPACITY,
-                   "alignment job %llu (%u x %u) needs %llu bytes of direction bytes, the budget is %llu", (unsigned long long)k, tlens[k],
-                   qlens[k], (unsigned long long)aln_z_bytes(tlens[k], qlens[k]), (unsigned long long)z_budget);
+        KV_STEP(kv_seq_lengths("alignment", k, tlens[k], qlens[k]));
+        table[k] = KvSeqJob{0, 0, tlens[k], qlens[k], 0, 0, 0};
     }
-    std::iota(order, order + n_jobs, 0u);
-    std::stable_sort(order, order + n_jobs, [&](uint32_t x, uint32_t y) {
-        return (uint64_t)tlens[x] * qlens[x] > (uint64_t)tlens[y] * qlens[y];
-    });
-    uint64_t used = 0;
-    for (uint64_t k = 0; k < n_jobs; ++k) {
-        const uint64_t need = aln_z_bytes(tlens[order[k]], qlens[order[k]]);
-        if (k && used + need > z_budget) {
-            launch_ends[(*n_launches)++] = k;
-            used = 0;
-        }
-        used += need;
-    }
-    if (n_jobs) launch_ends[(*n_launches)++] = n_jobs;
+    AlignLayout lay;
+    KV_STEP(aln_layout(table, z_budget, lay));
+    for (uint64_t k = 0; k < n_jobs; ++k) order[k] = lay.descs[k].index;
+    std::copy(lay.ends.begin(), lay.ends.end(), launch_ends);
+    *n_launches = lay.ends.size();
     return KV_OK;
 }
 
@@ -278,109 +246,61 @@ extern "C" int kv_align_batch(const char *tbases, const uint64_t *toffsets, uint
                               int mismatch, int gapopen, int gapextend, uint64_t z_budget, int32_t *scores, uint64_t *run_offsets,
                               uint32_t *run_counts, uint32_t *runs, uint64_t capacity, uint64_t *n_runs)
 {
-    KV_REQUIRE(toffsets && qoffsets && n_runs && (n_jobs == 0 || (tbases && qbases && jobs && scores && run_offsets && run_counts)) &&
-                   (capacity == 0 || runs),
-               KV_ERR_ARG, "kv_align_batch: null argument");
+    KV_REQUIRE(n_runs && (n_jobs == 0 || (tbases && qbases && scores && run_offsets && run_counts)) && (capacity == 0 || runs), KV_ERR_ARG,
+               "kv_align_batch: null argument");
     if (mismatch < 0) mismatch = -mismatch;
     KV_REQUIRE(match >= 0 && match <= 127 && mismatch <= 127 && gapopen >= 0 && gapopen <= 127 && gapextend >= 0 && gapextend <= 127,
-               KV_ERR_ARG, "alignment scores must lie in 0..127 (match %d, mismatch %d, gap open %d, gap extension %d)", match, mismatch,
-               gapopen, gapextend);
-    for (uint64_t c = 0; c < n_targets; ++c)
-        KV_REQUIRE(toffsets[c] <= toffsets[c + 1], KV_ERR_ARG, "kv_align_batch: target offsets must not decrease");
-    for (uint64_t c = 0; c < n_queries; ++c)
-        KV_REQUIRE(qoffsets[c] <= qoffsets[c + 1], KV_ERR_ARG, "kv_align_batch: query offsets must not decrease");
+               KV_ERR_ARG, "alignment scores must lie in 0..127 (match %d, mismatch %d, gap open %d, gap extension %d)", match, mismatch, gapopen, gapextend);
     *n_runs = 0;
-    std::vector<uint32_t> tlens(n_jobs), qlens(n_jobs), order(n_jobs);
-    std::vector<uint64_t> ends(n_jobs);
-    for (uint64_t k = 0; k < n_jobs; ++k) {
-        const uint32_t t = jobs[3 * k], q = jobs[3 * k + 1];
-        KV_REQUIRE(t < n_targets && q < n_queries && jobs[3 * k + 2] <= 1, KV_ERR_ARG,
-                   "alignment job %llu names target %u of %llu, query %u of %llu, strand flag %u", (unsigned long long)k, t,
-                   (unsigned long long)n_targets, q, (unsigned long long)n_queries, jobs[3 * k + 2]);
-        const uint64_t tl = toffsets[t + 1] - toffsets[t], ql = qoffsets[q + 1] - qoffsets[q];
-        KV_REQUIRE(tl <= ALN_MAX_LEN && ql <= ALN_MAX_LEN, KV_ERR_ARG, "alignment job %llu: sequences of %llu and %llu bases (at most %u)",
-                   (unsigned long long)k, (unsigned long long)tl, (unsigned long long)ql, ALN_MAX_LEN);
-        tlens[k] = (uint32_t)tl;
-        qlens[k] = (uint32_t)ql;
-    }
-    uint64_t n_launches = 0;
-    const int rc = kv_align_plan(tlens.data(), qlens.data(), n_jobs, z_budget, order.data(), ends.data(), &n_launches);
-    if (rc != KV_OK) return rc;
+    std::vector<KvSeqJob> table;
+    KV_STEP(kv_seq_jobs("kv_align_batch", "alignment", toffsets, n_targets, qoffsets, n_queries, jobs, n_jobs, table));
+    AlignLayout lay;
+    KV_STEP(aln_layout(table, z_budget, lay));
     g_align_stats[0] = g_align_stats[1] = g_align_stats[2] = g_align_stats[3] = 0;
     if (n_jobs == 0) return KV_OK;
 
-    // every job's place in its launch's working memory
-    std::vector<AlignJob> descs(n_jobs);
-    uint64_t z_max = 0, bnd_max = 0, tmp_max = 0, cells = 0;
-    for (uint64_t l = 0, k = 0; l < n_launches; ++l) {
-        uint64_t zo = 0, bo = 0, to = 0;
-        for (; k < ends[l]; ++k) {
-            const uint32_t x = order[k];
-            AlignJob &d = descs[k];
-            d.toff = toffsets[jobs[3 * x]];
-            d.qoff = qoffsets[jobs[3 * x + 1]];
-            d.rev = jobs[3 * x + 2];
-            d.tlen = tlens[x];
-            d.qlen = qlens[x];
-            d.index = x;
-            d.zoff = zo;
-            d.bndoff = bo;
-            d.tmpoff = to;
-            zo += aln_z_bytes(d.tlen, d.qlen);
-            bo += 2ull * d.tlen;
-            to += (uint64_t)d.tlen + d.qlen;
-            cells += (uint64_t)d.tlen * d.qlen;
-        }
-        z_max = std::max(z_max, zo);
-        bnd_max = std::max(bnd_max, bo);
-        tmp_max = std::max(tmp_max, to);
-    }
-
+    // carve and upload: one device buffer, its pieces in the order of their sizes
+    enum { AB_Z, AB_BND, AB_TMP, AB_T, AB_Q, AB_JOBS, AB_SCORES, AB_OFF, AB_CNT, AB_POOL, AB_CTR, AB_PIECES };
     hipStream_t st = kv_stream();
     const uint64_t tbytes = toffsets[n_targets], qbytes = qoffsets[n_queries];
-    KvDevBuf d_t, d_q, d_jobs, d_z, d_bnd, d_tmp, d_scores, d_off, d_cnt, d_pool, d_ctr;
-    hipError_t e = d_t.alloc(tbytes);
-    if (e == hipSuccess) e = d_q.alloc(qbytes);
-    if (e == hipSuccess) e = d_jobs.alloc(n_jobs * sizeof(AlignJob));
-    if (e == hipSuccess) e = d_z.alloc(z_max);
-    if (e == hipSuccess) e = d_bnd.alloc(bnd_max * sizeof(int2));
-    if (e == hipSuccess) e = d_tmp.alloc(tmp_max * 4);
-    if (e == hipSuccess) e = d_scores.alloc(n_jobs * 4);
-    if (e == hipSuccess) e = d_off.alloc(n_jobs * 8);
-    if (e == hipSuccess) e = d_cnt.alloc(n_jobs * 4);
-    if (e == hipSuccess) e = d_pool.alloc(capacity * 4);
-    if (e == hipSuccess) e = d_ctr.alloc(64);
+    const size_t sizes[AB_PIECES] = {lay.z_max, lay.bnd_max * sizeof(int2), lay.tmp_max * 4, tbytes, qbytes, n_jobs * sizeof(AlignJob),
+                                     n_jobs * 4, n_jobs * 8, n_jobs * 4, capacity * 4, 64};
+    KvDevBuf buf;
+    KvCarve<AB_PIECES> d(sizes);
+    const hipError_t e = d.from(buf);
     KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "alignment buffers (%llu bytes of direction bytes) allocation failed: %s",
-               (unsigned long long)z_max, hipGetErrorString(e));
-    KV_HIP(hipMemcpyAsync(d_t.p, tbases, tbytes, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_q.p, qbases, qbytes, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_jobs.p, descs.data(), n_jobs * sizeof(AlignJob), hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemsetAsync(d_ctr.p, 0, 64, st));
+               (unsigned long long)lay.z_max, hipGetErrorString(e));
     AlignParams p;
-    p.tbases = d_t.as<uint8_t>(); p.qbases = d_q.as<uint8_t>(); p.z = d_z.as<uint8_t>(); p.bnd = d_bnd.as<int2>(); p.tmp = d_tmp.as<uint32_t>();
-    p.a = match; p.b = -mismatch; p.e = gapextend; p.oe = gapopen + gapextend;
-    p.scores = d_scores.as<int32_t>(); p.run_off = d_off.as<uint64_t>(); p.run_cnt = d_cnt.as<uint32_t>(); p.pool = d_pool.as<uint32_t>();
-    p.cap = capacity; p.ctr = d_ctr.as<unsigned long long>();
-    {
+    p.tbases = d.at<uint8_t>(AB_T); p.qbases = d.at<uint8_t>(AB_Q); p.z = d.at<uint8_t>(AB_Z); p.bnd = d.at<int2>(AB_BND); p.tmp = d.at<uint32_t>(AB_TMP);
+    p.a = match; p.b = -mismatch; p.e = gapextend; p.oe = gapopen + gapextend; p.cap = capacity; p.ctr = d.at<unsigned long long>(AB_CTR);
+    p.scores = d.at<int32_t>(AB_SCORES); p.run_off = d.at<uint64_t>(AB_OFF); p.run_cnt = d.at<uint32_t>(AB_CNT); p.pool = d.at<uint32_t>(AB_POOL);
+    KV_HIP(hipMemcpyAsync(d.at<void>(AB_T), tbases, tbytes, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(d.at<void>(AB_Q), qbases, qbytes, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(d.at<void>(AB_JOBS), lay.descs.data(), n_jobs * sizeof(AlignJob), hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemsetAsync(p.ctr, 0, 64, st));
+    {   // launch per plan chunk; launches share z: one after the other on the stream
         KvProfScope prof("k_align");
-        for (uint64_t l = 0, k = 0; l < n_launches; k = ends[l++]) {     // launches share z: one after the other on the stream
-            p.jobs = d_jobs.as<AlignJob>() + k;
-            hipLaunchKernelGGL(k_align, dim3((unsigned)(ends[l] - k)), dim3(ALN_LANES), 0, st, p);
+        uint64_t k = 0;
+        for (const uint64_t end : lay.ends) {
+            p.jobs = d.at<AlignJob>(AB_JOBS) + k;
+            hipLaunchKernelGGL(k_align, dim3((unsigned)(end - k)), dim3(ALN_LANES), 0, st, p);
+            k = end;
         }
     }
     KV_HIP(hipGetLastError());
+    // fetch; the runs only when the caller's pool held them all
     unsigned long long ctr[3] = {0, 0, 0};
-    KV_HIP(hipMemcpyAsync(ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(scores, d_scores.p, n_jobs * 4, hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(run_offsets, d_off.p, n_jobs * 8, hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(run_counts, d_cnt.p, n_jobs * 4, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(scores, p.scores, n_jobs * 4, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(run_offsets, p.run_off, n_jobs * 8, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(run_counts, p.run_cnt, n_jobs * 4, hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     *n_runs = ctr[0];
     if (ctr[0] && ctr[0] <= capacity) {
-        KV_HIP(hipMemcpyAsync(runs, d_pool.p, ctr[0] * 4, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipMemcpyAsync(runs, p.pool, ctr[0] * 4, hipMemcpyDeviceToHost, st));
         KV_HIP(hipStreamSynchronize(st));
     }
-    g_align_stats[0] = n_launches; g_align_stats[1] = ctr[1]; g_align_stats[2] = ctr[2]; g_align_stats[3] = cells;
+    g_align_stats[0] = lay.ends.size(); g_align_stats[1] = ctr[1]; g_align_stats[2] = ctr[2]; g_align_stats[3] = lay.cells;
     return KV_OK;
 }
 

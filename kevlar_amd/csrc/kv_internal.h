@@ -18,6 +18,7 @@
 #include "kv_fastmod.h"
 #include "kv_reads_layout.h"   // TileDesc, the tile geometry and the layout planner
 #include "kv_mem.h"            // KvDevBuf, KvArena, KvPerStream
+#include "kv_require.h"        // kv_set_error, KV_REQUIRE, KV_STEP
 
 enum { ST_BYTE = 0, ST_NIBBLE = 1, ST_BIT = 2 };
 enum { HF_MURMUR = 0, HF_TWOBIT = 1 };
@@ -269,8 +270,7 @@ int kv_skm_mex_pack(const kv_mex_plan *plan, const uint64_t *d_seg, const uint32
 #define KV_TILE_THREADS 256
 #define KV_MAX_READ_LEN 0x7fffffff   // sequences longer than a tile are cut into segment tiles (reference genomes for masks)
 
-// error plumbing -------------------------------------------------------------------------
-void kv_set_error(const char *fmt, ...);
+// error plumbing (kv_set_error, KV_REQUIRE, KV_STEP: kv_require.h) -----------------------
 // the hipError_t behind the calling thread's last KV_ERR_HIP (KV_HIP notes it): callers that can do without the GPU for a step
 // tell "out of memory" from a device fault by it
 extern thread_local int kv_last_hip_code;
@@ -290,17 +290,6 @@ void kv_thread_device();
                          __LINE__);                                                         \
             return KV_ERR_HIP;                                                              \
         }                                                                                   \
-    } while (0)
-#define KV_REQUIRE(cond, code, ...)                                                         \
-    do {                                                                                    \
-        if (!(cond)) { kv_set_error(__VA_ARGS__); return (code); }                          \
-    } while (0)
-
-// a step of a host function that returns a KV_* code: anything but KV_OK is the caller's result as well
-#define KV_STEP(call)                                                                       \
-    do {                                                                                    \
-        const int rc__ = (call);                                                            \
-        if (rc__ != KV_OK) return rc__;                                                     \
     } while (0)
 
 hipStream_t kv_stream();

@@ -48,8 +48,9 @@ struct KvArena {
     }
 };
 
-// Consecutive pieces of an arena, each rounded up to a multiple of 256 bytes.  The pieces' sizes are listed once: the arena is
-// grown to their sum and at<T>(i) is where piece i begins, so the two cannot disagree.
+// Consecutive pieces of an arena, or of one call's buffer, each rounded up to a multiple of 256 bytes.  The pieces' sizes are
+// listed once: the arena is grown (the buffer allocated) to their sum and at<T>(i) is where piece i begins, so the two cannot
+// disagree.  A piece of 0 bytes begins where the next one does.
 template <size_t N>
 struct KvCarve {
     size_t off[N + 1];
@@ -60,12 +61,8 @@ struct KvCarve {
         for (size_t i = 0; i < N; ++i) off[i + 1] = off[i] + (bytes[i] + 255) / 256 * 256;
     }
     size_t total() const { return off[N]; }
-    hipError_t from(KvArena &a)
-    {
-        const hipError_t e = a.need(total());
-        base = (unsigned char *)a.p;
-        return e;
-    }
+    hipError_t from(KvArena &a) { const hipError_t e = a.need(total()); base = (unsigned char *)a.p; return e; }
+    hipError_t from(KvDevBuf &b) { const hipError_t e = b.alloc(total()); base = (unsigned char *)b.p; return e; }     // freed with b
     template <typename T> T *at(size_t i) const { return (T *)(base + off[i]); }
 };
 

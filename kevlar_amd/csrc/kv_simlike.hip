@@ -14,11 +14,11 @@
 #include <vector>
 
 #include "kv_device.h"
+#include "kv_seq_jobs.h"        // KV_SEQ_MAX_LEN (per window, as kv_call.hip takes its sequences), kv_seq_offsets
 
 namespace {
 
 #define SIM_LANES 64
-#define SIM_MAX_LEN (1u << 22)          // per window, as kv_call.hip takes its sequences
 #define SIM_OUTLIER 20.0                // kevlar/simlike.py:41
 
 static_assert(KV_SIMLIKE_RECORD_WORDS == KV_MAX_SAMPLES + 4, "include/kvsketch.h states the record");
@@ -275,19 +275,17 @@ extern "C" int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sket
         KV_REQUIRE(sk->h.hashfam != HF_TWOBIT || ksize <= 32, KV_ERR_ARG, "graph sketches need k <= 32 (got %d)", ksize);
         p.fam_mask |= 1 << sk->h.hashfam;
     }
+    KV_STEP(kv_seq_offsets("kv_simlike_score", "window", alt_offsets, n_calls));
+    KV_STEP(kv_seq_offsets("kv_simlike_score", "window", ref_offsets, n_calls));
     std::vector<SimCall> descs(n_calls);
     uint64_t total = 0;
     for (uint64_t c = 0; c < n_calls; ++c) {
-        KV_REQUIRE(alt_offsets[c] <= alt_offsets[c + 1] && ref_offsets[c] <= ref_offsets[c + 1], KV_ERR_ARG,
-                   "kv_simlike_score: window offsets must not decrease");
         const uint64_t al = alt_offsets[c + 1] - alt_offsets[c], rl = ref_offsets[c + 1] - ref_offsets[c];
         KV_REQUIRE(al >= (uint64_t)ksize && rl >= (uint64_t)ksize, KV_ERR_ARG, "call %llu: windows of %llu and %llu bases, shorter than k = %d",
                    (unsigned long long)c, (unsigned long long)al, (unsigned long long)rl, ksize);
-        KV_REQUIRE(al <= SIM_MAX_LEN && rl <= SIM_MAX_LEN, KV_ERR_ARG, "call %llu: windows of %llu and %llu bases (at most %u)",
-                   (unsigned long long)c, (unsigned long long)al, (unsigned long long)rl, SIM_MAX_LEN);
-        SimCall &d = descs[c];
-        d.aoff = alt_offsets[c]; d.roff = ref_offsets[c]; d.kbase = total;
-        d.alen = (uint32_t)al; d.rlen = (uint32_t)rl;
+        KV_REQUIRE(al <= KV_SEQ_MAX_LEN && rl <= KV_SEQ_MAX_LEN, KV_ERR_ARG, "call %llu: windows of %llu and %llu bases (at most %u)",
+                   (unsigned long long)c, (unsigned long long)al, (unsigned long long)rl, KV_SEQ_MAX_LEN);
+        descs[c] = SimCall{alt_offsets[c], ref_offsets[c], total, (uint32_t)al, (uint32_t)rl};
         total += al - (uint64_t)ksize + 1;
     }
     if (n_calls == 0) return KV_OK;
@@ -296,25 +294,25 @@ extern "C" int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sket
     p.refr = refr->d_desc;
     p.refr_fam = refr->h.hashfam;
 
+    // allocate and upload: a device buffer per piece, in the order of their sizes.  (One buffer carved into the seven, as kv_align_batch
+    // and kv_call_scan have it, made the whole call of 10 000 windows 6 % slower: seven allocations below a megabyte beat one of four.)
+    enum { SB_ALT, SB_REF, SB_CALLS, SB_REC, SB_LL, SB_COUNTS, SB_REFR, SB_PIECES };
     hipStream_t st = kv_stream();
-    const uint64_t abytes = alt_offsets[n_calls], rbytes = ref_offsets[n_calls];
-    KvDevBuf d_alt, d_ref, d_calls, d_rec, d_ll, d_counts, d_refr;
-    hipError_t e = d_alt.alloc(abytes);
-    if (e == hipSuccess) e = d_ref.alloc(rbytes);
-    if (e == hipSuccess) e = d_calls.alloc(n_calls * sizeof(SimCall));
-    if (e == hipSuccess) e = d_rec.alloc(n_calls * KV_SIMLIKE_RECORD_WORDS * 4);
-    if (e == hipSuccess) e = d_ll.alloc(n_calls * 3 * sizeof(double));
-    if (e == hipSuccess) e = d_counts.alloc(total * (uint64_t)nsamples);
-    if (e == hipSuccess) e = d_refr.alloc(total);
+    const uint64_t abytes = alt_offsets[n_calls], rbytes = ref_offsets[n_calls], cbytes = total * (uint64_t)nsamples;
+    const size_t sizes[SB_PIECES] = {abytes, rbytes, n_calls * sizeof(SimCall), n_calls * KV_SIMLIKE_RECORD_WORDS * 4, n_calls * 3 * sizeof(double),
+                                     cbytes, total};
+    KvDevBuf d[SB_PIECES];
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < SB_PIECES && e == hipSuccess; ++i) e = d[i].alloc(sizes[i]);
     KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "simlike buffers allocation failed: %s", hipGetErrorString(e));
-    KV_HIP(hipMemcpyAsync(d_alt.p, alt, abytes, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_ref.p, ref, rbytes, hipMemcpyHostToDevice, st));
-    KV_HIP(hipMemcpyAsync(d_calls.p, descs.data(), n_calls * sizeof(SimCall), hipMemcpyHostToDevice, st));
+    p.calls = d[SB_CALLS].as<SimCall>(); p.alt = d[SB_ALT].as<uint8_t>(); p.ref = d[SB_REF].as<uint8_t>();
+    p.records = d[SB_REC].as<uint32_t>(); p.ll = d[SB_LL].as<double>(); p.counts = d[SB_COUNTS].as<uint8_t>(); p.refr_out = d[SB_REFR].as<uint8_t>();
+    KV_HIP(hipMemcpyAsync(d[SB_ALT].p, alt, abytes, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(d[SB_REF].p, ref, rbytes, hipMemcpyHostToDevice, st));
+    KV_HIP(hipMemcpyAsync(d[SB_CALLS].p, descs.data(), n_calls * sizeof(SimCall), hipMemcpyHostToDevice, st));
     // (the lists' room behind their final lengths reads as zero)
-    KV_HIP(hipMemsetAsync(d_counts.p, 0, total * (uint64_t)nsamples, st));
-    KV_HIP(hipMemsetAsync(d_refr.p, 0, total, st));
-    p.calls = d_calls.as<SimCall>(); p.alt = d_alt.as<uint8_t>(); p.ref = d_ref.as<uint8_t>();
-    p.records = d_rec.as<uint32_t>(); p.ll = d_ll.as<double>(); p.counts = d_counts.as<uint8_t>(); p.refr_out = d_refr.as<uint8_t>();
+    KV_HIP(hipMemsetAsync(p.counts, 0, cbytes, st));
+    KV_HIP(hipMemsetAsync(p.refr_out, 0, total, st));
     p.mu = mu; p.sigma = sigma; p.epsilon = epsilon;
     p.nsamples = nsamples; p.ksize = ksize;
     p.casemin = casemin; p.ctrlmax = ctrlmax; p.caseabundlow = caseabundlow; p.ctrlabundhigh = ctrlabundhigh;
@@ -324,10 +322,10 @@ extern "C" int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sket
         hipLaunchKernelGGL(k_simlike, dim3((unsigned)n_calls), dim3(SIM_LANES), 0, st, p);
     }
     KV_HIP(hipGetLastError());
-    KV_HIP(hipMemcpyAsync(records, d_rec.p, n_calls * KV_SIMLIKE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(likelihoods, d_ll.p, n_calls * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(counts, d_counts.p, total * (uint64_t)nsamples, hipMemcpyDeviceToHost, st));
-    KV_HIP(hipMemcpyAsync(refr_abunds, d_refr.p, total, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(records, p.records, n_calls * KV_SIMLIKE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(likelihoods, p.ll, n_calls * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(counts, p.counts, cbytes, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(refr_abunds, p.refr_out, total, hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     return KV_OK;
 }

@@ -265,49 +265,9 @@ def test_cigar_shapes():
             jobs.append(shaped(spec, rng, reverse, fold))
             wanted.append((folded, cc.CLASS_CODE[cls]))
 
-    for lead in (None, 'D', 'I'):
-        for trail in (None, 'D', 'I'):
-            head = [(lead, 9)] if lead else []
-            tail = [(trail, 12)] if trail else []
-            add(head + [('M', 120, [60])] + tail, 'snv')
-            for gap in 'DI':
-                unfold = False if not trail else None
-                add(head + [('M', 80, [40]), (gap, 6), ('M', 90, [45])] + tail, 'indel', unfold)
-    add([('M', 70, [30]), ('D', 5), ('M', 60, [20]), ('I', 4), ('M', 80, [40])], None, False)          # two indels
-    add([('M', 70, [30]), ('D', 5), ('M', 60, [20]), ('I', 4), ('M', 80, [40]), ('D', 3)], None)
-    add([('M', 40, [])], 'snv')
-    add([('M', 40, []), ('D', 7)], 'snv')
-    add([('I', 7), ('M', 40, [11])], 'snv')
-    add([('D', 7), ('I', 9)], None)
-    add([('I', 9), ('D', 7)], None)
-    add([('M', 50, []), ('M', 50, [25])], None)                                                        # two runs are two blocks
-    add([('M', 50, []), ('M', 50, [25]), ('M', 50, [])], None)
-    add([('D', 3), ('M', 50, [5]), ('I', 2), ('M', 50, [25]), ('D', 2), ('M', 50, []), ('I', 1)], None)    # seven blocks
-    # tails M (D|I) M: folded into snv / indel / none, and left alone
-    for gap in 'DI':
-        add([('M', 60, [30]), (gap, 3), ('M', 50, [])], 'snv', True, 1)
-        add([('M', 60, [30]), (gap, 3), ('M', 50, [])], 'indel', False)
-        add([('D', 4), ('M', 60, [30]), (gap, 3), ('M', 50, [20])], 'snv', True, 1)
-        add([('M', 90, [40]), ('I', 5), ('M', 60, [30]), (gap, 7), ('M', 40, [])], 'indel', True, 1)
-        add([('M', 90, [40]), ('D', 5), ('M', 60, [30]), (gap, 2), ('M', 140, [100])], 'indel', True, 1)
-        add([('M', 90, [40]), ('D', 5), ('M', 60, [30]), (gap, 2), ('M', 140, [100])], None, False)
-        add([('I', 2), ('M', 90, [40]), ('D', 5), ('M', 60, [30]), ('I', 5), ('M', 60, [30]), (gap, 7), ('M', 40, [])], None, True, 1)
-        # a mismatch in each segment and at the seam (the last block's break of the period at 0 sits right behind it), windows
-        # that straddle the seam, a gap longer than the last block, a last block of one base
-        add([('M', 64, [10, 63]), (gap, 3), ('M', 70, [0, 40])], 'snv', True, 1)
-        add([('M', 45, [44]), (gap, 5), ('M', 45, [])], 'snv', True, 1)
-        add([('M', 45, [40]), (gap, 60), ('M', 45, [3])], 'snv', True, 1)
-        add([('M', 45, [20]), (gap, 2), ('M', 1, [])], 'snv', True, 1)
-        add([('M', 45, [20]), (gap, 2), ('M', 1, [])], 'indel', False)
-        add([('M', 3, []), (gap, 2), ('M', 300, [150])], 'snv', True, 1)
-    # flanks shorter than ksize - 1 on either side, an insertion longer than 2 * ksize, deletions
-    for gap, size in (('D', 4), ('I', 4), ('I', 2 * K + 9), ('D', 200), ('I', 1), ('D', 1)):
-        add([('M', 10, []), (gap, size), ('M', 200, [100])], 'indel', False)
-        add([('M', 200, [100]), (gap, size), ('M', 10, [])], 'indel', False)
-        add([('M', 10, [5]), (gap, size), ('M', 12, [6])], 'indel', False)
-        add([('M', K - 2, []), (gap, size), ('M', K - 1, [])], 'indel', False)
-        add([('M', 120, [30, 60, 90, 100]), (gap, size), ('M', 130, [20, 40, 60, 120])], 'indel', False)
-        add([('I', 6), ('M', 120, [30, 60, 90, 100, 110]), (gap, size), ('M', 130, []), ('D', 9)], 'indel')
+    assert K == 31
+    for spec, cls, fold, folded in cc.CIGAR_SHAPES:
+        add(spec, cls, fold, folded)
     got = agree(jobs)
     assert [record[:2] for record in got] == wanted
     assert max(sum(1 for word in record[5:9] + record[12:16] if word != cc.NO_POSITION) for record in got) == 8
