@@ -273,11 +273,12 @@ void skm_launch_emit(const SkmGeom &g, const kv_reads *reads, hipStream_t st)
 void skm_launch_split(const SkmGeom &g, hipStream_t st)
 {
     KvProfScope prof("k_skm_split");
-    // sorted scatter while a chunk holds ~2 records per fine bucket or more (KV_SKM_S2=plain|sorted overrides)
+    // sorted scatter while a chunk of the instance holds 2 records per fine bucket or more (KV_SKM_S2=plain|sorted overrides)
     const char *s2 = kv_knob("KV_SKM_S2");
-    const bool sorted = s2 ? strcmp(s2, "sorted") == 0 && g.F2 <= SKM_S2_MAXF : g.F2 <= SKM_S2_MAXF;
+    const bool fits = skm_s2_sorted_fits(g.recw, g.F2);
+    const bool sorted = s2 ? strcmp(s2, "sorted") == 0 && fits : fits;
     if (sorted) {
-        const size_t lds = (size_t)SKM_S2_CHUNK * g.recw * 8;
+        const size_t lds = skm_s2_lds(g.recw, g.F2);
         auto kernel = g.recw == 2 ? SKM_INST(k_skm_split_sorted<2>) : SKM_INST(k_skm_split_sorted<3>);
         if (g.recw > 3) kernel = SKM_INST(k_skm_split_sorted<4>);
         kv_ensure_dynamic_lds((const void *)kernel.fn, lds);

@@ -857,21 +857,32 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split(SkmGeom sg)
 // S2 with the scatter sorted in LDS first.  The plain kernel above stores every record where it falls: 64 lanes, 64
 // different cache lines per store instruction, 8-byte pieces of 24-byte records that straddle 32-byte sectors -- PMC:
 // 2.5 GB written for 1.36 GB of records, 68 % of the wave cycles stalled on the memory pipe.  Here a workgroup takes
-// SKM_S2_CHUNK records at a time, ranks them by fine bucket (LDS atomics: rank inside the chunk's share of the bucket),
+// a chunk of records at a time, ranks them by fine bucket (LDS atomics: rank inside the chunk's share of the bucket),
 // lays them out bucket by bucket in LDS and copies that image out with consecutive lanes on consecutive words: a bucket's
-// records of one chunk leave as one contiguous run.  Used while a chunk holds at least ~2 records per bucket.
-#define SKM_S2_CHUNK 2048u
-#define SKM_S2_MAXF 1024u
+// records of one chunk leave as one contiguous run.  Used while a chunk holds at least 2 records per bucket.
+//
+// What the kernel's time follows is the LENGTH of those runs, not how many waves wait side by side: measured at config 2
+// (F2 = 256, 16-byte records, per launch), chunks of 2048 records at two workgroups per CU 0.65 ms, the same chunks at three
+// per CU (80 registers) 0.72, at four 0.66; chunks of 4096 at two per CU 0.57, at one 0.73.  So the chunk is as large as
+// two workgroups' images fit a CU's 160 KB of LDS -- 64 KB for 16- and 32-byte records, 60 KB for 24-byte ones -- with the
+// counters behind the image sized by the fine buckets of THIS launch (12 bytes each; 12 KB at the most), and the kernel is
+// compiled for the four waves per SIMD that two workgroups are (128 registers: eight records a thread in flight twice over).
+#define SKM_S2_MAXF 1024u                                                 // the most fine buckets the sorted kernel takes (two a thread in its scan)
+constexpr uint32_t skm_s2_chunk(int recw) { return recw == 2 ? 4096u : recw == 3 ? 2560u : 2048u; }    // records per chunk
+constexpr bool skm_s2_sorted_fits(int recw, uint32_t F2) { return F2 <= SKM_S2_MAXF && 2u * F2 <= skm_s2_chunk(recw); }
+// dynamic LDS of a launch: the image, then cur / hist / off of F2 counters each
+constexpr size_t skm_s2_lds(int recw, uint32_t F2) { return (size_t)skm_s2_chunk(recw) * recw * 8 + 3 * (size_t)F2 * 4; }
 template <int RECW>
-__global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
+__global__ __launch_bounds__(SKM_THREADS2, 4) void k_skm_split_sorted(SkmGeom sg)
 {
-    __shared__ uint32_t cur[SKM_S2_MAXF];            // records this workgroup has stored per fine bucket
-    __shared__ uint32_t hist[SKM_S2_MAXF];           // the chunk's records per bucket, then slot of sorted position 0 minus that position
-    __shared__ uint32_t off[SKM_S2_MAXF];            // sorted position of the bucket's first record of the chunk
+    constexpr uint32_t CHUNK = skm_s2_chunk(RECW);
     __shared__ uint32_t spre[769];
     __shared__ uint32_t wsum[SKM_THREADS2 / 64];
-    extern __shared__ __attribute__((aligned(16))) uint64_t img[];     // [SKM_S2_CHUNK][RECW]
+    extern __shared__ __attribute__((aligned(16))) uint64_t img[];     // [CHUNK][RECW], then the three counter arrays
     const uint32_t c = blockIdx.y, F2 = sg.F2;
+    uint32_t *const cur = (uint32_t *)(img + CHUNK * RECW);           // records this workgroup has stored per fine bucket
+    uint32_t *const hist = cur + F2;                                  // the chunk's records per bucket, then slot of sorted position 0 minus that position
+    uint32_t *const off = hist + F2;                                  // sorted position of the bucket's first record of the chunk
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t f = threadIdx.x; f < F2; f += SKM_THREADS2) { cur[f] = 0; hist[f] = 0; }
     const uint32_t nmine = (skm_seg1_count(sg) - blockIdx.x + sg.nwg2 - 1) / sg.nwg2;       // <= 768
@@ -884,21 +895,26 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
     }
     __syncthreads();
     const uint32_t total = spre[nmine];
-    constexpr uint32_t PER = SKM_S2_CHUNK / SKM_THREADS2;             // records per thread and chunk
+    constexpr uint32_t PER = CHUNK / SKM_THREADS2;                    // records per thread and chunk
     const uint32_t fper = (F2 + SKM_THREADS2 - 1) / SKM_THREADS2;     // buckets per thread in the scan (1 or 2)
     uint64_t *const out = sg.seg2 + ((uint64_t)c * F2 * sg.nwg2 + blockIdx.x) * sg.cap2 * RECW;      // + fine * nwg2 * cap2 * RECW
     const uint64_t fstride = (uint64_t)sg.nwg2 * sg.cap2 * RECW;
     // the records of the NEXT chunk are requested before this chunk is ranked, laid out and stored: a workgroup's chunk used to begin
-    // with a round trip to HBM that nothing covered (two workgroups per CU, five barriers per chunk)
+    // with a round trip to HBM that nothing covered
     uint64_t nh[PER], n0[PER], n1[PER], n2[PER];
+    // A thread's records come in rising order, SKM_THREADS2 apart, through this chunk and the next: the segment of each is found by
+    // walking spre forward from the segment of the one before (a segment holds a few hundred records: a step or two), not by a
+    // binary search of eight dependent LDS reads in front of every load.  All the walks of a thread together make <= nmine steps.
+    uint32_t si = 0;
     auto request = [&](uint32_t c0) {
-        const uint32_t n = c0 < total ? min(SKM_S2_CHUNK, total - c0) : 0u;
+        const uint32_t n = c0 < total ? min(CHUNK, total - c0) : 0u;
 #pragma unroll
         for (uint32_t r = 0; r < PER; ++r) {
             const uint32_t i = r * SKM_THREADS2 + threadIdx.x;
             nh[r] = 0; n0[r] = 0; n1[r] = 0; n2[r] = 0;
             if (i < n) {
-                const uint32_t gi = c0 + i, si = skm_search(spre, nmine, gi);
+                const uint32_t gi = c0 + i;
+                while (spre[si + 1] <= gi) ++si;                      // (gi < total = spre[nmine]: the walk ends at nmine - 1 at the latest)
                 const uint32_t seg = blockIdx.x + si * sg.nwg2;
                 const uint64_t *rec = sg.seg1 + (skm_seg1_first(sg, skm_seg1_slot(sg, c, seg)) + (gi - spre[si])) * (uint64_t)RECW;
                 if (RECW == 2) {                                      // compact: the word that says the bucket is the second one
@@ -913,13 +929,13 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
         }
     };
     request(0);
-    for (uint32_t c0 = 0; c0 < total; c0 += SKM_S2_CHUNK) {
-        const uint32_t n = min(SKM_S2_CHUNK, total - c0);
+    for (uint32_t c0 = 0; c0 < total; c0 += CHUNK) {
+        const uint32_t n = min(CHUNK, total - c0);
         uint64_t hdr[PER], w0[PER], w1[PER], w2[PER];
         uint32_t rank[PER];
 #pragma unroll
         for (uint32_t r = 0; r < PER; ++r) { hdr[r] = nh[r]; w0[r] = n0[r]; w1[r] = n1[r]; w2[r] = n2[r]; rank[r] = 0; }
-        request(c0 + SKM_S2_CHUNK);
+        request(c0 + CHUNK);
 #pragma unroll
         for (uint32_t r = 0; r < PER; ++r)
             if (r * SKM_THREADS2 + threadIdx.x < n) rank[r] = atomicAdd(&hist[RECW == 2 ? skm_c_fine(hdr[r]) : skm_hdr_fine(hdr[r])], 1u);
@@ -957,7 +973,7 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
 #pragma unroll
         for (uint32_t r = 0; r < PER; ++r) {
             if (r * SKM_THREADS2 + threadIdx.x < n) {
-                uint64_t *dst = img + (uint64_t)(off[RECW == 2 ? skm_c_fine(hdr[r]) : skm_hdr_fine(hdr[r])] + rank[r]) * RECW;
+                uint64_t *dst = img + (off[RECW == 2 ? skm_c_fine(hdr[r]) : skm_hdr_fine(hdr[r])] + rank[r]) * (uint32_t)RECW;
                 if (RECW == 2) { dst[0] = w0[r]; dst[1] = hdr[r]; }
                 else { dst[0] = hdr[r]; dst[1] = w0[r]; dst[2] = w1[r]; }
                 if (RECW == 4) dst[3] = w2[r];
@@ -966,16 +982,16 @@ __global__ __launch_bounds__(SKM_THREADS2) void k_skm_split_sorted(SkmGeom sg)
         __syncthreads();
         for (uint32_t wd = threadIdx.x; wd < n * RECW; wd += SKM_THREADS2) {
             const uint32_t q = wd / RECW, part = wd - q * RECW;
-            const uint64_t h0 = img[(uint64_t)q * RECW + (RECW == 2 ? 1 : 0)];
+            const uint64_t h0 = img[q * RECW + (RECW == 2 ? 1 : 0)];
             const uint32_t f = RECW == 2 ? skm_c_fine(h0) : skm_hdr_fine(h0);
             const uint32_t slot = q + hist[f];
-            if (slot < sg.cap2) out[(uint64_t)f * fstride + (uint64_t)slot * RECW + part] = img[wd];
+            if (slot < sg.cap2) out[(uint64_t)f * fstride + (slot * (uint32_t)RECW + part)] = img[wd];
             else if (part == 0) {
                 if (RECW == 2) {                                      // a compact record leaves in the loose list's (classic) form, position unknown
-                    uint64_t bw[3] = {img[(uint64_t)q * RECW], skm_c_b1(h0), 0ull};
+                    uint64_t bw[3] = {img[q * RECW], skm_c_b1(h0), 0ull};
                     skm_loose_push(sg, skm_header(0ull, skm_c_n(h0), f, skm_c_rev(h0)), bw);
                 } else {
-                    uint64_t bw[3] = {img[(uint64_t)q * RECW + 1], img[(uint64_t)q * RECW + 2], RECW == 4 ? img[(uint64_t)q * RECW + 3] : 0ull};
+                    uint64_t bw[3] = {img[q * RECW + 1], img[q * RECW + 2], RECW == 4 ? img[q * RECW + 3] : 0ull};
                     skm_loose_push(sg, h0, bw);
                 }
             }
