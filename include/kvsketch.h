@@ -113,7 +113,8 @@ int kv_skm_last_instances(char *out, uint64_t cap);
  * out[0..12] = T (tables), maxsl (most slices of 2^16 bins of any table), cmax (the bucket budget), F (slices per coarse bucket),
  * C (coarse buckets in use), ringB (stage B's ring entries), threadsA (stage A's workgroup size), nwgA, nwgB (writers per coarse
  * bucket / per slice), cap1, cap2 (items per private segment), weighted (0 | 1), fast4 (0 | 1).  n < 13: KV_ERR_CAPACITY.  All
- * zero when the stream's last plan failed or none was made.                                                                    */
+ * zero when the stream's last plan failed or none was made.  The rules behind the numbers are bin_shape and bin_sizes of
+ * kevlar_amd/csrc/kv_bin_plan.h, which compiles without HIP (tests/test_bin_plan.py).                                         */
 int kv_bin_last_instances(char *out, uint64_t cap);
 int kv_bin_last_plan(uint64_t *out, uint64_t n);
 

@@ -2,19 +2,7 @@
 // super-k-mer front end (kv_skm.hip), which feeds the same coarse buckets with (bin, count) items.
 #pragma once
 #include "kv_internal.h"
-
-#define BIN_C 64            // most coarse buckets per table
-#define BIN_MAX_T 4         // tables handled by the partitioned path
-#define BIN_MAX_F 512       // slices per coarse bucket (9 bits of a coarse item)
-
-// A coarse item (stage A -> stage B) is one u32.  Unweighted (one item per k-mer):
-//   bits  0..15  offset of the bin inside its 65536-bin slice        bits 16..24  slice inside the coarse bucket (< F <= 512)
-// Weighted (one item per distinct k-mer of a batch; saturating adds commute, so a k-mer seen c times is one item of
-// weight c instead of c items): the same layout plus bits 25..31 = weight - 1.
-// A fine item (stage B -> stage C) is the u16 offset, or for weighted items offset | weight << 16.
-#define BIN_W_SHIFT 25
-#define BIN_W_MAX 128u
-#define BIN_SLICE_BITS 16
+#include "kv_bin_plan.h"   // the constants, the item layout and the planner's arithmetic
 
 struct BinGeom {
     int T, F, C;                     // tables, slices per coarse bucket, coarse buckets in use (<= BIN_C)

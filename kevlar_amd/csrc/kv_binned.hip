@@ -35,13 +35,7 @@
 
 namespace {
 
-#define BIN_RING_MIN 64
-#define BIN_RING_MAX 4096   // a round appends at most 4096 items to one stream
-#define BIN_B_THREADS 512   // 8 waves: one lane per slice stream for F <= 512
-#define BIN_B_ITEMS 8       // items per thread per round in stage B
-#define BIN_B_BUDGET 16384  // LDS ring entries per stage-B workgroup
-#define BIN_C_THREADS 1024
-#define BIN_MAX_SEG 512      // stage-B writers per slice (nwgB)
+#define BIN_B_ITEMS 8       // items per thread per round in stage B (the planner's constants: kv_bin_plan.h)
 
 // ---- LDS write-combining rings ------------------------------------------------------------
 // ns streams, each a ring of R items (R a power of two) plus an append counter and a flushed
@@ -193,10 +187,62 @@ __device__ __forceinline__ void rings_store_counts(uint32_t ns, uint32_t written
 }
 
 // ---- stage A -----------------------------------------------------------------------------
-// Every workgroup owns a private segment of every coarse bucket; the segment's write cursor lives in
-// LDS and each item is stored straight to HBM -- no barrier, no flush phase between hashing a k-mer
-// and storing its T items.  The write frontier (workgroups x
-// buckets x one 128-B line) sits in L2, which merges the partial lines before they reach HBM.
+// Every workgroup owns a private segment of every coarse bucket; the segment's write cursor lives in LDS and each item is stored
+// straight to HBM -- no barrier, no flush phase between hashing a k-mer and storing its T items.  The write frontier (workgroups x
+// buckets x one 128-B line) sits in L2, which merges the partial lines before they reach HBM.  The three kernels share four steps:
+template <int THREADS> __device__ __forceinline__ void bin_clear_cursors(const BinGeom &g, uint32_t *cur)
+{
+    for (uint32_t s = threadIdx.x; s < (uint32_t)(g.T * g.C); s += THREADS) cur[s] = 0;
+}
+
+// the workgroup's next unit of work off the device-wide counter (its callers stop at g.quotaA tickets or past the last unit)
+template <typename U> __device__ __forceinline__ U bin_ticket(const BinGeom &g, U *next)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) *next = (U)atomicAdd(&g.ctr[4], 1ull);
+    __syncthreads();
+    return *next;
+}
+
+// One hash into its T coarse buckets, in three passes so that the T LDS atomics are in flight together: all T items, all T
+// cursor bumps, then the T stores (or the spill list for a segment that is full).  W: the item carries wgt - 1 (kv_bin_plan.h).
+template <bool W> __device__ __forceinline__ void bin_route(const BinGeom &g, const SketchDev *sk, uint32_t *cur, uint64_t h, uint32_t wgt)
+{
+    constexpr uint32_t SB = BIN_SLICE_BITS;
+    uint32_t sidx[BIN_MAX_T], item[BIN_MAX_T], pos[BIN_MAX_T];
+    uint64_t bins[BIN_MAX_T];
+#pragma unroll
+    for (int t = 0; t < BIN_MAX_T; ++t) {
+        if (t >= g.T) break;
+        const uint64_t bin = fastmod(h, sk->size[t], sk->magic[t]);
+        const uint32_t slice = (uint32_t)(bin >> SB);
+        const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
+        bins[t] = bin;
+        item[t] = ((slice - c * (uint32_t)g.F) << SB) | ((uint32_t)bin & ((1u << SB) - 1u)) | (W ? (wgt - 1u) << BIN_W_SHIFT : 0u);
+        sidx[t] = (uint32_t)t * (uint32_t)g.C + c;
+    }
+#pragma unroll
+    for (int t = 0; t < BIN_MAX_T; ++t)
+        if (t < g.T) pos[t] = atomicAdd(&cur[sidx[t]], 1u);
+#pragma unroll
+    for (int t = 0; t < BIN_MAX_T; ++t) {
+        if (t >= g.T) break;
+        if (pos[t] < g.cap1) g.gbuf1[((uint64_t)sidx[t] * g.nwgA + blockIdx.x) * g.cap1 + pos[t]] = item[t];
+        else spill_item(g, t, bins[t], wgt);
+    }
+}
+
+// the segments' item counts; ADDED: and the workgroup's share of the k-mers added, one atomic a wave
+template <int THREADS, bool ADDED = true> __device__ __forceinline__ void bin_close(const BinGeom &g, const uint32_t *cur, uint64_t n_added)
+{
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < (uint32_t)(g.T * g.C); s += THREADS)
+        g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
+    if (!ADDED) return;
+    n_added = wave_sum_u64(n_added);
+    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
+}
+
 template <int THREADS, int NW>
 __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_direct(
     ReadsDev rd, uint32_t n_tiles, const SketchDev *__restrict__ sk, const SketchDev *__restrict__ mask,
@@ -207,14 +253,10 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_
     __shared__ uint32_t next_tile;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (threadIdx.x == 0) sh.ascii = (uint32_t *)smem;
-    const uint32_t ns = (uint32_t)(g.T * g.C);
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS) cur[s] = 0;
+    bin_clear_cursors<THREADS>(g, cur);
     uint64_t n_added = 0;
     for (uint32_t taken = 0; taken < g.quotaA; ++taken) {
-        __syncthreads();
-        if (threadIdx.x == 0) next_tile = (uint32_t)atomicAdd(&g.ctr[4], 1ull);
-        __syncthreads();
-        const uint32_t tile = next_tile;
+        const uint32_t tile = bin_ticket(g, &next_tile);
         if (tile >= n_tiles) break;
         uint32_t read0;
         const uint32_t nr = stage_tile(sh, rd, tile, f.hp.k, 0, 0, read0);
@@ -243,41 +285,16 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_
             }
             if (!consume_filter_pass(f, mask, h)) continue;
             n_added += 1;
-            uint32_t sidx[BIN_MAX_T], item[BIN_MAX_T], pos[BIN_MAX_T];
-            uint64_t bins[BIN_MAX_T];
-#pragma unroll
-            for (int t = 0; t < BIN_MAX_T; ++t) {
-                if (t >= g.T) break;
-                const uint64_t bin = fastmod(h, sk->size[t], sk->magic[t]);
-                const uint32_t slice = (uint32_t)(bin >> 16);
-                const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-                bins[t] = bin;
-                item[t] = ((slice - c * (uint32_t)g.F) << 16) | (uint32_t)(bin & 0xffffu);
-                sidx[t] = (uint32_t)t * (uint32_t)g.C + c;
-            }
-#pragma unroll
-            for (int t = 0; t < BIN_MAX_T; ++t)
-                if (t < g.T) pos[t] = atomicAdd(&cur[sidx[t]], 1u);
-#pragma unroll
-            for (int t = 0; t < BIN_MAX_T; ++t) {
-                if (t >= g.T) break;
-                if (pos[t] < g.cap1) g.gbuf1[((uint64_t)sidx[t] * g.nwgA + blockIdx.x) * g.cap1 + pos[t]] = item[t];
-                else spill_item(g, t, bins[t]);
-            }
+            bin_route<false>(g, sk, cur, h, 1u);
         }
     }
-    __syncthreads();
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS)
-        g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
-    n_added = wave_sum_u64(n_added);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
+    bin_close<THREADS>(g, cur, n_added);
 }
 
 // Stage A for batches of equal-length reads, hashed from the 2-bit form (kv_kmer2bit_device.h): a thread takes BIN2_CH consecutive
 // k-mers of one read; what passes the band / mask filter is collected per wave and routed 64 at a time -- T reductions, T items through
 // the LDS cursors, direct stores, exactly as k_bin_hash_direct stores them.  A ticket is BIN2_TILES tiles' worth of reads.
 #define BIN2_CH 10
-#define BIN2_TILES 8u
 // FK = 31: the instance for kevlar's default k, with the murmurs' first multiplications from the product tables (skm_key_hash_pl)
 template <int THREADS, int KW, int FK = 0>
 __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_2bit(
@@ -287,8 +304,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_
     __shared__ uint32_t cur[BIN_MAX_T * BIN_C];
     __shared__ uint32_t next_unit;
     __shared__ unsigned long long queue[(THREADS / 64) * 128];
-    const uint32_t ns = (uint32_t)(g.T * g.C);
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS) cur[s] = 0;
+    bin_clear_cursors<THREADS>(g, cur);
     if (threadIdx.x < 256) {
         if (FK) { ((uint64_t *)lut)[threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C1); ((uint64_t *)lut)[256 + threadIdx.x] = skm_ascii4_times(threadIdx.x, MM_C2); }
         else lut[threadIdx.x] = skm_ascii4(threadIdx.x);
@@ -304,33 +320,10 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_
     auto route = [&](bool have, uint64_t h) {
         if (!have) return;
         n_added += 1;
-        uint32_t sidx[BIN_MAX_T], item[BIN_MAX_T], pos[BIN_MAX_T];
-        uint64_t bins[BIN_MAX_T];
-#pragma unroll
-        for (int t = 0; t < BIN_MAX_T; ++t) {
-            if (t >= g.T) break;
-            const uint64_t bin = fastmod(h, sk->size[t], sk->magic[t]);
-            const uint32_t slice = (uint32_t)(bin >> 16);
-            const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-            bins[t] = bin;
-            item[t] = ((slice - c * (uint32_t)g.F) << 16) | (uint32_t)(bin & 0xffffu);
-            sidx[t] = (uint32_t)t * (uint32_t)g.C + c;
-        }
-#pragma unroll
-        for (int t = 0; t < BIN_MAX_T; ++t)
-            if (t < g.T) pos[t] = atomicAdd(&cur[sidx[t]], 1u);
-#pragma unroll
-        for (int t = 0; t < BIN_MAX_T; ++t) {
-            if (t >= g.T) break;
-            if (pos[t] < g.cap1) g.gbuf1[((uint64_t)sidx[t] * g.nwgA + blockIdx.x) * g.cap1 + pos[t]] = item[t];
-            else spill_item(g, t, bins[t]);
-        }
+        bin_route<false>(g, sk, cur, h, 1u);
     };
     for (uint32_t taken = 0; taken < g.quotaA; ++taken) {
-        __syncthreads();
-        if (threadIdx.x == 0) next_unit = (uint32_t)atomicAdd(&g.ctr[4], 1ull);
-        __syncthreads();
-        const uint32_t unit = next_unit;
+        const uint32_t unit = bin_ticket(g, &next_unit);
         if (unit >= n_units) break;
         const uint64_t r0 = (uint64_t)unit * reads_per_unit;
         const uint32_t nr = (uint32_t)min(reads_per_unit, rd.n_reads - r0), n_items = nr * cpr;
@@ -346,16 +339,11 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_hash_
         }
     }
     wave_queue_flush(wq, route);
-    __syncthreads();
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS)
-        g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
-    n_added = wave_sum_u64(n_added);
-    if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
+    bin_close<THREADS>(g, cur, n_added);
 }
 
 // stage A over a list of hashes already in HBM (read-sharded multi-GPU count: the hashes of this
 // rank's band arrive from the other ranks, kv_shard.hip).  Element i sits at list[i * stride].
-#define BIN_LIST_ROUNDS 16
 // W: the list holds (hash, count) pairs -- element i at list[i * stride], its count at list[i * stride + 1] -- and the
 // items carry min(count, 255) as their weight (what a band owner receives from ranks that deduplicated their shards)
 template <int THREADS, bool W>
@@ -365,15 +353,11 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_list(
     // same direct stores through LDS cursors as k_bin_hash_direct; the hashes just come from HBM
     __shared__ uint32_t cur[BIN_MAX_T * BIN_C];
     __shared__ uint64_t next_chunk;
-    const uint32_t ns = (uint32_t)(g.T * g.C);
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS) cur[s] = 0;
+    bin_clear_cursors<THREADS>(g, cur);
     const uint64_t chunk = (uint64_t)THREADS * BIN_LIST_ROUNDS;
     uint64_t n_added = 0;
     for (uint32_t taken = 0; taken < g.quotaA; ++taken) {
-        __syncthreads();
-        if (threadIdx.x == 0) next_chunk = (uint64_t)atomicAdd(&g.ctr[4], 1ull);
-        __syncthreads();
-        const uint64_t i0 = next_chunk * chunk;
+        const uint64_t i0 = bin_ticket(g, &next_chunk) * chunk;
         if (i0 >= n) break;
         uint64_t idx = i0 + threadIdx.x;
         uint64_t h_next = idx < n ? list[idx * stride] : 0, c_next = (W && idx < n) ? list[idx * stride + 1] : 1;
@@ -391,37 +375,11 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 6 : 4)) void k_bin_list(
             while (left) {
                 const uint32_t wgt = W ? min(left, BIN_W_MAX) : 1u;
                 left -= wgt;
-                uint32_t sidx[BIN_MAX_T], item[BIN_MAX_T], pos[BIN_MAX_T];
-                uint64_t bins[BIN_MAX_T];
-#pragma unroll
-                for (int t = 0; t < BIN_MAX_T; ++t) {
-                    if (t >= g.T) break;
-                    const uint64_t bin = fastmod(h, sk->size[t], sk->magic[t]);
-                    const uint32_t slice = (uint32_t)(bin >> g.sbits);
-                    const uint32_t c = g.F == 1 ? slice : __umulhi(slice, g.recipF);
-                    bins[t] = bin;
-                    item[t] = ((slice - c * (uint32_t)g.F) << g.sbits) | ((uint32_t)bin & ((1u << g.sbits) - 1u)) | (W ? (wgt - 1u) << BIN_W_SHIFT : 0u);
-                    sidx[t] = (uint32_t)t * (uint32_t)g.C + c;
-                }
-#pragma unroll
-                for (int t = 0; t < BIN_MAX_T; ++t)
-                    if (t < g.T) pos[t] = atomicAdd(&cur[sidx[t]], 1u);
-#pragma unroll
-                for (int t = 0; t < BIN_MAX_T; ++t) {
-                    if (t >= g.T) break;
-                    if (pos[t] < g.cap1) g.gbuf1[((uint64_t)sidx[t] * g.nwgA + blockIdx.x) * g.cap1 + pos[t]] = item[t];
-                    else spill_item(g, t, bins[t], wgt);
-                }
+                bin_route<W>(g, sk, cur, h, wgt);
             }
         }
     }
-    __syncthreads();
-    for (uint32_t s = threadIdx.x; s < ns; s += THREADS)
-        g.gcnt1[(uint64_t)s * g.nwgA + blockIdx.x] = (uint32_t)min((uint64_t)cur[s], g.cap1);
-    if (W) {
-        n_added = wave_sum_u64(n_added);
-        if ((threadIdx.x & 63) == 0 && n_added) atomicAdd(&g.ctr[2], (unsigned long long)n_added);
-    }
+    bin_close<THREADS, W>(g, cur, n_added);     // (an unweighted list's length is its caller's n_added)
 }
 
 // ---- stage B -----------------------------------------------------------------------------
@@ -438,9 +396,9 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
     rs.R = g.ringB;
     rs.skew = 8;
     rs.ring = (Out *)smem;
-    rs.cnt = (uint32_t *)(smem + (((size_t)F * rs.R * sizeof(Out) + 15) & ~(size_t)15));
-    rs.base = rs.cnt + F;
-    uint8_t *ready = (uint8_t *)(rs.base + F);      // BIN_B_THREADS bytes: every wave's list of lanes with a burst to flush
+    const BinSplitLds lay = bin_split_lds(F, rs.R, sizeof(Out));
+    rs.cnt = (uint32_t *)(smem + lay.cnt); rs.base = (uint32_t *)(smem + lay.base);
+    uint8_t *ready = smem + lay.ready;              // BIN_B_THREADS bytes: every wave's list of lanes with a burst to flush
     for (uint32_t i = threadIdx.x; i < F; i += BIN_B_THREADS) { rs.cnt[i] = 0; rs.base[i] = 0; }
     __syncthreads();
     uint32_t written = 0;
@@ -523,28 +481,12 @@ __global__ __launch_bounds__(BIN_B_THREADS) void k_bin_split(BinGeom g)
 }
 
 // ---- stage C -----------------------------------------------------------------------------
-__device__ __forceinline__ bool lds_inc(uint32_t *lds, uint32_t off, int storage)
+// Where bin `off` keeps its counter: the index of its 32-bit word and the counter's shift inside it.  ST_BYTE: a byte per bin;
+// ST_NIBBLE: two bins per byte, the even bin in the high nibble.
+template <int STORAGE, typename Off> __device__ __forceinline__ void counter_slot(Off off, Off &word, uint32_t &shift)
 {
-    if (storage == ST_BIT) {
-        const uint32_t bit = 1u << (off & 31);
-        return (atomicOr(&lds[off >> 5], bit) & bit) == 0;
-    }
-    uint32_t *w;
-    uint32_t shift, maxv;
-    if (storage == ST_BYTE) {
-        w = &lds[off >> 2]; shift = (off & 3) * 8u; maxv = 255u;
-    } else {
-        const uint32_t byte = off >> 1;
-        w = &lds[byte >> 2]; shift = (byte & 3) * 8u + ((off & 1) ? 0u : 4u); maxv = 15u;
-    }
-    uint32_t old = *w;
-    for (;;) {
-        const uint32_t cur = (old >> shift) & maxv;
-        if (cur == maxv) return false;
-        const uint32_t prev = atomicCAS(w, old, old + (1u << shift));
-        if (prev == old) return cur == 0;
-        old = prev;
-    }
+    if (STORAGE == ST_BYTE) { word = off >> 2; shift = ((uint32_t)off & 3u) << 3; }
+    else { word = off >> 3; shift = ((((uint32_t)off >> 1) & 3u) << 3) + ((off & 1u) ? 0u : 4u); }
 }
 
 // Eight saturating increments with the LDS round trips overlapped: all eight words are read first, then
@@ -574,8 +516,7 @@ __device__ __forceinline__ uint32_t lds_inc8(uint32_t *lds, const uint32_t (&w)[
     for (int e = 0; e < 8; ++e) {
         const uint32_t off = (e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu);
         uint32_t shift;
-        if (STORAGE == ST_BYTE) { widx[e] = off >> 2; shift = (off & 3u) << 3; }
-        else { widx[e] = off >> 3; shift = (((off >> 1) & 3u) << 3) + ((off & 1u) ? 0u : 4u); }
+        counter_slot<STORAGE>(off, widx[e], shift);
         inc[e] = 1u << shift;
     }
     // two groups of four: the window between reading a word and swapping it stays short (fewer lost races)
@@ -641,8 +582,7 @@ __device__ __forceinline__ uint32_t lds_addw4(uint32_t *lds, const uint32_t (&w)
     for (int e = 0; e < 4; ++e) {
         const uint32_t off = w[e] & 0xffffu;
         add[e] = w[e] >> 16;
-        if (STORAGE == ST_BYTE) { widx[e] = off >> 2; shift[e] = (off & 3u) << 3; }
-        else { widx[e] = off >> 3; shift[e] = (((off >> 1) & 3u) << 3) + ((off & 1u) ? 0u : 4u); }
+        counter_slot<STORAGE>(off, widx[e], shift[e]);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) old[e] = lds[widx[e]];               // absent items (e >= n) read a harmless word
@@ -776,20 +716,20 @@ __global__ __launch_bounds__(BIN_C_THREADS) void k_bin_apply(const SketchDev *__
         for (uint32_t j = threadIdx.x; j < nvec; j += THREADS) l4[j] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     uint32_t fresh = 0;
+    auto apply = [&](const Vec &v) {
+        const uint32_t w[4] = {v.q.x, v.q.y, v.q.z, v.q.w};
+        return W ? lds_addw4<STORAGE>(lds, w, v.n) : lds_inc8<STORAGE>(lds, w, v.n);
+    };
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const uint32_t w[4] = {first[i].q.x, first[i].q.y, first[i].q.z, first[i].q.w};
-        // (an absent vector would still issue its compare-and-swaps, all on word 0: same-address LDS atomics serialise)
-        if (first[i].n) fresh += W ? lds_addw4<STORAGE>(lds, w, first[i].n) : lds_inc8<STORAGE>(lds, w, first[i].n);
-    }
+    for (int i = 0; i < MAXV; ++i)
+        if (first[i].n) fresh += apply(first[i]);   // (an absent vector would still issue its compare-and-swaps, all on word 0: same-address LDS atomics serialise)
     if (total_vec > (uint32_t)MAXV * THREADS) {
         // a fuller slice: the rest through a software pipeline, two vectors ahead
         const uint32_t v_start = (uint32_t)MAXV * THREADS + threadIdx.x;
         Vec v0 = fetch(v_start), v1 = fetch(v_start + THREADS);
         for (uint32_t v = v_start; v < total_vec; v += THREADS) {
             const Vec v2 = fetch(v + 2 * THREADS);
-            const uint32_t w[4] = {v0.q.x, v0.q.y, v0.q.z, v0.q.w};
-            fresh += W ? lds_addw4<STORAGE>(lds, w, v0.n) : lds_inc8<STORAGE>(lds, w, v0.n);
+            fresh += apply(v0);
             v0 = v1; v1 = v2;
         }
     }
@@ -813,14 +753,11 @@ __device__ __forceinline__ bool table_add_bin(const SketchDev *s, int t, uint64_
         const uint32_t bit = 1u << (bin & 31);
         return (atomicOr((uint32_t *)tab + (bin >> 5), bit) & bit) == 0;
     }
-    uint32_t *w;
-    uint32_t shift, maxv;
-    if (s->storage == ST_BYTE) {
-        w = (uint32_t *)(tab + (bin & ~3ull)); shift = (uint32_t)(bin & 3) * 8u; maxv = 255u;
-    } else {
-        const uint64_t byte = bin >> 1;
-        w = (uint32_t *)(tab + (byte & ~3ull)); shift = (uint32_t)(byte & 3) * 8u + ((bin & 1) ? 0u : 4u); maxv = 15u;
-    }
+    uint64_t word; uint32_t shift;
+    if (s->storage == ST_BYTE) counter_slot<ST_BYTE>(bin, word, shift);
+    else counter_slot<ST_NIBBLE>(bin, word, shift);
+    const uint32_t maxv = s->storage == ST_BYTE ? 255u : 15u;
+    uint32_t *w = (uint32_t *)tab + word;
     uint32_t old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (;;) {
         const uint32_t cur = (old >> shift) & maxv;
@@ -938,89 +875,39 @@ int kv_bin_plan(kv_sketch *s, uint64_t n_items_max, int nbands, bool use_mask, u
     BinGeom &g = plan->g;
     memset(&g, 0, sizeof(g));
     plan->weighted = weighted;
-    g.zero_tables = s->lazy_zero ? 1 : 0;
-    g.T = s->h.ntables;
-    for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) { g.tsize[t] = s->h.size[t]; g.ttab[t] = s->h.tab[t]; }
-    g.tile_lds = lds_front;
-    uint64_t pmin = UINT64_MAX;
-    for (int t = 0; t < g.T; ++t) pmin = std::min(pmin, s->h.size[t]);
-    g.sbits = BIN_SLICE_BITS;
-    uint32_t maxsl = 1;
-    for (int t = 0; t < g.T; ++t) {
-        g.nslices[t] = (uint32_t)((s->h.size[t] + (1ull << g.sbits) - 1) >> g.sbits);
-        maxsl = std::max(maxsl, g.nslices[t]);
+    g.zero_tables = s->lazy_zero ? 1 : 0; g.T = s->h.ntables;
+    g.tile_lds = lds_front; g.sbits = BIN_SLICE_BITS;
+    // shape and sizes: the arithmetic is kv_bin_plan.h's
+    const BinShape sh = bin_shape(s->h.size, g.T, weighted);
+    const BinSizes z = bin_sizes(sh, n_items_max, nbands, use_mask, work_units, nwgA_fixed, weighted, kv_device_cus());
+    plan->maxsl = sh.maxsl; plan->cmax = sh.cmax; plan->threadsA = sh.threadsA;
+    g.F = sh.F; g.C = sh.C; g.recipF = sh.recipF; g.ringB = sh.ringB;
+    for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) {
+        g.tsize[t] = s->h.size[t]; g.ttab[t] = s->h.tab[t]; g.nslices[t] = sh.nslices[t]; g.tmagic[t] = kv_fastmod_magic(s->h.size[t]);
     }
-    plan->maxsl = maxsl;
-    // Coarse buckets per table: as few as keep stage B's fan-out F at <= 384 slices per bucket (its u16 rings then
-    // fit three workgroups per CU), between 4 and 32 with 512-thread stage-A workgroups; 64 buckets / 1024 threads
-    // beyond 2^30 bins.  Fewer buckets = fewer distinct lines per stage-A store instruction (that stage is bound by
-    // L2 write requests): measured per 525 M k-mers into 5e8-bin tables, A/B/C = 10.5/5.0/4.0 ms with 32 buckets,
-    // 8.7/4.9/4.0 with 20, 8.3/6.1/4.0 with 16 (F = 478: rings too big for three workgroups).
-    const int cmax = maxsl <= 32u * BIN_MAX_F ? (int)std::min<uint32_t>(32u, std::max<uint32_t>(4u, (maxsl + 383u) / 384u)) : BIN_C;
-    plan->cmax = cmax;
-    g.F = (int)((maxsl + (uint32_t)cmax - 1) / (uint32_t)cmax);
-    g.C = (int)((maxsl + (uint32_t)g.F - 1) / (uint32_t)g.F);
-    g.recipF = g.F == 1 ? 0u : (uint32_t)((1ull << 32) / (uint64_t)g.F + 1);   // F == 1: kernels take slice as is
-    g.ringB = weighted ? 32u : BIN_RING_MIN;                // budget in entries: u32 rings get half the entries per byte
-    while (g.ringB * 2 <= BIN_RING_MAX && (uint64_t)g.ringB * 2 * g.F <= BIN_B_BUDGET) g.ringB *= 2;
-    if (weighted) while (g.ringB > 32u && (uint64_t)g.ringB * g.F * 4 > 2u * BIN_B_BUDGET) g.ringB /= 2;
-    const int cus = kv_device_cus();
-    const double expected = (double)(nbands > 0 && !use_mask ? n_items_max / (uint64_t)nbands + 1 : n_items_max);
-    const uint64_t ns = (uint64_t)g.T * g.C;
-    // writers: stage A = persistent workgroups (tiles dealt round-robin, so their loads are equal
-    // to within one tile); stage B = nwgB workgroups per coarse bucket, ~256 k items each
-    const uint32_t threadsA = cmax <= 32 ? 512u : 1024u;
-    plan->threadsA = threadsA;
-    if (nwgA_fixed) g.nwgA = nwgA_fixed;
-    else g.nwgA = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(work_units, 1), (cmax <= 32 ? 3u : 1u) * (uint32_t)cus);
-    {
-        const uint64_t avg = (std::max<uint64_t>(work_units, 1) + g.nwgA - 1) / g.nwgA;
-        g.quotaA = (uint32_t)std::min<uint64_t>(avg + avg / 2 + 1, 0xffffffffull);   // matches the 1.5x slack of cap1
-    }
-    const double slice_bins = (double)(1u << g.sbits);
-    const double per_bucket = expected * std::min(1.0, (double)g.F * slice_bins / (double)pmin);
-    const double per_slice = expected * std::min(1.0, slice_bins / (double)pmin);
-    g.nwgB = (uint32_t)std::max(1.0, std::min((double)std::min<uint32_t>(g.nwgA, 512), std::ceil(per_bucket / 524288.0)));
-    // a stage-B workgroup drains its segments one after the other, a dependent round trip or two each: with few items per
-    // segment (a shard of a multi-GPU run, a small batch) that chain is the stage's whole time -- at most 32 segments each
-    g.nwgB = std::max<uint32_t>(g.nwgB, std::min<uint32_t>(std::min<uint32_t>(g.nwgA, 512), (g.nwgA + 31u) / 32u));
-    const double m1 = per_bucket / g.nwgA, m2 = per_slice / g.nwgB;
-    g.cap1 = kv_round_up((uint64_t)(m1 * 1.5 + 8.0 * std::sqrt(m1)) + 2048, 64);   // tiles are dealt dynamically: shares are uneven
-    g.cap2 = kv_round_up((uint64_t)(m2 * 1.05 + 8.0 * std::sqrt(m2)) + 64, 64);
-    g.spill_cap = std::max<uint64_t>(1u << 22, (uint64_t)(expected * g.T / 8));
-    const size_t fine_bytes = weighted ? 4 : 2;
-    const size_t b_buf1 = kv_round_up(ns * g.nwgA * g.cap1 * 4, 256), b_buf2 = kv_round_up(ns * g.F * g.nwgB * g.cap2 * fine_bytes, 256);
-    const size_t b_cnt1 = kv_round_up(ns * g.nwgA * 4, 256), b_cnt2 = kv_round_up(ns * g.F * g.nwgB * 4, 256);
-    const size_t b_spill = kv_round_up(g.spill_cap * 8, 256), b_ctr = 256;
+    g.nwgA = z.nwgA; g.nwgB = z.nwgB; g.quotaA = z.quotaA;
+    g.cap1 = z.cap1; g.cap2 = z.cap2; g.spill_cap = z.spill_cap; g.fast4 = z.fast4;
     // (no memory for the staging buffers is a CAPACITY answer: the caller has a path that needs less -- in the end the atomic kernel, which needs none)
-    if (scratch.need(b_buf1 + b_buf2 + b_cnt1 + b_cnt2 + b_spill + b_ctr) != hipSuccess) {
+    if (scratch.need(z.b_total) != hipSuccess) {
         (void)hipGetLastError();
-        kv_set_error("no device memory for the partitioned count's staging buffers (%.1f GB)", (double)(b_buf1 + b_buf2 + b_cnt1 + b_cnt2 + b_spill + b_ctr) / 1e9);
+        kv_set_error("no device memory for the partitioned count's staging buffers (%.1f GB)", (double)z.b_total / 1e9);
         return KV_ERR_CAPACITY;
     }
     unsigned char *base = (unsigned char *)scratch.p;
-    g.gbuf1 = (uint32_t *)base; base += b_buf1;
-    g.gbuf2 = (uint16_t *)base; base += b_buf2;
-    g.gcnt1 = (uint32_t *)base; base += b_cnt1;
-    g.gcnt2 = (uint32_t *)base; base += b_cnt2;
-    g.spill = (unsigned long long *)base; base += b_spill;
+    g.gbuf1 = (uint32_t *)base; base += z.b_buf1;
+    g.gbuf2 = (uint16_t *)base; base += z.b_buf2;
+    g.gcnt1 = (uint32_t *)base; base += z.b_cnt1;
+    g.gcnt2 = (uint32_t *)base; base += z.b_cnt2;
+    g.spill = (unsigned long long *)base; base += z.b_spill;
     g.ctr = (unsigned long long *)base;
     {
-        bool ok = g.T == 4 && ns * g.nwgA * g.cap1 < (1ull << 32);
-        for (int t = 0; t < g.T && t < BIN_MAX_T; ++t) {
-            g.tmagic[t] = kv_fastmod_magic(s->h.size[t]);
-            ok = ok && kv_fastmod_fp(s->h.size[t]) && s->h.size[t] < (1ull << 31);
-        }
-        g.fast4 = ok ? 1 : 0;
-    }
-    {
         // the order kv_bin_last_plan documents (include/kvsketch.h)
-        const uint64_t numbers[BIN_PLAN_NUMBERS] = {(uint64_t)g.T, maxsl, (uint64_t)cmax, (uint64_t)g.F, (uint64_t)g.C, g.ringB, threadsA, g.nwgA, g.nwgB,
+        const uint64_t numbers[BIN_PLAN_NUMBERS] = {(uint64_t)g.T, sh.maxsl, (uint64_t)sh.cmax, (uint64_t)g.F, (uint64_t)g.C, g.ringB, sh.threadsA, g.nwgA, g.nwgB,
                                                     g.cap1, g.cap2, weighted ? 1u : 0u, (uint64_t)g.fast4};
         std::lock_guard<std::mutex> lk(launched.list.mu);
         memcpy(launched.plan, numbers, sizeof(numbers));
     }
-    KV_HIP(hipMemsetAsync(g.ctr, 0, b_ctr, st));   // every segment count is written by its owner: no other memset
+    KV_HIP(hipMemsetAsync(g.ctr, 0, z.b_ctr, st));   // every segment count is written by its owner: no other memset
     return KV_OK;
 }
 
@@ -1031,8 +918,7 @@ int kv_bin_finish(kv_sketch *s, BinPlan &plan, bool added_from_ctr, uint64_t n_a
     const uint64_t ns = (uint64_t)g.T * g.C;
     {
         KvProfScope prof(plan.weighted ? "k_bin_split_w" : "k_bin_split");
-        const size_t isz = plan.weighted ? 4 : 2;
-        const size_t lds = (((size_t)g.F * g.ringB * isz + 15) & ~(size_t)15) + (size_t)g.F * 2 * 4 + BIN_B_THREADS;
+        const size_t lds = bin_split_lds((uint32_t)g.F, g.ringB, plan.weighted ? 4 : 2).total;
         const auto kernel = plan.weighted ? BIN_INST(k_bin_split<true>) : BIN_INST(k_bin_split<false>);
         ensure_dynamic_lds(kernel.fn, lds);
         hipLaunchKernelGGL(bin_launching(kernel, st), dim3(g.nwgB, (unsigned)ns), dim3(BIN_B_THREADS), lds, st, g);
@@ -1085,10 +971,8 @@ int kv_consume_binned(kv_sketch *s, const kv_reads *reads, const uint64_t *d_lis
     const bool two_bit = reads && kv_bin_two_bit(s, reads);
     const uint32_t n_units2 = two_bit ? (reads->n_tiles + BIN2_TILES - 1u) / BIN2_TILES : 0u;
     {
-        // the stage-A workgroup size depends on the geometry, which depends only on the table sizes: probe it first
-        uint32_t maxsl = 1;
-        for (int t = 0; t < s->h.ntables; ++t) maxsl = std::max(maxsl, (uint32_t)((s->h.size[t] + 65535) >> 16));
-        const uint32_t threadsA = maxsl <= 32u * BIN_MAX_F ? 512u : 1024u;
+        // a list's work units depend on the stage-A workgroup size, which the table sizes alone decide
+        const uint32_t threadsA = bin_shape(s->h.size, s->h.ntables, weighted_list).threadsA;
         const uint64_t work_units = two_bit ? n_units2 : reads ? reads->n_tiles
                                           : (n_kmers + (uint64_t)threadsA * BIN_LIST_ROUNDS - 1) / ((uint64_t)threadsA * BIN_LIST_ROUNDS);
         const int rc = kv_bin_plan(s, n_kmers, nbands, filter.use_mask != 0, work_units, reads && !two_bit ? reads->tile_lds_bytes : 0u, 0u, weighted_list, &plan);

@@ -1,10 +1,12 @@
 """The case table of the partitioned count (kv_binned.hip: stage A k_bin_hash_2bit / k_bin_hash_direct / k_bin_list, stage B k_bin_split,
 stage C k_bin_apply, k_bin_spill): one row per case, each with the exact list of template instances kv_bin_last_instances must report,
 the numbers of the plan kv_bin_last_plan must report, and the planner condition the row stands on.  Shared by
-tests/test_gpu_bin_instances.py (runs every row on the GPU, holds it to the oracle) and tests/test_bin_instances_ledger.py (no GPU: the
-instances named here are exactly the ones the launch sites of kv_binned.hip can launch).  Not collected itself.
+tests/test_gpu_bin_instances.py (runs every row on the GPU, holds it to the oracle), tests/test_bin_instances_ledger.py (no GPU: the
+instances named here are exactly the ones the launch sites of kv_binned.hip can launch) and tests/test_bin_plan.py (no GPU: the
+planner's header gives every geometry's plan).  Not collected itself.
 
-The plan literals are derived from kv_bin_plan's arithmetic and written down; the report then shows whether the planner still agrees.
+The plan literals are derived from the planner's arithmetic (bin_shape of kevlar_amd/csrc/kv_bin_plan.h, which kv_bin_plan runs) and
+written down; tests/test_bin_plan.py asks the header and the GPU rows ask the report whether the planner still agrees.
 With maxsl = the most slices of 2^16 bins of any table of the sketch:
 
   cmax      the bucket budget: min(32, max(4, ceil(maxsl / 384))) up to 32 x 512 = 16384 slices (2^30 bins), 64 beyond.  Four buckets

@@ -134,7 +134,7 @@ COUNT_GEOMETRIES = {
     'N2x1e6': N(1e6, 2), 'N7x1e6': N(1e6, 7),
     'C5x1e5': C(1e5, 5), 'C8x1e5': C(1e5, 8), 'C16x1e5': C(1e5, 16),
 }
-BIN_MAX_T = 4                       # kevlar_amd/csrc/kv_binned.h: more tables than this take the atomic kernel whatever is asked for
+BIN_MAX_T = 4                       # kevlar_amd/csrc/kv_bin_plan.h: more tables than this take the atomic kernel whatever is asked for
 
 _count_states = {}
 
