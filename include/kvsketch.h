@@ -628,6 +628,33 @@ int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sketch *refr, c
                      int casemin, int ctrlmax, int caseabundlow, int ctrlabundhigh, int dropoutliers, uint32_t *records,
                      double *likelihoods, uint8_t *counts, uint8_t *refr_abunds);
 
+/* ---- per-partition unitigs for `kevlar assemble` (kevlar/assemble.py, kevlar/assembly.pyx; kv_assemble.hip) ------------------
+ * The reference hands every partition to fermi-lite.  Here a stated rule is computed for a batch of partitions in one call
+ * (DESIGN.md section 13): per partition, the canonical K-mers seen at least min_count times are the nodes of a de Bruijn graph
+ * and every maximal chain of simple edges is reported once, as the smaller of the chain's sequence and its reverse complement.
+ * Read r = bases[read_off[r] .. read_off[r + 1]) (ASCII, either case; a window with any other byte is skipped); partition p =
+ * reads part_first[p] .. part_first[p + 1), part_first[0] = 0 and part_first[n_parts] = n_reads.  K is odd, 13..63.  A key of one
+ * partition says nothing about the same key of another.
+ * kv_assemble_batch computes ALL unitigs (filtering by length, ordering and naming are the caller's) and keeps them in *out;
+ * *n_unitigs and *n_bases size the arrays of kv_assemble_fetch: bases_out[n_bases], offsets_out[n_unitigs + 1], part_out[n_unitigs]
+ * (the partition of each unitig; unitigs come partition after partition, in no particular order inside one) and
+ * count_out[n_parts] (unitigs per partition).  mem_budget bounds the device memory of one launch (0: 4 GiB): the partitions are
+ * taken in order and cut into as many launches as that takes (kv_assemble_plan, host code only: launch_ends[l] = one past the last
+ * partition of launch l, n_parts entries at most); one partition that alone exceeds the budget is KV_ERR_CAPACITY.
+ * kv_assemble_stats: stats_out[0..6] = windows of valid bases, distinct (partition, key) pairs, solid ones, heads (oriented nodes
+ * that start a unitig, both strands), unitigs, solid keys on no unitig (cycles without a head), launches.
+ * Null arguments, an even K or one outside 13..63, min_count 0, offsets or partition bounds that decrease or do not cover the
+ * reads: KV_ERR_ARG before anything touches the device, the outputs untouched.                                                  */
+#define KV_ASSEMBLE_NSTATS 7
+typedef struct kv_assembly kv_assembly;
+int kv_assemble_plan(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
+                     uint64_t mem_budget, uint64_t *launch_ends, uint64_t *n_launches);
+int kv_assemble_batch(const char *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts,
+                      int ksize, uint32_t min_count, uint64_t mem_budget, uint64_t *n_unitigs, uint64_t *n_bases, kv_assembly **out);
+int kv_assemble_fetch(kv_assembly *h, char *bases_out, uint64_t *offsets_out, uint32_t *part_out, uint32_t *count_out);
+int kv_assemble_stats(kv_assembly *h, uint64_t *stats_out);
+int kv_assemble_destroy(kv_assembly *h);
+
 #ifdef __cplusplus
 }
 #endif

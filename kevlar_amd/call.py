@@ -6,7 +6,7 @@ host core; here all pairs of a run are aligned in one device batch (kevlar_amd.a
 scanned in one more (kevlar_amd.varmap.scan_batch), and the host only assembles `Variant` objects from the records.
 
 The command line is this module's: `python -m kevlar_amd.call contigs.augfasta cutouts.fa -o calls.vcf`, with the reference's
-flags.  The `kevlar` command of kevlar_amd.cli has no `call` entry yet."""
+flags; `python -m kevlar_amd call ...` takes the same ones (kevlar_amd.cli builds its subcommand from parser() below)."""
 import argparse
 from collections import defaultdict
 import sys

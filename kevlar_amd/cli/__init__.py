@@ -1,4 +1,5 @@
-"""Command line of the drop-in: `kevlar count | novel | filter | partition | unband | dist | split | augment | localize`.
+"""Command line of the drop-in: `kevlar count | novel | filter | partition | unband | dist | split | augment | localize | assemble |
+alac | call | simlike`.
 
 Flag names, defaults and dispatch follow the reference (kevlar/cli/__init__.py:31-108 and
 kevlar/cli/{count,novel,filter,partition,unband,dist}.py); only the subcommands on the
@@ -6,6 +7,7 @@ novel-k-mer path exist here.  `novel` has extra switches: --ref-band-quirk (see
 kevlar_amd/novel.py) and --all-bands / --distributed / --dist-backend (kevlar_amd/allbands.py).
 """
 import argparse
+import importlib
 import sys
 
 import kevlar_amd
@@ -175,6 +177,27 @@ def _localize(sub):
     p.add_argument('contigs', nargs='+', help='assembled reads in augmented Fasta format')
 
 
+def _module(name):
+    """kevlar_amd.assemble, .alac, .call and .simlike are also commands of their own (`python -m kevlar_amd.call`), so nothing
+    imports them before they run: this module takes their parsers and drivers when the command line is built or dispatched"""
+    return importlib.import_module('kevlar_amd.' + name)
+
+
+def _own_parser(name):
+    """a subcommand made of the flags, defaults and help of the module's own parser(): one definition for both ways in"""
+    def add(sub):
+        own = _module(name).parser()
+        sub.add_parser(name, parents=[own], add_help=False, description=own.description)
+    return add
+
+
+def _own_main(name):
+    def main(args):
+        return _module(name).main(args)
+    main.__name__ = name + '_main'
+    return main
+
+
 mains = {
     'augment': kevlar_amd.augment.main,
     'gentrio': kevlar_amd.gentrio.main,
@@ -193,6 +216,15 @@ downstream_mains = {
     'localize': kevlar_amd.localize.main,
 }
 
+# The variant-calling half: contigs from partitions, and calls from contigs.  A third dict for the same reason as the second
+# (tests/test_localize_reference.py holds `downstream_mains` to its one entry).
+calling_mains = {
+    'assemble': _own_main('assemble'),
+    'alac': _own_main('alac'),
+    'call': _own_main('call'),
+    'simlike': _own_main('simlike'),
+}
+
 subparser_funcs = {
     'augment': _augment,
     'gentrio': _gentrio,
@@ -204,20 +236,24 @@ subparser_funcs = {
     'partition': _partition,
     'unband': _unband,
     'localize': _localize,
+    'assemble': _own_parser('assemble'),
+    'alac': _own_parser('alac'),
+    'call': _own_parser('call'),
+    'simlike': _own_parser('simlike'),
 }
 
 
 def parser():
     top = argparse.ArgumentParser(
         prog='kevlar', formatter_class=argparse.RawDescriptionHelpFormatter,
-        description='kevlar novel-k-mer discovery on AMD MI355X (count, novel, filter, partition, unband, dist, split, augment, gentrio, '
-        'localize)')
+        description='kevlar novel-k-mer discovery and variant calling on AMD MI355X (count, novel, filter, partition, unband, dist, split, '
+        'augment, gentrio, localize, assemble, alac, call, simlike)')
     top._positionals.title = 'Subcommands'
     top._optionals.title = 'Global arguments'
     top.add_argument('-v', '--version', action='version', version='kevlar v{}'.format(kevlar_amd.__version__))
     top.add_argument('-l', '--logfile', metavar='F', help='write diagnostics to F instead of stderr')
     top.add_argument('--tee', action='store_true', help='write diagnostics to the logfile and to stderr')
-    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(list(mains) + list(downstream_mains))) + '"')
+    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(list(mains) + list(downstream_mains) + list(calling_mains))) + '"')
     for func in subparser_funcs.values():
         func(sub)
     return top
@@ -238,7 +274,7 @@ def run(arglist=None):
     tests pass an argument list."""
     top = parser()
     args = parse_args(arglist)
-    driver = mains.get(args.cmd) or downstream_mains.get(args.cmd)
+    driver = mains.get(args.cmd) or downstream_mains.get(args.cmd) or calling_mains.get(args.cmd)
     if driver is None:
         top.print_help()
         raise SystemExit(0 if args.cmd is None else 2)

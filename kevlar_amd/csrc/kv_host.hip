@@ -438,6 +438,7 @@ extern "C" int kv_scratch_trim(void)
     kv_route_scratch_release();
     kv_bin_scratch_release();
     kv_novel_scratch_release();
+    kv_asm_scratch_release();
     kv_unique_scratch_release();
     kv_table_cache_release();
     return KV_OK;

@@ -304,6 +304,7 @@ void kv_skm_scratch_release();       // kv_skm.hip: every stream's bucket arena,
 void kv_route_scratch_release();     // kv_shard.hip: every stream's pair sink
 void kv_novel_scratch_release();     // kv_novel.hip: every stream's bit map of the pairs scan
 void kv_bin_scratch_release();       // kv_binned.hip: every stream's staging of the partitioned add
+void kv_asm_scratch_release();       // kv_assemble.hip: every stream's windows, key table, heads and unitigs
 void kv_unique_scratch_release();    // kv_graph.hip: every stream's first-toucher arrays of kv_unique_new that no running call holds
 void kv_ensure_dynamic_lds(const void *kernel, size_t bytes);   // hipFuncSetAttribute once per growth
 

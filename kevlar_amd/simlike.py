@@ -9,7 +9,8 @@ objects from the records.  The three look-up functions at the top are the earlie
 kv_hash_kmers + kv_get_hashes here), which the device batch is tested against.
 
 The command line is this module's: `python -m kevlar_amd.simlike --case kid.ct --controls mom.ct dad.ct --refr refr.sct
-calls.vcf`, with the reference's flags.  The `kevlar` command of kevlar_amd.cli has no `simlike` entry yet."""
+calls.vcf`, with the reference's flags; `python -m kevlar_amd simlike ...` takes the same ones (kevlar_amd.cli builds its subcommand
+from parser() below)."""
 import argparse
 from collections import namedtuple
 import ctypes
