@@ -1,6 +1,7 @@
 """Plain-Python restatement of the assembly rule of `kevlar assemble`, literal and slow: strings,
 dictionaries and sets, no packing, no table.  The GPU tests hold kv_assemble.hip to it and tests/test_assemble_reference.py holds
-it to what the reference states about its own assembler.
+it to what the reference states about its own assembler and, through check_unitigs below (which takes an answer and checks rules 1
+to 5 on it without a walk), to the rule itself on inputs made of repeats (structured_partition).
 
 The rule, per partition, with K odd and min_count >= 1:
  1. windows: every window of K bases of every read, either letter case; one with a byte outside ACGT is skipped; its key is the
@@ -197,6 +198,165 @@ def seeded_partition(seed, n_reads=30, read_len=150, hap_len=400, error=0.01):
         read = ''.join(read)
         reads.append(rc(read) if rng.random() < 0.5 else read)
     return reads
+
+
+# ---- structured inputs: repeats, hairpins, rings ---------------------------------------------------------------------------------
+# Random DNA has no repeated K-mer at K >= 13; these haplotypes are made of them.
+KINDS = ('alpha2', 'alpha2rc', 'tandem', 'repeat', 'hairpin', 'ringtail')
+TANDEM_UNITS = (1, 2, 3, 5, 7, 11, 14, 17)
+FUZZ_SEEDS = range(600)
+
+
+def letters(rng, alphabet, n):
+    return ''.join(rng.choice(alphabet) for _ in range(n))
+
+
+def structured_haplotype(rng, kind):
+    """60 to 260 bases of the kind"""
+    if kind == 'alpha2':                            # two letters: 2^13 possible 13-mers, forks and repeats everywhere
+        hap = letters(rng, 'AC', rng.randrange(60, 261))
+    elif kind == 'alpha2rc':                        # ... and every K-mer's reverse complement is of the same alphabet
+        hap = letters(rng, 'AT', rng.randrange(60, 261))
+    elif kind == 'tandem':                          # units shorter and longer than K = 13
+        unit = random_dna(rng, rng.choice(TANDEM_UNITS))
+        span = rng.randrange(20, 221)
+        hap = random_dna(rng, 20) + (unit * (span // len(unit) + 1))[:span] + random_dna(rng, 20)
+    elif kind == 'repeat':                          # one element several times, each copy on a random strand
+        element = random_dna(rng, rng.randrange(13, 40))
+        hap = random_dna(rng, rng.randrange(5, 40))
+        for _ in range(rng.randrange(2, 6)):
+            hap += (rc(element) if rng.random() < 0.5 else element) + random_dna(rng, rng.randrange(5, 40))
+    elif kind == 'hairpin':                         # the node in the middle of the stem has its own reverse complement behind it
+        stem = random_dna(rng, rng.randrange(10, 40))
+        hap = random_dna(rng, rng.randrange(20, 90)) + stem + random_dna(rng, rng.randrange(0, 4)) + rc(stem) + random_dna(rng, rng.randrange(20, 90))
+    else:                                           # a cycle with a way in and a way out
+        assert kind == 'ringtail'
+        hap = random_dna(rng, 25) + 3 * random_dna(rng, rng.randrange(13, 60)) + random_dna(rng, 25)
+    hap = hap[:260]
+    assert 60 <= len(hap) <= 260
+    return hap
+
+
+def structured_partition(seed):
+    """(kind, reads): 4 to 29 reads of one length of 20 to 69 bases at random starts over a structured haplotype, about a third of
+    them with one byte replaced by a letter of ACGTN, about half of the N-free ones reverse-complemented"""
+    rng = random.Random(seed)
+    kind = KINDS[seed % len(KINDS)]
+    hap = structured_haplotype(rng, kind)
+    length = rng.randrange(20, 70)
+    reads = []
+    for _ in range(rng.randrange(4, 30)):
+        s = rng.randrange(0, len(hap) - length + 1)
+        read = hap[s:s + length]
+        if rng.random() < 1 / 3:
+            at = rng.randrange(length)
+            read = read[:at] + rng.choice('ACGTN') + read[at + 1:]
+        if 'N' not in read and rng.random() < 0.5:
+            read = rc(read)
+        reads.append(read)
+    return kind, reads
+
+
+_structured = {}
+
+
+def structured_answers(K, min_count, seeds=FUZZ_SEEDS):
+    """[(kind, reads, unitigs, stats)] of the restatement over the seeds, each computed once and shared; nobody changes them"""
+    rows = []
+    for seed in seeds:
+        if (K, min_count, seed) not in _structured:
+            kind, reads = structured_partition(seed)
+            _structured[K, min_count, seed] = (kind, reads) + unitigs(reads, K, min_count)
+        rows.append(_structured[K, min_count, seed])
+    return rows
+
+
+# ---- an answer against rules 1 to 5, without a walk -------------------------------------------------------------------------------
+def check_unitigs(reads, K, min_count, found, stats):
+    """Asserts that `found` (a list of strings) and `stats` are the unitigs of the partition by rules 1 to 5 above.  Independent of
+    unitigs(): it starts from the answer, not from heads, follows no chain and uses key_counts, canonical, rc and set membership
+    only.  Every chain of the answer must be a chain of simple edges that cannot be extended, every solid key must lie on exactly
+    one of them, and a solid key on none must have a simple edge coming in on both strands (so it is not on a chain with a head: the
+    head of that chain would be a solid key on no unitig WITHOUT such an edge)."""
+    counts, windows = key_counts(reads, K)
+    solid = set(key for key, c in counts.items() if c >= min_count)
+
+    def succ(w):
+        return [w[1:] + b for b in 'ACGT' if canonical(w[1:] + b) in solid]
+
+    def pred(w):
+        return [b + w[:-1] for b in 'ACGT' if canonical(b + w[:-1]) in solid]
+
+    def simple(w, v):
+        return succ(w) == [v] and pred(v) == [w]
+
+    def simple_edge_in(w):
+        return len(pred(w)) == 1 and simple(pred(w)[0], w)
+
+    def simple_edge_out(w):
+        return len(succ(w)) == 1 and simple(w, succ(w)[0])
+
+    where = {}                                      # key: the unitigs it lies on, once per node
+    for i, u in enumerate(found):
+        assert len(u) >= K and not u.strip('ACGT'), (i, u)
+        assert u <= rc(u), 'unitig {} is the larger strand'.format(i)
+        nodes = [u[j:j + K] for j in range(len(u) - K + 1)]
+        for w in nodes:
+            assert canonical(w) in solid, 'unitig {}: {} is not solid'.format(i, w)
+            where.setdefault(canonical(w), []).append(i)
+        for w, v in zip(nodes, nodes[1:]):
+            assert simple(w, v), 'unitig {}: {} -> {} is not a simple edge'.format(i, w, v)
+        assert not simple_edge_in(nodes[0]), 'unitig {} goes on in front'.format(i)
+        assert not simple_edge_out(nodes[-1]), 'unitig {} goes on behind'.format(i)
+    for key, on in where.items():
+        assert len(set(on)) == 1, '{} lies on unitigs {}'.format(key, sorted(set(on)))
+        assert len(on) == 1 or (len(on) == 2 and found[on[0]] == rc(found[on[0]])), '{} lies {} times on unitig {}'.format(key, len(on), on[0])
+    off = solid - set(where)
+    for key in off:
+        assert simple_edge_in(key) and simple_edge_in(rc(key)), '{} is on no unitig and not on a cycle'.format(key)
+    heads = sum(1 for key in solid for w in (key, rc(key)) if not simple_edge_in(w))
+    assert stats['cycle_keys'] == len(off)
+    assert stats['unitigs'] == len(found)
+    assert stats['solid'] == len(solid)
+    assert stats['distinct'] == len(counts)
+    assert stats['windows'] == windows
+    assert stats['heads'] == heads                  # (a unitig has two, or one when it is its own reverse complement)
+    assert heads == sum(1 if u == rc(u) else 2 for u in found)
+
+
+# ---- the device against the restatement ---------------------------------------------------------------------------------------------
+def agree(partitions, K=31, min_count=2, mem_budget=0, launches=None, want=None):
+    """the device's unitigs and stats equal the restatement's; returns (unitigs per partition, stats).  `want`: the restatement's
+    (unitigs, stats) per partition where the caller has them already"""
+    from kevlar_amd import assemble as asm
+    got, stats = asm.unitigs_batch(partitions, K, min_count, mem_budget)
+    if want is None:
+        want = [unitigs(reads, K, min_count) for reads in partitions]
+    assert len(got) == len(partitions) == len(want)
+    for p, (mine, (theirs, _)) in enumerate(zip(got, want)):
+        assert len(set(mine)) == len(mine), 'partition {}: a unitig reported twice'.format(p)
+        assert sorted(mine) == theirs, 'partition {}'.format(p)
+    assert {name: stats[name] for name in STAT_NAMES} == add_stats([s for _, s in want])
+    if launches is not None:
+        assert stats['launches'] == launches
+    return [u for u, _ in want], stats
+
+
+def device_plan(parts, K, budget):
+    """(return code, one past the last partition of every launch) of kv_assemble_plan"""
+    import ctypes
+    import numpy as np
+    from kevlar_amd import _lib
+    lib = _lib.load()
+    lengths = [len(r) for reads in parts for r in reads]
+    read_off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    read_off[1:] = np.cumsum(np.array(lengths, dtype=np.uint64))
+    part_first = np.zeros(len(parts) + 1, dtype=np.uint64)
+    part_first[1:] = np.cumsum(np.array([len(reads) for reads in parts], dtype=np.uint64))
+    ends = np.zeros(max(len(parts), 1), dtype=np.uint64)
+    n = ctypes.c_uint64(0)
+    rc_ = lib.kv_assemble_plan(read_off.ctypes.data, len(lengths), part_first.ctypes.data, len(parts), K, budget, ends.ctypes.data, ctypes.byref(n))
+    return rc_, ends[:n.value].tolist()
 
 
 # ---- the planner of kv_asm_plan.h, restated -------------------------------------------------------------------------------------

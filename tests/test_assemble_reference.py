@@ -1,7 +1,8 @@
 """The assembly rule without a GPU: the plain-Python restatement of tests/assemble_common.py against what the reference's own
 tests state about fermi-lite's contigs (tests/golden/assemble/recorded.json, read out of kevlar/tests/test_assemble.py), the
-restatement held to change, the planner of kevlar_amd/csrc/kv_asm_plan.h at its edges (the header compiles for the host;
-tests/harness/asm_plan_host.cpp wraps it in a C ABI), and the command line's four new entries.
+restatement held to change and, on repeats, hairpins and rings, to the rule itself (ac.check_unitigs), the planner of
+kevlar_amd/csrc/kv_asm_plan.h at its edges (the header compiles for the host; tests/harness/asm_plan_host.cpp wraps it in a C
+ABI), and the command line's four new entries.
 
 The two assemblers differ by a few bases at contig ends and on repeats; the figures measured when the module was written stand
 beside each assertion."""
@@ -120,6 +121,104 @@ def test_restatement_on_hand_made_graphs():
     own = half + ac.rc(half)
     found, stats = ac.unitigs([own, own], 31)
     assert found == [own] and stats['heads'] == 1 and stats['solid'] == 25
+
+
+# ---- the restatement against the rule itself: ac.check_unitigs needs no walk -------------------------------------------------------
+@pytest.mark.parametrize('third', [0, 1, 2])
+@pytest.mark.parametrize('min_count', [1, 2, 3])
+@pytest.mark.parametrize('K', [13, 15, 31, 33, 63])
+def test_restatement_keeps_the_rule_on_structured_partitions(K, min_count, third):
+    seeds = ac.FUZZ_SEEDS[200 * third:200 * third + 200]
+    assert len(seeds) == 200 and len(ac.FUZZ_SEEDS) == 600
+    for kind, reads, found, stats in ac.structured_answers(K, min_count, seeds):
+        ac.check_unitigs(reads, K, min_count, found, stats)
+
+
+def test_restatement_keeps_the_rule_on_seeded_partitions_and_fixtures():
+    for K in (13, 31, 33, 63):                      # the inputs of tests/test_gpu_assemble.py
+        for i in range(4):
+            reads = ac.seeded_partition(100 * K + i, n_reads=14, read_len=90 + 7 * i, hap_len=230)
+            ac.check_unitigs(reads, K, 2, *ac.unitigs(reads, K, 2))
+    for seed in (5, 77, 78):
+        reads = ac.seeded_partition(seed, 12, 80, 200)
+        ac.check_unitigs(reads, 31, 2, *ac.unitigs(reads, 31, 2))
+    names = [name for name in ac.recorded()['files'] if name.startswith(('fml/', 'pico-var/'))]
+    assert len(names) >= 13
+    for name in names:
+        for partid, reads in ac.read_partitions(name):
+            found, stats = ac.unitigs(reads, 31, 2)
+            ac.check_unitigs(reads, 31, 2, found, stats)
+            assert stats['solid'] > 0, name
+
+
+def test_structured_partitions_are_what_they_say():
+    assert [ac.structured_partition(seed)[0] for seed in range(12)] == list(ac.KINDS) * 2
+    assert ac.structured_partition(41) == ac.structured_partition(41)
+    for seed in ac.FUZZ_SEEDS:
+        kind, reads = ac.structured_partition(seed)
+        assert 4 <= len(reads) <= 29 and len(set(len(r) for r in reads)) == 1 and 20 <= len(reads[0]) <= 69
+        assert not ''.join(reads).strip('ACGTN')
+        if kind in ('alpha2', 'alpha2rc'):          # (on either strand; a replaced byte may be any letter: at most one per read)
+            alphabet = 'AC' if kind == 'alpha2' else 'AT'
+            assert all(min(len(r.replace(alphabet[0], '').replace(alphabet[1], '')) for r in (read, ac.rc(read))) <= 1 for read in reads)
+    rng = random.Random(1)
+    for _ in range(200):
+        for kind in ac.KINDS:
+            assert 60 <= len(ac.structured_haplotype(rng, kind)) <= 260
+
+
+# The census of the fuzz, as conditions on the inputs: what the device test of tests/test_gpu_assemble_shapes.py is certain to meet.
+# Counted by the restatement alone over the same seeds in four of that test's fifteen cases, the cheapest that clear every floor
+# (each further case only adds).  Figures when written: 116 cases with cycle keys, 20 of them with heads too, 276 unitigs that are
+# their own reverse complement, 1184 cases of three unitigs or more; over K in {13, 15, 31} and min_count in {1, 2}: 57, 20, 469, 2659.
+def test_census_of_the_structured_fuzz():
+    cycles = cycles_and_heads = own = three = 0
+    answered = dict.fromkeys(ac.KINDS, 0)
+    for K in (13, 31):
+        for min_count in (2, 3):
+            for kind, reads, found, stats in ac.structured_answers(K, min_count):
+                cycles += stats['cycle_keys'] > 0
+                cycles_and_heads += stats['cycle_keys'] > 0 and stats['heads'] > 0
+                own += sum(1 for u in found if u == ac.rc(u))
+                three += len(found) >= 3
+                answered[kind] += len(found) > 0
+    assert cycles_and_heads >= 10
+    assert cycles >= 40
+    assert own >= 100
+    assert three >= 1000
+    assert all(n >= 1 for n in answered.values()), answered
+    # the two-word keys meet hairpins and their own reverse complements too (K = 33; a read of the fuzz is too short for one at 63)
+    assert sum(1 for m in (2, 3) for _, _, found, _ in ac.structured_answers(33, m) for u in found if u == ac.rc(u)) >= 10
+
+
+def test_the_checker_rejects_three_wrong_answers():
+    K, min_count = 15, 2
+    cases = ac.structured_answers(K, min_count)
+    # a unitig reported as the larger strand
+    kind, reads, found, stats = next(c for c in cases if any(u != ac.rc(u) for u in c[2]))
+    ac.check_unitigs(reads, K, min_count, found, stats)
+    at = next(i for i, u in enumerate(found) if u != ac.rc(u))
+    with pytest.raises(AssertionError, match='larger strand'):
+        ac.check_unitigs(reads, K, min_count, found[:at] + [ac.rc(found[at])] + found[at + 1:], stats)
+    # a unitig cut in two at a simple edge, each piece as its smaller strand
+    kind, reads, found, stats = next(c for c in cases if any(len(u) >= K + 4 and u != ac.rc(u) for u in c[2]))
+    at = next(i for i, u in enumerate(found) if len(u) >= K + 4 and u != ac.rc(u))
+    cut = (len(found[at]) - K) // 2
+    pieces = [min(piece, ac.rc(piece)) for piece in (found[at][:cut + K], found[at][cut + 1:])]
+    assert len(pieces[0]) + len(pieces[1]) == len(found[at]) + K - 1
+    with pytest.raises(AssertionError, match='goes on'):
+        ac.check_unitigs(reads, K, min_count, sorted(found[:at] + pieces + found[at + 1:]), dict(stats, unitigs=stats['unitigs'] + 1))
+    # a unitig that is its own reverse complement dropped, its keys counted as a cycle's
+    kind, reads, found, stats = next(c for c in cases if any(u == ac.rc(u) for u in c[2]))
+    ac.check_unitigs(reads, K, min_count, found, stats)
+    at = next(i for i, u in enumerate(found) if u == ac.rc(u))
+    fewer = dict(stats, unitigs=stats['unitigs'] - 1, heads=stats['heads'] - 1, cycle_keys=stats['cycle_keys'] + (len(found[at]) - K + 1) // 2)
+    with pytest.raises(AssertionError, match='on no unitig and not on a cycle'):
+        ac.check_unitigs(reads, K, min_count, found[:at] + found[at + 1:], fewer)
+    # and a wrong count alone
+    for name in ac.STAT_NAMES:
+        with pytest.raises(AssertionError):
+            ac.check_unitigs(reads, K, min_count, found, dict(stats, **{name: stats[name] + 1}))
 
 
 # ---- the planner -------------------------------------------------------------------------------------------------------------------

@@ -20,18 +20,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def agree(partitions, K=31, min_count=2, mem_budget=0, launches=None):
-    """the device's unitigs and stats equal the restatement's; returns (unitigs per partition, stats)"""
-    got, stats = asm.unitigs_batch(partitions, K, min_count, mem_budget)
-    want = [ac.unitigs(reads, K, min_count) for reads in partitions]
-    assert len(got) == len(partitions)
-    for p, (mine, (theirs, _)) in enumerate(zip(got, want)):
-        assert len(set(mine)) == len(mine), 'partition {}: a unitig reported twice'.format(p)
-        assert sorted(mine) == theirs, 'partition {}'.format(p)
-    assert {name: stats[name] for name in ac.STAT_NAMES} == ac.add_stats([s for _, s in want])
-    if launches is not None:
-        assert stats['launches'] == launches
-    return [u for u, _ in want], stats
+agree, device_plan = ac.agree, ac.device_plan       # (shared with tests/test_gpu_assemble_shapes.py)
 
 
 @pytest.fixture(scope='module')
@@ -177,19 +166,6 @@ def test_300_partitions_at_once_in_sevens_and_one_at_a_time(hk):
 
 
 # ---- 6. the planner's edges through the device ---------------------------------------------------------------------------------
-def device_plan(parts, K, budget):
-    lib = _lib.load()
-    lengths = [len(r) for reads in parts for r in reads]
-    read_off = np.zeros(len(lengths) + 1, dtype=np.uint64)
-    read_off[1:] = np.cumsum(np.array(lengths, dtype=np.uint64))
-    part_first = np.zeros(len(parts) + 1, dtype=np.uint64)
-    part_first[1:] = np.cumsum(np.array([len(reads) for reads in parts], dtype=np.uint64))
-    ends = np.zeros(max(len(parts), 1), dtype=np.uint64)
-    n = ctypes.c_uint64(0)
-    rc = lib.kv_assemble_plan(read_off.ctypes.data, len(lengths), part_first.ctypes.data, len(parts), K, budget, ends.ctypes.data, ctypes.byref(n))
-    return rc, ends[:n.value].tolist()
-
-
 @pytest.mark.parametrize('K', [31, 33])
 def test_launch_split_and_capacity_edges(hk, K):
     parts = [ac.seeded_partition(400 + i, n_reads=5 + 3 * (i % 4), read_len=70 + i, hap_len=180) for i in range(12)]
