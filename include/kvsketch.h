@@ -520,6 +520,38 @@ int kv_localize_counts(kv_localize *h, uint32_t *counts_out, uint64_t n_windows)
 int kv_localize_stats(kv_localize *h, uint64_t *stats_out);
 int kv_localize_destroy(kv_localize *h);
 
+/* ---- calls against BED regions for `kevlar varfilter` (kevlar/varfilter.py, kevlar.parse_bed; kv_varfilter.hip) ----------------
+ * The reference keeps the calls in an interval tree and looks every BED line up in it.  Here the calls become an index on the
+ * device -- sorted by (chromosome, start), with the running maximum of `end` per chromosome -- and the BED text is scanned against
+ * it chunk by chunk.  A region (s, e) hits a call (a, b) on a chromosome of the same name, byte for byte, iff s < e, a < e and
+ * b > s (intervaltree >= 3.0.2); coordinates are 0-based half-open int64.
+ * kv_varfilter_create: the distinct chromosome names of the calls, name c = names[name_off[c] .. name_off[c + 1]); call i lies on
+ * chromosome call_chrom[i] at [call_start[i], call_end[i]).  A repeated name or an id out of range is KV_ERR_ARG.
+ * kv_varfilter_scan: one chunk of BED text (host or device memory) that begins at a line start and ends at a line end or at the
+ * end of the file; text_offset is the chunk's place in the file.  Lines end at '\n'; a line whose first byte is '#' and a line
+ * of separators only (0x09-0x0d, 0x1c-0x20) are skipped; otherwise the first three tokens are chromosome, start and end, a number
+ * being [+-]?[0-9]+ within int64.  A line with fewer tokens or another number makes the call KV_ERR_ARG, and
+ * kv_varfilter_bad_line then gives the least file offset of such a line of that call (UINT64_MAX after a good one).
+ * kv_varfilter_regions: the same join for n parsed regions (host arrays); chrom_id 0xFFFFFFFF = not among the calls' names.
+ * kv_varfilter_hits: flags_out[i] = 1 if call i was hit so far, in the order the calls were given.
+ * kv_varfilter_stats: stats_out[0..5] = lines seen, comment and blank lines, regions parsed, regions on a known chromosome,
+ * region-call overlaps found, calls flagged.
+ * kv_varfilter_plan: plan_out[0..4] = the workgroup tile (bytes) a chunk of n_bytes is scanned in, the number of tiles, the two
+ * tile sizes there are and the chunk size from which the larger one is taken.  Host only.
+ * kv_varfilter_chunk_cut: where a buffer of text is cut so that the chunk ends at a line end: behind its last '\n', at n_bytes
+ * when the file ends with the buffer, 0 when no line ends in it (read on).  Host only.                                        */
+typedef struct kv_varfilter kv_varfilter;
+int kv_varfilter_create(const char *names, const uint64_t *name_off, uint64_t n_chroms, const uint32_t *call_chrom,
+                        const int64_t *call_start, const int64_t *call_end, uint64_t n_calls, kv_varfilter **out);
+int kv_varfilter_scan(kv_varfilter *h, const char *text, uint64_t n_bytes, uint64_t text_offset);
+int kv_varfilter_bad_line(kv_varfilter *h, uint64_t *offset);
+int kv_varfilter_regions(kv_varfilter *h, const uint32_t *chrom_id, const int64_t *start, const int64_t *end, uint64_t n);
+int kv_varfilter_hits(kv_varfilter *h, uint8_t *flags_out, uint64_t n_calls);
+int kv_varfilter_stats(kv_varfilter *h, uint64_t *stats_out);
+int kv_varfilter_destroy(kv_varfilter *h);
+int kv_varfilter_plan(uint64_t n_bytes, uint64_t *plan_out);
+int kv_varfilter_chunk_cut(const char *buf, uint64_t n_bytes, int at_eof, uint64_t *cut);
+
 /* ---- contig-to-cutout alignment, the first half of `kevlar call` (kevlar/alignment.pyx, src/align.c; kv_align.hip) ----------
  * The reference aligns one contig against one cutout with ksw2's extension aligner, unbanded and without z-drop: a global
  * alignment, score = H(tlen - 1, qlen - 1), traceback from that corner.  Here a batch of such jobs runs on the device and

@@ -7,6 +7,7 @@ import builtins
 from gzip import open as gzopen
 from os import makedirs
 from os.path import dirname
+import re
 import sys
 
 __version__ = '0.7+mi355x.r1'
@@ -103,6 +104,48 @@ def same_seq(seq1, seq2, seq2revcom=None):
     if seq2revcom is None:
         seq2revcom = revcom(seq2)
     return seq1 == seq2 or seq1 == seq2revcom
+
+
+_BED_SEPARATORS = '\t\n\x0b\x0c\r\x1c\x1d\x1e\x1f '
+_BED_SPLIT = re.compile('[' + _BED_SEPARATORS + ']+')
+_BED_NUMBER = re.compile('[+-]?[0-9]+')
+
+
+def _bed_number(token):
+    if _BED_NUMBER.fullmatch(token) is None or not -2 ** 63 <= int(token) < 2 ** 63:
+        raise ValueError('not an integer coordinate of a BED line: {!r}'.format(token))
+    return int(token)
+
+
+def parse_bed(instream):
+    """(chromosome, start, end, further columns) of every line of a BED stream (kevlar/__init__.py:131-140), by the grammar the device
+    scans by (kevlar_amd.varfilter): a line whose first byte is `#` and a line of separators only are skipped,
+    separators are 0x09-0x0d, 0x1c-0x1f and the space, a coordinate is [+-]?[0-9]+ within int64.  Lines of str or of bytes."""
+    for line in instream:
+        if isinstance(line, (bytes, bytearray)):
+            line = bytes(line).decode('utf-8', 'surrogateescape')
+        if line.startswith('#'):
+            continue
+        line = line.strip(_BED_SEPARATORS)
+        if line == '':
+            continue
+        values = _BED_SPLIT.split(line)
+        if len(values) < 3:
+            raise ValueError('a BED line needs chromosome, start and end: {!r}'.format(line))
+        chrom, start, end, *data = values
+        yield chrom, _bed_number(start), _bed_number(end), data
+
+
+def bedstream(bedfilelist):
+    """parse_bed over several files (kevlar/__init__.py:143-147); read as bytes, so lines end at `\\n` alone, as on the device"""
+    for bedfile in bedfilelist:
+        if bedfile in ('-', None):
+            lines = sys.stdin.buffer.read().split(b'\n')
+        else:
+            with (gzopen(bedfile, 'rb') if bedfile.endswith('.gz') else builtins.open(bedfile, 'rb')) as fh:
+                lines = fh.read().split(b'\n')
+        for values in parse_bed(lines):
+            yield values
 
 
 from kevlar_amd.timer import Timer  # noqa: E402

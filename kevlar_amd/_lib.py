@@ -147,6 +147,15 @@ SIGNATURES = {
     'kv_localize_counts': (i32, [vp, vp, u64]),
     'kv_localize_stats': (i32, [vp, vp]),
     'kv_localize_destroy': (i32, [vp]),
+    'kv_varfilter_create': (i32, [vp, vp, u64, vp, vp, vp, u64, vpp]),
+    'kv_varfilter_scan': (i32, [vp, vp, u64, u64]),
+    'kv_varfilter_bad_line': (i32, [vp, u64p]),
+    'kv_varfilter_regions': (i32, [vp, vp, vp, vp, u64]),
+    'kv_varfilter_hits': (i32, [vp, vp, u64]),
+    'kv_varfilter_stats': (i32, [vp, vp]),
+    'kv_varfilter_destroy': (i32, [vp]),
+    'kv_varfilter_plan': (i32, [u64, vp]),
+    'kv_varfilter_chunk_cut': (i32, [vp, u64, i32, u64p]),
     'kv_align_z_bytes': (i32, [u32, u32, u64p]),
     'kv_align_plan': (i32, [vp, vp, u64, u64, vp, vp, u64p]),
     'kv_align_batch': (i32, [vp, vp, u64, vp, vp, u64, vp, u64, i32, i32, i32, i32, u64, vp, vp, vp, vp, u64, u64p]),

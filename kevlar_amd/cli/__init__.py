@@ -1,5 +1,5 @@
 """Command line of the drop-in: `kevlar count | novel | filter | partition | unband | dist | split | augment | localize | assemble |
-alac | call | simlike`.
+alac | call | varfilter | simlike`.
 
 Flag names, defaults and dispatch follow the reference (kevlar/cli/__init__.py:31-108 and
 kevlar/cli/{count,novel,filter,partition,unband,dist}.py); only the subcommands on the
@@ -225,6 +225,12 @@ calling_mains = {
     'simlike': _own_main('simlike'),
 }
 
+# Masking calls against BED regions, between `alac` and `simlike` in the reference's workflow.  A fourth dict, again because tests
+# hold the three above to their exact contents.
+filtering_mains = {
+    'varfilter': _own_main('varfilter'),
+}
+
 subparser_funcs = {
     'augment': _augment,
     'gentrio': _gentrio,
@@ -240,6 +246,7 @@ subparser_funcs = {
     'alac': _own_parser('alac'),
     'call': _own_parser('call'),
     'simlike': _own_parser('simlike'),
+    'varfilter': _own_parser('varfilter'),
 }
 
 
@@ -247,13 +254,13 @@ def parser():
     top = argparse.ArgumentParser(
         prog='kevlar', formatter_class=argparse.RawDescriptionHelpFormatter,
         description='kevlar novel-k-mer discovery and variant calling on AMD MI355X (count, novel, filter, partition, unband, dist, split, '
-        'augment, gentrio, localize, assemble, alac, call, simlike)')
+        'augment, gentrio, localize, assemble, alac, call, varfilter, simlike)')
     top._positionals.title = 'Subcommands'
     top._optionals.title = 'Global arguments'
     top.add_argument('-v', '--version', action='version', version='kevlar v{}'.format(kevlar_amd.__version__))
     top.add_argument('-l', '--logfile', metavar='F', help='write diagnostics to F instead of stderr')
     top.add_argument('--tee', action='store_true', help='write diagnostics to the logfile and to stderr')
-    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(list(mains) + list(downstream_mains) + list(calling_mains))) + '"')
+    sub = top.add_subparsers(dest='cmd', metavar='cmd', help='"' + '", "'.join(sorted(list(mains) + list(downstream_mains) + list(calling_mains) + list(filtering_mains))) + '"')
     for func in subparser_funcs.values():
         func(sub)
     return top
@@ -274,7 +281,7 @@ def run(arglist=None):
     tests pass an argument list."""
     top = parser()
     args = parse_args(arglist)
-    driver = mains.get(args.cmd) or downstream_mains.get(args.cmd) or calling_mains.get(args.cmd)
+    driver = mains.get(args.cmd) or downstream_mains.get(args.cmd) or calling_mains.get(args.cmd) or filtering_mains.get(args.cmd)
     if driver is None:
         top.print_help()
         raise SystemExit(0 if args.cmd is None else 2)
