@@ -676,13 +676,30 @@ int kv_simlike_score(kv_sketch *const *samples, int nsamples, kv_sketch *refr, c
  * kv_assemble_stats: stats_out[0..6] = windows of valid bases, distinct (partition, key) pairs, solid ones, heads (oriented nodes
  * that start a unitig, both strands), unitigs, solid keys on no unitig (cycles without a head), launches.
  * Null arguments, an even K or one outside 13..63, min_count 0, offsets or partition bounds that decrease or do not cover the
- * reads: KV_ERR_ARG before anything touches the device, the outputs untouched.                                                  */
+ * reads: KV_ERR_ARG before anything touches the device, the outputs untouched.
+ * kv_assemble_clean_batch is the same call with the graph cleaned first (rules 3a to 3c), per partition, in
+ * at most clean_rounds rounds, each decided on the graph the round met: a unitig of at most tip_nodes nodes that ends in nothing
+ * and hangs on a node with a stronger successor is removed (a tip), and of the unitigs of at most bubble_nodes nodes that run
+ * between one pair of nodes all but the one of the highest mean count (a bubble's arms); a round that removes nothing is the
+ * last.  tip_nodes = bubble_nodes = 0 is kv_assemble_batch, byte for byte and launch for launch; a limit above 0 with
+ * clean_rounds 0 is KV_ERR_ARG.  The stats are over the cleaned graph ([2] counts the solid keys before cleaning, [5] the live
+ * keys on no unitig).  kv_assemble_clean_stats: clean_out[0..4] = unitigs removed as tips, their keys, unitigs removed as arms,
+ * their keys, removing rounds (summed over launches; a launch runs as many as the partition of it that needs the most).
+ * kv_assemble_clean_plan is kv_assemble_plan for such a call: a launch that cleans takes 12 bytes more per window.              */
 #define KV_ASSEMBLE_NSTATS 7
+#define KV_ASSEMBLE_NCLEAN 5
 typedef struct kv_assembly kv_assembly;
 int kv_assemble_plan(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
                      uint64_t mem_budget, uint64_t *launch_ends, uint64_t *n_launches);
 int kv_assemble_batch(const char *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts,
                       int ksize, uint32_t min_count, uint64_t mem_budget, uint64_t *n_unitigs, uint64_t *n_bases, kv_assembly **out);
+int kv_assemble_clean_plan(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
+                           uint64_t mem_budget, uint32_t tip_nodes, uint32_t bubble_nodes, uint32_t clean_rounds, uint64_t *launch_ends,
+                           uint64_t *n_launches);
+int kv_assemble_clean_batch(const char *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts,
+                            int ksize, uint32_t min_count, uint64_t mem_budget, uint32_t tip_nodes, uint32_t bubble_nodes,
+                            uint32_t clean_rounds, uint64_t *n_unitigs, uint64_t *n_bases, kv_assembly **out);
+int kv_assemble_clean_stats(kv_assembly *h, uint64_t *clean_out);
 int kv_assemble_fetch(kv_assembly *h, char *bases_out, uint64_t *offsets_out, uint32_t *part_out, uint32_t *count_out);
 int kv_assemble_stats(kv_assembly *h, uint64_t *stats_out);
 int kv_assemble_destroy(kv_assembly *h);

@@ -164,6 +164,9 @@ SIGNATURES = {
     'kv_simlike_score': (i32, [vpp, i32, vp, vp, vp, vp, vp, u64, i32, f64, f64, f64, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     'kv_assemble_plan': (i32, [vp, u64, vp, u64, i32, u64, vp, u64p]),
     'kv_assemble_batch': (i32, [vp, vp, u64, vp, u64, i32, u32, u64, u64p, u64p, vpp]),
+    'kv_assemble_clean_plan': (i32, [vp, u64, vp, u64, i32, u64, u32, u32, u32, vp, u64p]),
+    'kv_assemble_clean_batch': (i32, [vp, vp, u64, vp, u64, i32, u32, u64, u32, u32, u32, u64p, u64p, vpp]),
+    'kv_assemble_clean_stats': (i32, [vp, vp]),
     'kv_assemble_fetch': (i32, [vp, vp, vp, vp, vp]),
     'kv_assemble_stats': (i32, [vp, vp]),
     'kv_assemble_destroy': (i32, [vp]),

@@ -11,7 +11,7 @@ import sys
 
 import kevlar_amd
 from kevlar_amd import khmer
-from kevlar_amd.assemble import DEFAULT_KSIZE, DEFAULT_MIN_COUNT, assemble
+from kevlar_amd.assemble import DEFAULT_CLEAN_ROUNDS, DEFAULT_KSIZE, DEFAULT_MIN_COUNT, add_clean_arguments, assemble, clean_settings
 from kevlar_amd.call import call_partitions
 from kevlar_amd.khmer import _buckets_per_byte
 from kevlar_amd.localize import DEFAULT_MAX_OCC, localize
@@ -25,9 +25,11 @@ def _partition_order(partid):
 
 def alac(pstream, refrfile, threads=1, ksize=31, maxreads=10000, delta=50, seedsize=31, maxdiff=None, inclpattern=None,
          exclpattern=None, match=1, mismatch=2, gapopen=5, gapextend=0, min_ikmers=None, maskfile=None, maskmem=1e6,
-         maskmaxfpr=0.01, maxtargetlen=10000, asmk=DEFAULT_KSIZE, mincount=DEFAULT_MIN_COUNT, maxocc=DEFAULT_MAX_OCC):
+         maskmaxfpr=0.01, maxtargetlen=10000, asmk=DEFAULT_KSIZE, mincount=DEFAULT_MIN_COUNT, maxocc=DEFAULT_MAX_OCC,
+         tip_nodes=0, bubble_nodes=0, clean_rounds=DEFAULT_CLEAN_ROUNDS):
     contigs_by_partition = defaultdict(list)
-    for partid, contig in assemble(pstream, maxreads=maxreads, ksize=asmk, min_count=mincount):
+    for partid, contig in assemble(pstream, maxreads=maxreads, ksize=asmk, min_count=mincount, tip_nodes=tip_nodes,
+                                   bubble_nodes=bubble_nodes, clean_rounds=clean_rounds):
         contigs_by_partition[partid].append(contig)
 
     targets_by_partition = defaultdict(list)
@@ -58,8 +60,8 @@ def alac(pstream, refrfile, threads=1, ksize=31, maxreads=10000, delta=50, seeds
 
 
 def parser():
-    """the reference's `kevlar alac` flags and defaults (kevlar/cli/alac.py), plus the two parameters of the assembly rule and
-    localize's --max-occ"""
+    """the reference's `kevlar alac` flags and defaults (kevlar/cli/alac.py), plus the two parameters of the assembly rule, its
+    cleaning options and localize's --max-occ"""
     parser = argparse.ArgumentParser(prog='python -m kevlar_amd.alac', add_help=False, description='Assemble partitioned reads, '
                                      'localize to the reference genome, align the assembled contig to the reference, and call variants.')
     parser._positionals.title = 'Required inputs'
@@ -71,6 +73,7 @@ def parser():
                             help='K-mer size of the assembly graph, odd, 13..63 (default: 31)')
     asmbl_args.add_argument('--min-count', type=int, metavar='C', default=DEFAULT_MIN_COUNT,
                             help='a K-mer seen fewer than C times in its partition is left out of the graph (default: 2)')
+    add_clean_arguments(asmbl_args)
     local_args = parser.add_argument_group('Target extraction')
     local_args.add_argument('-z', '--seed-size', type=int, default=51, metavar='Z', help='seed size; default is 51')
     local_args.add_argument('-d', '--delta', type=int, default=50, metavar='D',
@@ -114,11 +117,13 @@ def main(args):
     else:
         pstream = kevlar_amd.parse_partitioned_reads(readstream)
     outstream = kevlar_amd.open(args.out, 'w')
+    tip_nodes, bubble_nodes, clean_rounds = clean_settings(args)
     workflow = alac(
         pstream, args.refr, threads=args.threads, ksize=args.ksize, maxreads=args.max_reads, delta=args.delta, seedsize=args.seed_size,
         maxdiff=args.max_diff, inclpattern=args.include, exclpattern=args.exclude, match=args.match, mismatch=args.mismatch,
         gapopen=args.open, gapextend=args.extend, min_ikmers=args.min_ikmers, maskfile=args.gen_mask, maskmem=args.mask_mem,
-        maskmaxfpr=args.mask_max_fpr, maxtargetlen=args.max_target_length, asmk=args.asm_k, mincount=args.min_count, maxocc=args.max_occ)
+        maskmaxfpr=args.mask_max_fpr, maxtargetlen=args.max_target_length, asmk=args.asm_k, mincount=args.min_count, maxocc=args.max_occ,
+        tip_nodes=tip_nodes, bubble_nodes=bubble_nodes, clean_rounds=clean_rounds)
     writer = VCFWriter(outstream, source='kevlar::alac', refr=args.refr)
     writer.write_header()
     for varcall in workflow:

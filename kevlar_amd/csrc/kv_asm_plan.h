@@ -1,5 +1,6 @@
 // kv_asm_plan.h -- the host rules of the batched assembly (kv_assemble.hip), free of HIP: what a batch of partitions must satisfy,
-// how many windows, runs and table slots it has, the launch grids, and where a call is cut into launches under a memory budget.
+// how many windows, runs and table slots it has, the launch grids, and where a call is cut into launches under a memory budget
+// (with the bytes of the cleaning rounds when a call cleans: tests/harness/asm_clean_plan_host.cpp).
 // A launch holds whole partitions: a K-mer of one partition says nothing about the same K-mer of another, so nothing crosses a
 // cut.  Plain C++17: tests/harness/asm_plan_host.cpp compiles it for the host, tests/test_assemble_reference.py checks the edges.
 #pragma once
@@ -19,6 +20,8 @@
 #define ASM_MAX_WINDOWS 0x3FFFFFF0ull       // per launch: window ids and 2 * id + strand are 32-bit
 #define ASM_BYTES_PER_WINDOW(W) (8ull * (W) + 16ull)   // key; owner, partition, count, degree mask + flags
 #define ASM_BYTES_PER_CHUNK 12ull                      // per ASM_THREADS windows: heads, heads in front
+#define ASM_CLEAN_BYTES_PER_WINDOW 12ull               // cleaning (rules 3a-3c): head index of either strand, liveness
+#define ASM_DEFAULT_CLEAN_ROUNDS 8
 
 struct AsmLaunch {
     uint64_t part0, part1;                  // partitions [part0, part1)
@@ -40,10 +43,18 @@ static inline uint64_t asm_table_cap(uint64_t n_windows)
     return c;
 }
 static inline unsigned asm_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + ASM_THREADS - 1) / ASM_THREADS, ASM_MAX_GRID)); }
-static inline uint64_t asm_launch_bytes(uint64_t n_windows, uint64_t n_bases, uint64_t n_reads, int ksize)
+static inline uint64_t asm_launch_bytes(uint64_t n_windows, uint64_t n_bases, uint64_t n_reads, int ksize, bool cleaning = false)
 {
-    return n_windows * ASM_BYTES_PER_WINDOW(asm_words(ksize)) + (asm_chunks(n_windows) + 1) * ASM_BYTES_PER_CHUNK + 8 * asm_table_cap(n_windows) +
-           n_bases + 32 * (n_reads + 1);
+    return n_windows * (ASM_BYTES_PER_WINDOW(asm_words(ksize)) + (cleaning ? ASM_CLEAN_BYTES_PER_WINDOW : 0)) +
+           (asm_chunks(n_windows) + 1) * ASM_BYTES_PER_CHUNK + 8 * asm_table_cap(n_windows) + n_bases + 32 * (n_reads + 1);
+}
+// limits 0, 0 mean no cleaning, and then the number of rounds says nothing
+static inline bool asm_cleaning(uint32_t tip_nodes, uint32_t bubble_nodes) { return tip_nodes != 0 || bubble_nodes != 0; }
+static inline int asm_check_clean(uint32_t tip_nodes, uint32_t bubble_nodes, uint32_t clean_rounds)
+{
+    KV_REQUIRE(!asm_cleaning(tip_nodes, bubble_nodes) || clean_rounds >= 1, KV_ERR_ARG,
+               "kv_assemble_clean_batch: clean_rounds must be at least 1 (tip_nodes %u, bubble_nodes %u)", tip_nodes, bubble_nodes);
+    return KV_OK;
 }
 
 static inline int asm_check_args(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
@@ -65,7 +76,7 @@ static inline int asm_check_args(const uint64_t *read_off, uint64_t n_reads, con
 
 // a launch takes partitions until the next one would pass the budget; a partition that alone passes it is refused
 static inline int asm_plan(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
-                           uint64_t mem_budget, std::vector<AsmLaunch> &launches)
+                           uint64_t mem_budget, std::vector<AsmLaunch> &launches, bool cleaning = false)
 {
     launches.clear();
     AsmLaunch cur = AsmLaunch();
@@ -76,12 +87,12 @@ static inline int asm_plan(const uint64_t *read_off, uint64_t n_reads, const uin
             runs += asm_read_runs(read_off[r + 1] - read_off[r], ksize);
         }
         const uint64_t bases = read_off[part_first[p + 1]] - read_off[part_first[p]], reads = part_first[p + 1] - part_first[p];
-        const uint64_t alone = asm_launch_bytes(win, bases, reads, ksize);
+        const uint64_t alone = asm_launch_bytes(win, bases, reads, ksize, cleaning);
         KV_REQUIRE(alone <= mem_budget && win <= ASM_MAX_WINDOWS, KV_ERR_CAPACITY,
                    "partition %llu (%llu reads, %llu windows) needs %llu bytes, the budget is %llu", (unsigned long long)p,
                    (unsigned long long)reads, (unsigned long long)win, (unsigned long long)alone, (unsigned long long)mem_budget);
         const bool open = cur.part1 > cur.part0;
-        if (open && (asm_launch_bytes(cur.n_windows + win, cur.n_bases + bases, cur.read1 - cur.read0 + reads, ksize) > mem_budget ||
+        if (open && (asm_launch_bytes(cur.n_windows + win, cur.n_bases + bases, cur.read1 - cur.read0 + reads, ksize, cleaning) > mem_budget ||
                      cur.n_windows + win > ASM_MAX_WINDOWS)) {
             launches.push_back(cur);
             cur = AsmLaunch();
@@ -94,7 +105,7 @@ static inline int asm_plan(const uint64_t *read_off, uint64_t n_reads, const uin
     if (cur.part1 > cur.part0) launches.push_back(cur);
     for (AsmLaunch &l : launches) {
         l.table_cap = asm_table_cap(l.n_windows);
-        l.bytes = asm_launch_bytes(l.n_windows, l.n_bases, l.read1 - l.read0, ksize);
+        l.bytes = asm_launch_bytes(l.n_windows, l.n_bases, l.read1 - l.read0, ksize, cleaning);
     }
     return KV_OK;
 }

@@ -13,6 +13,11 @@
 //       a prefix sum over the kept lengths gives exact offsets and the second walk writes the bases.
 // A walk from a head cannot loop (entering a cycle takes a node with two predecessors); the guard of 2 * windows + 2 steps per
 // partition only bounds a walk over damaged memory.  A component of simple edges alone is a cycle without a head: no output, counted.
+// Cleaning (rules 3a to 3c, kv_assemble_clean_batch with a limit above 0) runs rounds in front of (3): every round computes degrees
+// and heads of the LIVE keys, a lane per head measures its unitig (k_asm_measure), a lane per head decides whether it is a tip or
+// a beaten bubble arm from those records alone (k_asm_decide), and a LATER launch marks the keys of the flagged unitigs dead
+// (k_asm_kill): nothing that walks or probes liveness runs beside the marking, so a round's answer does not depend on scheduling.
+// Liveness is a word of its own: the counts stay what the reads gave.
 #include <algorithm>
 #include <vector>
 
@@ -43,7 +48,8 @@ struct AsmDev {
     const uint64_t *hbase;                  // per chunk: heads in front
     unsigned long long *table;
     uint64_t capmask;
-    unsigned long long *ctr;                // [0] valid windows [1] distinct [2] solid [3] unitigs [4] solid keys on a unitig
+    unsigned long long *ctr;                // [0] valid windows [1] distinct [2] solid [3] unitigs [4] live keys on a unitig
+                                            // [5] tips removed [6] their keys [7] arms removed [8] their keys [9] = [6] + [8]
     uint32_t *pcount;                       // per partition: unitigs
     uint64_t n_heads;
     uint32_t *heads, *klen, *kflag;         // per head: 2 * window + strand; bases if kept, else 0; kept
@@ -53,7 +59,18 @@ struct AsmDev {
     uint32_t *upart;
     uint64_t out_base;
     uint32_t part0;
+    // cleaning; dead is null without it
+    uint32_t *dead;                         // per window: 1 once the key it owns was removed
+    uint32_t *hinv;                         // per 2 * window + strand of a head: its index in heads
+    uint32_t count_pass;                    // k_asm_degree adds to ctr[1] and ctr[2]: the first degree pass of a launch only
+    uint32_t tip_nodes, bubble_nodes;
+    uint32_t *rm, *rpq, *rlast, *rpcode, *rqcode, *rflag;   // per head: nodes; P | Q << 4 (masks by base); last node, the one node of P,
+    uint64_t *rsum;                                         // the one node of Q as 2 * window + strand or ASM_EMPTY32; verdict; sum of counts
 };
+#define ASM_CTR_BYTES 128
+#define ASM_FLAG_TIP 1u
+#define ASM_FLAG_ARM 2u
+#define ASM_FLAG_MARKS 4u                   // of a unitig's two heads the one that counts it and marks its keys
 
 template <int W>
 __device__ __forceinline__ uint64_t asm_hash(const uint64_t *key, uint32_t part)
@@ -150,6 +167,25 @@ __device__ __forceinline__ uint32_t asm_find_solid(const AsmDev &d, const LocRol
     return (id != ASM_EMPTY32 && d.cnt[id] >= d.min_count) ? id : ASM_EMPTY32;
 }
 
+// ... that no earlier round of the cleaning removed (CLEAN = 1; without cleaning every solid key is live).  k_asm_degree alone asks
+// this: heads and walks follow its masks, which say where a live node is, so they never read liveness and the count is all they check
+template <int W, int CLEAN>
+__device__ __forceinline__ bool asm_is_live(const AsmDev &d, const LocRoll<W> &roll, uint32_t part)
+{
+    uint32_t strand;
+    const uint32_t id = asm_find_solid<W>(d, roll, part, strand);
+    return id != ASM_EMPTY32 && !(CLEAN && d.dead[id]);
+}
+
+// the key of the rolled window where a degree mask of this round says it is live: no look at the count or at liveness
+template <int W>
+__device__ __forceinline__ uint32_t asm_find_node(const AsmDev &d, const LocRoll<W> &roll, uint32_t part, uint32_t &strand)
+{
+    uint64_t key[W];
+    strand = asm_canonical<W>(roll, key);
+    return asm_find<W>(d, key, part);
+}
+
 // ---- keys and counts --------------------------------------------------------------------------------------------------------
 // run t of the launch: read r with cpre[r] <= t < cpre[r + 1], windows (t - cpre[r]) * ASM_RUN .. of it
 template <int W>
@@ -222,7 +258,8 @@ __global__ __launch_bounds__(ASM_THREADS) void k_asm_group(AsmDev d)
 }
 
 // ---- degrees ----------------------------------------------------------------------------------------------------------------
-template <int W>
+// CLEAN = 0 is the kernel of a call that does not clean: no liveness test, the registers it had before there was cleaning
+template <int W, int CLEAN>
 __global__ __launch_bounds__(ASM_THREADS) void k_asm_degree(AsmDev d)
 {
     const int K = d.K, topbits = 2 * K - 64 * (W - 1);
@@ -232,23 +269,24 @@ __global__ __launch_bounds__(ASM_THREADS) void k_asm_degree(AsmDev d)
         ++n_distinct;
         if (d.cnt[a] < d.min_count) continue;
         ++n_solid;
+        if (CLEAN && d.dead[a]) { d.info[a] = 0; continue; }           // removed in an earlier round: no node
         const uint32_t part = d.wpart[a];
         LocRoll<W> node;
         asm_load<W>(node, d.keys + a * W, K, topbits, 0);
-        uint32_t mask = 0, strand;
+        uint32_t mask = 0;
         for (uint32_t b = 0; b < 4; ++b) {
             LocRoll<W> t = node;
             t.push(b, topbits);
-            if (asm_find_solid<W>(d, t, part, strand) != ASM_EMPTY32) mask |= 1u << b;
+            if (asm_is_live<W, CLEAN>(d, t, part)) mask |= 1u << b;
             t = node;
             asm_push_front<W>(t, b, topbits);
-            if (asm_find_solid<W>(d, t, part, strand) != ASM_EMPTY32) mask |= 16u << b;
+            if (asm_is_live<W, CLEAN>(d, t, part)) mask |= 16u << b;
         }
         d.info[a] = ASM_SOLID | mask;
     }
     n_distinct = wave_sum_u64(n_distinct);
     n_solid = wave_sum_u64(n_solid);
-    if ((threadIdx.x & 63u) == 0) {
+    if ((threadIdx.x & 63u) == 0 && (!CLEAN || d.count_pass)) {
         if (n_distinct) atomicAdd(&d.ctr[1], (unsigned long long)n_distinct);
         if (n_solid) atomicAdd(&d.ctr[2], (unsigned long long)n_solid);
     }
@@ -309,6 +347,10 @@ __global__ __launch_bounds__(ASM_THREADS) void k_asm_compact(AsmDev d)
         if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
         __syncthreads();
         uint64_t at = d.hbase[chunk] + waves_before(wsum, threadIdx.x >> 6) + incl - mine;
+        if (d.hinv) {
+            if (info & ASM_HEAD0) d.hinv[2 * a] = (uint32_t)at;
+            if (info & ASM_HEAD1) d.hinv[2 * a + 1] = (uint32_t)(at + ((info & ASM_HEAD0) ? 1u : 0u));
+        }
         if (info & ASM_HEAD0) d.heads[at++] = 2u * (uint32_t)a;
         if (info & ASM_HEAD1) d.heads[at] = 2u * (uint32_t)a + 1u;
         __syncthreads();
@@ -384,6 +426,167 @@ __global__ __launch_bounds__(ASM_THREADS) void k_asm_walk(AsmDev d)
     }
 }
 
+// ---- cleaning: measure, decide, apply -------------------------------------------------------------------------------------------
+// a lane per head: the record of its unitig on this round's graph
+template <int W>
+__global__ __launch_bounds__(ASM_THREADS) void k_asm_measure(AsmDev d)
+{
+    const int K = d.K, topbits = 2 * K - 64 * (W - 1);
+    for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < d.n_heads; h += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t a = d.heads[h] >> 1, strand0 = d.heads[h] & 1u;
+        const uint32_t part = d.wpart[a];
+        LocRoll<W> node;
+        asm_load<W>(node, d.keys + (uint64_t)a * W, K, topbits, strand0);
+        uint32_t m = asm_orient(d.info[a], strand0), strand;
+        const uint32_t pm = m >> 4;
+        uint32_t pcode = ASM_EMPTY32, qcode = ASM_EMPTY32, last = d.heads[h];
+        if (__popc(pm) == 1) {
+            LocRoll<W> v = node;
+            asm_push_front<W>(v, (uint32_t)__ffs(pm) - 1u, topbits);
+            const uint32_t id = asm_find_node<W>(d, v, part, strand);
+            if (id != ASM_EMPTY32) pcode = 2u * id + strand;
+        }
+        uint64_t sum = d.cnt[a];
+        const uint32_t guard = d.guard[part];
+        uint32_t steps = 0;
+        while (steps < guard) {
+            const uint32_t sm = m & 15u;
+            if (__popc(sm) != 1) break;
+            LocRoll<W> next = node;
+            next.push((uint32_t)__ffs(sm) - 1u, topbits);
+            const uint32_t id = asm_find_node<W>(d, next, part, strand);
+            if (id == ASM_EMPTY32) break;               // (the mask says it is there)
+            qcode = 2u * id + strand;                   // the one node of Q, if the walk ends here
+            const uint32_t m2 = asm_orient(d.info[id], strand);
+            if (__popc(m2 >> 4) != 1) break;
+            node = next;
+            m = m2;
+            ++steps;
+            sum += d.cnt[id];
+            last = qcode;
+            qcode = ASM_EMPTY32;
+        }
+        d.rm[h] = steps + 1u;
+        d.rsum[h] = sum;
+        d.rpq[h] = pm | ((m & 15u) << 4);
+        d.rlast[h] = last;
+        d.rpcode[h] = pcode;
+        d.rqcode[h] = qcode;
+    }
+}
+
+// is the canonical key that window x owns smaller than the one y owns?
+template <int W>
+__device__ __forceinline__ bool asm_key_less(const AsmDev &d, uint32_t x, uint32_t y)
+{
+    const uint64_t *kx = d.keys + (uint64_t)x * W, *ky = d.keys + (uint64_t)y * W;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+        if (kx[w] != ky[w]) return kx[w] < ky[w];
+    return false;
+}
+
+// id(U): the window that owns the smaller canonical key of the first and the last node
+template <int W>
+__device__ __forceinline__ uint32_t asm_unit_id(const AsmDev &d, uint64_t h)
+{
+    const uint32_t first = d.heads[h] >> 1, last = d.rlast[h] >> 1;
+    return asm_key_less<W>(d, last, first) ? last : first;
+}
+
+// a lane per head: rules 3a and 3b from the records of this round, which nothing changes while this runs
+template <int W>
+__global__ __launch_bounds__(ASM_THREADS) void k_asm_decide(AsmDev d)
+{
+    const int K = d.K, topbits = 2 * K - 64 * (W - 1);
+    uint64_t n_tips = 0, n_tip_keys = 0, n_arms = 0, n_arm_keys = 0;
+    for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < d.n_heads; h += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t code = d.heads[h], a = code >> 1, m = d.rm[h], pq = d.rpq[h], pcode = d.rpcode[h];
+        const uint32_t qn = (uint32_t)__popc(pq >> 4);
+        const bool tip = qn == 0 && m <= d.tip_nodes, arm = qn == 1 && m <= d.bubble_nodes && d.rqcode[h] != ASM_EMPTY32;
+        uint32_t flag = 0;
+        if (__popc(pq & 15u) == 1 && pcode != ASM_EMPTY32 && (tip || arm)) {
+            const uint32_t part = d.wpart[a], other = d.rlast[h] ^ 1u;      // the head of the reverse complement of this unitig
+            const uint32_t jid = pcode >> 1, jstrand = pcode & 1u;
+            const uint32_t sm = asm_orient(d.info[jid], jstrand) & 15u;
+            LocRoll<W> j;
+            asm_load<W>(j, d.keys + (uint64_t)jid * W, K, topbits, jstrand);
+            const uint64_t S = d.rsum[h];
+            for (uint32_t b = 0; b < 4; ++b) {
+                if (!((sm >> b) & 1u)) continue;
+                LocRoll<W> s = j;
+                s.push(b, topbits);
+                uint32_t strand;
+                const uint32_t sid = asm_find_node<W>(d, s, part, strand);
+                if (sid == ASM_EMPTY32) continue;       // (the mask says it is there)
+                const uint32_t scode = 2u * sid + strand;
+                if (scode == code) continue;
+                if (tip) {
+                    const uint32_t cs = d.cnt[sid], c1 = d.cnt[a];
+                    if (cs > c1 || (cs == c1 && asm_key_less<W>(d, sid, a))) flag = ASM_FLAG_TIP;
+                    continue;
+                }
+                if (scode == other) continue;           // its own reverse complement, from a to rc(a), is no rival
+                const uint64_t hv = d.hinv[scode];      // a successor of a node with two is a head
+                if (hv >= d.n_heads || d.heads[hv] != scode) continue;
+                const uint32_t mv = d.rm[hv], pqv = d.rpq[hv];
+                if (mv > d.bubble_nodes || __popc(pqv & 15u) != 1 || __popc(pqv >> 4) != 1 || d.rqcode[hv] != d.rqcode[h]) continue;
+                const uint64_t lhs = d.rsum[hv] * (uint64_t)m, rhs = S * (uint64_t)mv;
+                bool beaten;
+                if (lhs != rhs) beaten = lhs > rhs;
+                else if (mv != m) beaten = mv > m;
+                else beaten = asm_key_less<W>(d, asm_unit_id<W>(d, hv), asm_unit_id<W>(d, h));
+                if (beaten) flag = ASM_FLAG_ARM;
+            }
+        }
+        // a tip is one in one orientation only; an arm in both, and the head with the smaller code counts it (one head: both)
+        if (flag == ASM_FLAG_TIP) { flag |= ASM_FLAG_MARKS; ++n_tips; n_tip_keys += m; }
+        if (flag == ASM_FLAG_ARM && code <= (d.rlast[h] ^ 1u)) {
+            flag |= ASM_FLAG_MARKS;
+            ++n_arms;
+            n_arm_keys += code == (d.rlast[h] ^ 1u) ? m / 2u : m;       // its own reverse complement: every key is on it twice
+        }
+        d.rflag[h] = flag;
+    }
+    n_tips = wave_sum_u64(n_tips);
+    n_tip_keys = wave_sum_u64(n_tip_keys);
+    n_arms = wave_sum_u64(n_arms);
+    n_arm_keys = wave_sum_u64(n_arm_keys);
+    if ((threadIdx.x & 63u) == 0 && (n_tips | n_arms)) {
+        atomicAdd(&d.ctr[5], (unsigned long long)n_tips);
+        atomicAdd(&d.ctr[6], (unsigned long long)n_tip_keys);
+        atomicAdd(&d.ctr[7], (unsigned long long)n_arms);
+        atomicAdd(&d.ctr[8], (unsigned long long)n_arm_keys);
+        atomicAdd(&d.ctr[9], (unsigned long long)(n_tip_keys + n_arm_keys));
+    }
+}
+
+// a lane per flagged unitig: its keys are dead from the next round on.  Reads masks and records only, never liveness.
+template <int W>
+__global__ __launch_bounds__(ASM_THREADS) void k_asm_kill(AsmDev d)
+{
+    const int K = d.K, topbits = 2 * K - 64 * (W - 1);
+    for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < d.n_heads; h += (uint64_t)gridDim.x * blockDim.x) {
+        if (!(d.rflag[h] & ASM_FLAG_MARKS)) continue;
+        const uint32_t a = d.heads[h] >> 1, strand0 = d.heads[h] & 1u;
+        const uint32_t part = d.wpart[a], nodes = d.rm[h];
+        LocRoll<W> node;
+        asm_load<W>(node, d.keys + (uint64_t)a * W, K, topbits, strand0);
+        uint32_t m = asm_orient(d.info[a], strand0);
+        d.dead[a] = 1u;
+        for (uint32_t i = 1; i < nodes; ++i) {
+            const uint32_t sm = m & 15u;
+            if (__popc(sm) != 1) break;                 // (the record says there are `nodes`)
+            node.push((uint32_t)__ffs(sm) - 1u, topbits);
+            uint32_t strand;
+            const uint32_t id = asm_find_node<W>(d, node, part, strand);
+            if (id == ASM_EMPTY32) break;
+            d.dead[id] = 1u;
+            m = asm_orient(d.info[id], strand);
+        }
+    }
+}
+
 }  // namespace
 
 // a stream's working memory, kept between calls (grow-only; kv_scratch_trim gives it back): gigabytes at 20 000 partitions a call,
@@ -402,13 +605,78 @@ struct kv_assembly {
     std::vector<uint64_t> off;              // n_unitigs + 1
     std::vector<uint32_t> part, count;      // per unitig; per partition
     uint64_t stats[KV_ASSEMBLE_NSTATS] = {0, 0, 0, 0, 0, 0, 0};
+    uint64_t clean[KV_ASSEMBLE_NCLEAN] = {0, 0, 0, 0, 0};
 };
 
 namespace {
 
+// degrees and heads of the live keys, the chunks' head counts summed: how many heads there are
 template <int W>
-int asm_launch(const AsmLaunch &L, AsmDev d, hipStream_t st, const char *bases, const uint64_t *read_off, const uint64_t *part_first, kv_assembly *res)
+int asm_count_heads(const AsmDev &d, uint64_t nw, uint64_t n_chunks, uint64_t *d_hbase, hipStream_t st, uint64_t *n_heads)
 {
+    const dim3 block(ASM_THREADS);
+    {
+        KvProfScope prof("k_asm_degree");
+        if (d.dead) hipLaunchKernelGGL((k_asm_degree<W, 1>), dim3(asm_grid(nw)), block, 0, st, d);
+        else hipLaunchKernelGGL((k_asm_degree<W, 0>), dim3(asm_grid(nw)), block, 0, st, d);
+    }
+    { KvProfScope prof("k_asm_heads"); hipLaunchKernelGGL(k_asm_heads<W>, dim3(asm_grid(nw)), block, 0, st, d); }
+    KV_HIP(hipGetLastError());
+    { KvProfScope prof("k_asm_scan"); kv_excl_scan_launch(d.ccount, (uint32_t)n_chunks, d_hbase, st); }
+    KV_HIP(hipGetLastError());
+    hipError_t re = hipSuccess;
+    KvReadback rb;
+    const uint64_t *got = rb.add((const uint64_t *)d_hbase + n_chunks, 1, st, &re);
+    KV_HIP(re);
+    KV_HIP(rb.wait(st));
+    *n_heads = *got;
+    KV_REQUIRE(*n_heads < 0xFFFFFFF0ull, KV_ERR_CAPACITY, "too many unitig heads in one launch (%llu)", (unsigned long long)*n_heads);
+    return KV_OK;
+}
+
+// rules 3a to 3c: rounds of measure, decide and -- in a launch of its own -- apply, until one removes nothing.  *final_heads is
+// set, to the number of heads, when the last round removed nothing: its degrees, heads and chunk sums are those of the final graph
+template <int W>
+int asm_clean_rounds(AsmDev &d, AsmScratch &scratch, uint64_t nw, uint64_t n_chunks, uint64_t *d_hbase, uint32_t clean_rounds, hipStream_t st,
+                     uint64_t *removing_rounds, uint64_t *final_heads)
+{
+    const dim3 block(ASM_THREADS);
+    uint64_t removed = 0;
+    for (uint32_t round = 0; round < clean_rounds; ++round) {
+        uint64_t n_heads = 0;
+        KV_STEP(asm_count_heads<W>(d, nw, n_chunks, d_hbase, st, &n_heads));
+        d.count_pass = 0;
+        if (!n_heads) { *final_heads = 0; break; }      // (cycles alone: nothing to remove)
+        const size_t hs[8] = {n_heads * 4, n_heads * 4, n_heads * 4, n_heads * 4, n_heads * 4, n_heads * 4, n_heads * 4, n_heads * 8};
+        KvCarve<8> hc(hs);
+        const hipError_t e = hc.from(scratch.heads);
+        KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "assembly head record allocation failed: %s", hipGetErrorString(e));
+        d.n_heads = n_heads;
+        d.heads = hc.at<uint32_t>(0); d.rm = hc.at<uint32_t>(1); d.rpq = hc.at<uint32_t>(2); d.rlast = hc.at<uint32_t>(3);
+        d.rpcode = hc.at<uint32_t>(4); d.rqcode = hc.at<uint32_t>(5); d.rflag = hc.at<uint32_t>(6); d.rsum = hc.at<uint64_t>(7);
+        hipLaunchKernelGGL(k_asm_compact, dim3(asm_grid(nw)), block, 0, st, d);
+        { KvProfScope prof("k_asm_measure"); hipLaunchKernelGGL(k_asm_measure<W>, dim3(asm_grid(n_heads)), block, 0, st, d); }
+        { KvProfScope prof("k_asm_decide"); hipLaunchKernelGGL(k_asm_decide<W>, dim3(asm_grid(n_heads)), block, 0, st, d); }
+        KV_HIP(hipGetLastError());
+        hipError_t re = hipSuccess;
+        KvReadback rb;
+        const uint64_t *got = rb.add((const uint64_t *)d.ctr + 9, 1, st, &re);     // keys removed so far: 8 bytes a round
+        KV_HIP(re);
+        KV_HIP(rb.wait(st));
+        if (*got == removed) { *final_heads = n_heads; break; }
+        removed = *got;
+        ++*removing_rounds;
+        { KvProfScope prof("k_asm_kill"); hipLaunchKernelGGL(k_asm_kill<W>, dim3(asm_grid(n_heads)), block, 0, st, d); }
+        KV_HIP(hipGetLastError());
+    }
+    return KV_OK;
+}
+
+template <int W>
+int asm_launch(const AsmLaunch &L, AsmDev d, hipStream_t st, const char *bases, const uint64_t *read_off, const uint64_t *part_first,
+               uint32_t clean_rounds, kv_assembly *res)
+{
+    const bool cleaning = asm_cleaning(d.tip_nodes, d.bubble_nodes);
     const uint64_t nr = L.read1 - L.read0, np = L.part1 - L.part0, nw = L.n_windows, n_chunks = asm_chunks(nw);
     // the host's view of the launch: everything counted from its first read and first partition
     std::vector<uint64_t> roff(nr + 1), wpre(nr + 1), cpre(nr + 1);
@@ -427,9 +695,10 @@ int asm_launch(const AsmLaunch &L, AsmDev d, hipStream_t st, const char *bases, 
         guard[p] = (uint32_t)(2 * (wpre[r1] - wpre[r0]) + 2);
     }
     roff[nr] = L.n_bases;
-    const size_t sizes[15] = {L.n_bases + 16, (nr + 1) * 8, (nr + 1) * 8, (nr + 1) * 8, (nr + 1) * 4, (np + 1) * 4, (np + 1) * 4,
-                              nw * W * 8, nw * 4, nw * 4, nw * 4, nw * 4, (n_chunks + 1) * 4, (n_chunks + 1) * 8, 64};
-    KvCarve<15> c(sizes);
+    const size_t sizes[17] = {L.n_bases + 16, (nr + 1) * 8, (nr + 1) * 8, (nr + 1) * 8, (nr + 1) * 4, (np + 1) * 4, (np + 1) * 4,
+                              nw * W * 8, nw * 4, nw * 4, nw * 4, nw * 4, (n_chunks + 1) * 4, (n_chunks + 1) * 8, ASM_CTR_BYTES,
+                              cleaning ? nw * 4 : 0, cleaning ? nw * 8 : 0};
+    KvCarve<17> c(sizes);
     AsmScratch &scratch = g_asm_scratch.get(st);
     hipError_t e = c.from(scratch.main);
     if (e == hipSuccess) e = scratch.table.need(L.table_cap * 8);
@@ -454,25 +723,21 @@ int asm_launch(const AsmLaunch &L, AsmDev d, hipStream_t st, const char *bases, 
     KV_HIP(hipMemsetAsync(d.pcount, 0, (np + 1) * 4, st));
     KV_HIP(hipMemsetAsync(d.cnt, 0, c.off[12] - c.off[10], st));        // counts and masks
     KV_HIP(hipMemsetAsync(d.table, 0xFF, L.table_cap * 8, st));
-    KV_HIP(hipMemsetAsync(d.ctr, 0, 64, st));
+    KV_HIP(hipMemsetAsync(d.ctr, 0, ASM_CTR_BYTES, st));
+    d.count_pass = 1;
+    d.dead = nullptr; d.hinv = nullptr;
+    if (cleaning) {
+        d.dead = c.at<uint32_t>(15); d.hinv = c.at<uint32_t>(16);
+        KV_HIP(hipMemsetAsync(d.dead, 0, nw * 4, st));
+    }
     const dim3 block(ASM_THREADS);
     { KvProfScope prof("k_asm_keys"); hipLaunchKernelGGL(k_asm_keys<W>, dim3(asm_grid(L.n_runs)), block, 0, st, d); }
     { KvProfScope prof("k_asm_group"); hipLaunchKernelGGL(k_asm_group<W>, dim3(asm_grid(nw)), block, 0, st, d); }
-    { KvProfScope prof("k_asm_degree"); hipLaunchKernelGGL(k_asm_degree<W>, dim3(asm_grid(nw)), block, 0, st, d); }
-    { KvProfScope prof("k_asm_heads"); hipLaunchKernelGGL(k_asm_heads<W>, dim3(asm_grid(nw)), block, 0, st, d); }
-    KV_HIP(hipGetLastError());
-    { KvProfScope prof("k_asm_scan"); kv_excl_scan_launch(d.ccount, (uint32_t)n_chunks, d_hbase, st); }
-    KV_HIP(hipGetLastError());
-    uint64_t n_heads = 0;
-    {
-        hipError_t re = hipSuccess;
-        KvReadback rb;
-        const uint64_t *got = rb.add((const uint64_t *)d_hbase + n_chunks, 1, st, &re);
-        KV_HIP(re);
-        KV_HIP(rb.wait(st));
-        n_heads = *got;
-    }
-    KV_REQUIRE(n_heads < 0xFFFFFFF0ull, KV_ERR_CAPACITY, "too many unitig heads in one launch (%llu)", (unsigned long long)n_heads);
+    uint64_t removing_rounds = 0;
+    uint64_t n_heads = ASM_EMPTY64;
+    if (cleaning) KV_STEP(asm_clean_rounds<W>(d, scratch, nw, n_chunks, d_hbase, clean_rounds, st, &removing_rounds, &n_heads));
+    if (n_heads == ASM_EMPTY64) KV_STEP(asm_count_heads<W>(d, nw, n_chunks, d_hbase, st, &n_heads));     // (else the last round left them)
+    d.hinv = nullptr;                                   // (the last compact has no one to leave the inverse map to)
     uint64_t n_unitigs = 0, n_out = 0;
     if (n_heads) {
         const size_t hs[5] = {n_heads * 4, n_heads * 4, n_heads * 4, (n_heads + 1) * 8, (n_heads + 1) * 8};
@@ -518,14 +783,16 @@ int asm_launch(const AsmLaunch &L, AsmDev d, hipStream_t st, const char *bases, 
         KV_HIP(hipMemcpyAsync(res->off.data() + at_u, d.uoff, n_unitigs * 8, hipMemcpyDeviceToHost, st));
         KV_HIP(hipMemcpyAsync(res->part.data() + at_u, d.upart, n_unitigs * 4, hipMemcpyDeviceToHost, st));
     }
-    unsigned long long ctrs[8];
+    unsigned long long ctrs[ASM_CTR_BYTES / 8];
     KV_HIP(hipMemcpyAsync(res->count.data() + L.part0, d.pcount, np * 4, hipMemcpyDeviceToHost, st));
     KV_HIP(hipMemcpyAsync(ctrs, d.ctr, sizeof(ctrs), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     res->off[at_u + n_unitigs] = at_b + n_out;
     res->stats[0] += ctrs[0]; res->stats[1] += ctrs[1]; res->stats[2] += ctrs[2]; res->stats[3] += n_heads; res->stats[4] += ctrs[3];
-    res->stats[5] += ctrs[2] - ctrs[4];
+    res->stats[5] += ctrs[2] - ctrs[9] - ctrs[4];      // solid, less the removed: live keys; less those on a unitig
     res->stats[6] += 1;
+    for (int i = 0; i < 4; ++i) res->clean[i] += ctrs[5 + i];
+    res->clean[4] += removing_rounds;
     return KV_OK;
 }
 
@@ -543,14 +810,39 @@ extern "C" int kv_assemble_plan(const uint64_t *read_off, uint64_t n_reads, cons
     return KV_OK;
 }
 
+extern "C" int kv_assemble_clean_plan(const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts, int ksize,
+                                      uint64_t mem_budget, uint32_t tip_nodes, uint32_t bubble_nodes, uint32_t clean_rounds,
+                                      uint64_t *launch_ends, uint64_t *n_launches)
+{
+    KV_REQUIRE(launch_ends && n_launches, KV_ERR_ARG, "kv_assemble_clean_plan: null argument");
+    KV_STEP(asm_check_args(read_off, n_reads, part_first, n_parts, ksize, 1));
+    KV_STEP(asm_check_clean(tip_nodes, bubble_nodes, clean_rounds));
+    std::vector<AsmLaunch> launches;
+    KV_STEP(asm_plan(read_off, n_reads, part_first, n_parts, ksize, mem_budget ? mem_budget : ASM_DEFAULT_BUDGET, launches,
+                     asm_cleaning(tip_nodes, bubble_nodes)));
+    for (size_t l = 0; l < launches.size(); ++l) launch_ends[l] = launches[l].part1;
+    *n_launches = launches.size();
+    return KV_OK;
+}
+
 extern "C" int kv_assemble_batch(const char *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts,
                                  int ksize, uint32_t min_count, uint64_t mem_budget, uint64_t *n_unitigs, uint64_t *n_bases, kv_assembly **out)
 {
+    return kv_assemble_clean_batch(bases, read_off, n_reads, part_first, n_parts, ksize, min_count, mem_budget, 0, 0, ASM_DEFAULT_CLEAN_ROUNDS,
+                                   n_unitigs, n_bases, out);
+}
+
+extern "C" int kv_assemble_clean_batch(const char *bases, const uint64_t *read_off, uint64_t n_reads, const uint64_t *part_first, uint64_t n_parts,
+                                       int ksize, uint32_t min_count, uint64_t mem_budget, uint32_t tip_nodes, uint32_t bubble_nodes,
+                                       uint32_t clean_rounds, uint64_t *n_unitigs, uint64_t *n_bases, kv_assembly **out)
+{
     KV_REQUIRE(out && n_unitigs && n_bases, KV_ERR_ARG, "kv_assemble_batch: null argument");
     KV_STEP(asm_check_args(read_off, n_reads, part_first, n_parts, ksize, min_count));
+    KV_STEP(asm_check_clean(tip_nodes, bubble_nodes, clean_rounds));
     KV_REQUIRE(bases || read_off[n_reads] == 0, KV_ERR_ARG, "kv_assemble_batch: null argument");
     std::vector<AsmLaunch> launches;
-    KV_STEP(asm_plan(read_off, n_reads, part_first, n_parts, ksize, mem_budget ? mem_budget : ASM_DEFAULT_BUDGET, launches));
+    KV_STEP(asm_plan(read_off, n_reads, part_first, n_parts, ksize, mem_budget ? mem_budget : ASM_DEFAULT_BUDGET, launches,
+                     asm_cleaning(tip_nodes, bubble_nodes)));
     hipStream_t st = kv_stream();
     kv_assembly *res = new kv_assembly;
     struct Guard { kv_assembly *h; ~Guard() { delete h; } } guard{res};
@@ -559,10 +851,12 @@ extern "C" int kv_assemble_batch(const char *bases, const uint64_t *read_off, ui
     AsmDev d = AsmDev();
     d.K = ksize;
     d.min_count = min_count;
+    d.tip_nodes = tip_nodes;
+    d.bubble_nodes = bubble_nodes;
     for (const AsmLaunch &L : launches) {
         if (L.n_windows == 0) continue;                 // (nothing to assemble: the counts stay 0)
-        if (ksize <= 31) KV_STEP(asm_launch<1>(L, d, st, bases, read_off, part_first, res));
-        else KV_STEP(asm_launch<2>(L, d, st, bases, read_off, part_first, res));
+        if (ksize <= 31) KV_STEP(asm_launch<1>(L, d, st, bases, read_off, part_first, clean_rounds, res));
+        else KV_STEP(asm_launch<2>(L, d, st, bases, read_off, part_first, clean_rounds, res));
     }
     *n_unitigs = res->part.size();
     *n_bases = res->bases.size();
@@ -586,6 +880,13 @@ extern "C" int kv_assemble_stats(kv_assembly *h, uint64_t *stats_out)
 {
     KV_REQUIRE(h && stats_out, KV_ERR_ARG, "kv_assemble_stats: null argument");
     std::copy(h->stats, h->stats + KV_ASSEMBLE_NSTATS, stats_out);
+    return KV_OK;
+}
+
+extern "C" int kv_assemble_clean_stats(kv_assembly *h, uint64_t *clean_out)
+{
+    KV_REQUIRE(h && clean_out, KV_ERR_ARG, "kv_assemble_clean_stats: null argument");
+    std::copy(h->clean, h->clean + KV_ASSEMBLE_NCLEAN, clean_out);
     return KV_OK;
 }
 
