@@ -221,9 +221,12 @@ int kv_reads_num_kmers(const kv_reads *r, int ksize, uint64_t *n_kmers);
  * increment landed); kv_unique_exact() gives the single-thread file-order value.   */
 int kv_consume(kv_sketch *s, const kv_reads *reads, int nbands, int band, const kv_sketch *mask,
                int threshold, int consume_masked, uint64_t *n_kmers_out);
-/* Re-derive n_unique_kmers exactly as a single khmer thread would have counted it over
- * `batches` consumed in this order into an initially empty sketch (needs 4 bytes of HBM
- * scratch per bin).  Used by `kevlar count` when --threads 1.                             */
+/* n_unique_kmers exactly as a single khmer thread would have counted it over `batches`
+ * consumed in this order into an initially empty sketch: `s` gives the geometry, the hash
+ * and k; its tables are neither read nor written, whatever they hold (needs 4 bytes of HBM
+ * scratch per bin, and every batch resident).  No caller in the product any more: `kevlar
+ * count` adds up kv_unique_new, batch by batch, which gives the same figure for a sketch
+ * that starts empty.  Kept as public ABI and held to the oracle by the tests.             */
 int kv_unique_exact(kv_sketch *s, const kv_reads *const *batches, int n_batches, int nbands,
                     int band, const kv_sketch *mask, int threshold, int consume_masked,
                     uint64_t *n_unique_out);

@@ -250,7 +250,11 @@ struct AbundParams {
     unsigned long long *hist;        // 256 entries (counts saturate at 255 / 15 / 1)
 };
 
-__global__ __launch_bounds__(KV_TILE_THREADS) void k_abund_hist(ReadsDev rd, const SketchDev *__restrict__ counts, AbundParams p)
+// the new k-mers bump the histogram AND are recorded in `tracking` -- they alone, as in khmer's loop: a counter of a byte or nibble
+// tracking sketch counts the new k-mers of its bin, not every occurrence.  Every bin of a k-mer that is not new is set already, before
+// the call or by the new k-mer that touched it first, so nothing else has to be written.
+__global__ __launch_bounds__(KV_TILE_THREADS) void k_abund_hist(ReadsDev rd, const SketchDev *__restrict__ counts,
+                                                               const SketchDev *__restrict__ tracking, AbundParams p)
 {
     __shared__ TileShared sh;
     __shared__ uint32_t lhist[256];
@@ -269,6 +273,7 @@ __global__ __launch_bounds__(KV_TILE_THREADS) void k_abund_hist(ReadsDev rd, con
         const uint32_t rc = sh.roff[r] + (sh.len[r] - (uint32_t)p.hp.k - i);
         const uint64_t h = kmer_hash_lds(sh.ascii, fwd, rc, p.hp);
         atomicAdd(&lhist[sketch_get(counts, h) & 255u], 1u);
+        sketch_add(tracking, h);
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
@@ -547,7 +552,8 @@ extern "C" int kv_unique_new(kv_sketch *s, const kv_reads *batch, int nbands, in
 // (get == 0) is recorded there and bumps hist[counts.get(kmer)].  "Not seen" at occurrence o means
 // some bin of the k-mer was clear before the call and no earlier occurrence of the call touched it --
 // the same first-toucher rule as kv_unique_exact, so the result is the single-thread one.  hist_out
-// has 65536 entries like khmer's (only the first 256 can be non-zero); tracking is updated.
+// has 65536 entries like khmer's (only the first 256 can be non-zero); tracking is updated as khmer
+// updates it: the new k-mers are recorded, each once (what a byte or nibble tracking sketch counts).
 extern "C" int kv_abundance_distribution(kv_sketch *counts, kv_sketch *tracking, const kv_reads *const *batches,
                                          int n_batches, uint64_t *hist_out)
 {
@@ -572,6 +578,7 @@ extern "C" int kv_abundance_distribution(kv_sketch *counts, kv_sketch *tracking,
     if (total == 0) return KV_OK;
     {
         std::lock_guard<std::mutex> lk(tracking->mu);
+        tracking->version++;
         FirstTouchParams p;
         memset(&p, 0, sizeof(p));
         p.f = make_consume_filter(k, tracking->h.hashfam, 0, 0, false, 0, 0);
@@ -628,17 +635,13 @@ extern "C" int kv_abundance_distribution(kv_sketch *counts, kv_sketch *tracking,
             KvProfScope prof("k_abund_hist");
             kv_ensure_dynamic_lds((const void *)k_abund_hist, r->tile_lds_bytes);
             hipLaunchKernelGGL(k_abund_hist, dim3(r->n_tiles), dim3(KV_TILE_THREADS), r->tile_lds_bytes, st, reads_dev(r),
-                               (const SketchDev *)counts->d_desc, a);
+                               (const SketchDev *)counts->d_desc, (const SketchDev *)tracking->d_desc, a);
         }
         KV_HIP(hipGetLastError());
         KV_HIP(hipMemcpyAsync(hist_out, d_hist.p, 256 * 8, hipMemcpyDeviceToHost, st));
         KV_HIP(hipStreamSynchronize(st));
-    }
-    // record every k-mer of the call in tracking (bins of k-mers that were not new are set already)
-    for (int b = 0; b < n_batches; ++b) {
-        uint64_t n = 0;
-        const int rc = kv_consume(tracking, batches[b], 0, 0, nullptr, 0, 0, &n);
-        if (rc != KV_OK) return rc;
+        for (int c = 0; c < 256; ++c) tracking->n_unique += hist_out[c];     // k_abund_hist recorded exactly these k-mers in tracking
+        tracking->occ_dirty = true;
     }
     return KV_OK;
 }
