@@ -523,6 +523,36 @@ int kv_localize_counts(kv_localize *h, uint32_t *counts_out, uint64_t n_windows)
 int kv_localize_stats(kv_localize *h, uint64_t *stats_out);
 int kv_localize_destroy(kv_localize *h);
 
+/* ---- the reference genome of `kevlar localize` / `kevlar alac` parsed on the device and kept there (kevlar/seqio.py
+ * parse_seq_dict, kevlar/localize.py; kv_genome.hip) ------------------------------------------------------
+ * kv_genome_open reads the file image -- uncompressed, blocked gzip (BGZF) or one gzip stream, told apart by their first bytes --,
+ * inflates it on the device and splits the FASTA there.  Lines end at LF and are taken without their trailing run of space, TAB, VT,
+ * FF and CR; a line whose first byte is '>' is a defline, its id the bytes behind the '>' up to the first space or TAB; a record's
+ * sequence is the concatenation of the stripped lines up to the next defline; text in front of the first defline is ignored.  The
+ * genome text -- the sequences in file order, one '>' byte between neighbours -- stays in one device allocation.  segment_text is the
+ * number of text bytes taken per pass (0: 256 MiB; at most 1 GiB; a gzip stream's passes are as long as its decoder makes them).
+ * KV_ERR_TYPE declines a file the host's text layer would read differently, and the caller parses it on the host: a byte >= 0x80, a
+ * byte 0x1c-0x1f, a NUL, a CR that no LF follows, more than 4096 strippable bytes on end, an id stretch of more than 4096 bytes, a
+ * gzip stream the device decoder does not take.  Duplicate ids are the caller's to refuse.
+ * kv_genome_info: the number of sequences, the bytes of genome text, stats[0..3] = container (0 plain, 1 BGZF, 2 gzip), passes, bytes
+ * of file text, bytes allocated for the genome text; id i = ids[id_offs[i] .. id_offs[i + 1]); sequence i = text[starts[i] ..
+ * starts[i] + lengths[i]).  The arrays belong to the handle and live as long as it does; any of the pointers may be NULL.
+ * kv_localize_scan_genome: kv_localize_scan over the whole resident text in one call, nothing uploaded.  The text is scanned in
+ * chunks that overlap by Z - 1 bytes; chunk_bytes is the most one holds (0: the whole text in one).  A chunk begins a multiple of
+ * chunk_bytes - (Z - 1) behind the text's first byte, that step rounded down to a multiple of 16 where it is 16 or more.  Matches,
+ * *n_found, the overflow contract (only `capacity` matches written, the caller repeats the call with larger buffers, the repeat
+ * does not count again) and the per-seed counters are those of kv_localize_scan.
+ * kv_genome_fetch: n slices text[global_start[i] .. global_start[i] + len[i]) in one gather launch, clipped at the text's end; slice
+ * i arrives at out[out_offs[i] .. out_offs[i + 1]) (out: room for the sum of len; out_offs: n + 1 entries).                    */
+typedef struct kv_genome kv_genome;
+int kv_genome_open(const char *path, uint64_t segment_text, kv_genome **out);
+int kv_genome_info(kv_genome *g, uint64_t *n_seqs, uint64_t *text_bytes, uint64_t *stats, const char **ids, const uint64_t **id_offs,
+                   const uint64_t **starts, const uint64_t **lengths);
+int kv_localize_scan_genome(kv_localize *h, kv_genome *g, uint64_t chunk_bytes, uint32_t *ids_out, uint64_t *pos_out, uint64_t capacity,
+                            uint64_t *n_found);
+int kv_genome_fetch(kv_genome *g, const uint64_t *global_start, const uint64_t *len, uint64_t n, char *out, uint64_t *out_offs);
+int kv_genome_close(kv_genome *g);
+
 /* ---- calls against BED regions for `kevlar varfilter` (kevlar/varfilter.py, kevlar.parse_bed; kv_varfilter.hip) ----------------
  * The reference keeps the calls in an interval tree and looks every BED line up in it.  Here the calls become an index on the
  * device -- sorted by (chromosome, start), with the running maximum of `end` per chromosome -- and the BED text is scanned against

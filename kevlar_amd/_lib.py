@@ -147,6 +147,11 @@ SIGNATURES = {
     'kv_localize_counts': (i32, [vp, vp, u64]),
     'kv_localize_stats': (i32, [vp, vp]),
     'kv_localize_destroy': (i32, [vp]),
+    'kv_genome_open': (i32, [cstr, u64, vpp]),
+    'kv_genome_info': (i32, [vp, u64p, u64p, vp, vpp, vpp, vpp, vpp]),
+    'kv_localize_scan_genome': (i32, [vp, vp, u64, vp, vp, u64, u64p]),
+    'kv_genome_fetch': (i32, [vp, vp, vp, u64, vp, vp]),
+    'kv_genome_close': (i32, [vp]),
     'kv_varfilter_create': (i32, [vp, vp, u64, vp, vp, vp, u64, vpp]),
     'kv_varfilter_scan': (i32, [vp, vp, u64, u64]),
     'kv_varfilter_bad_line': (i32, [vp, u64p]),

@@ -398,6 +398,15 @@ int kv_fastq_device_next(KvFastqDevice *d, uint64_t max_reads, kv_reads **reads_
 // raw text (four lines each) of records idx[0 .. n) of the batch last returned: record i at blob[offs[i] .. offs[i + 1])
 int kv_fastq_device_fetch(KvFastqDevice *d, const uint64_t *idx, uint64_t n, std::string *blob, std::vector<uint64_t> *offs);
 
+// ---- a reference genome parsed and kept on the device (kv_genome.hip) ----
+// the joined text of a kv_genome for the kernels of other files: n bytes at text, `alloc` of them readable (a multiple of 16,
+// zero behind the text); uid: never reused
+struct KvGenomeView {
+    const uint8_t *text;
+    uint64_t n, alloc, uid;
+};
+int kv_genome_view(const kv_genome *g, KvGenomeView *view);
+
 // growing text buffer of the native writers (kv_format_augmented, kv_format_records): malloc'ed, handed to the caller as it is
 struct KvTextOut {
     char *buf = nullptr;

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "kv_device.h"
+#include "kv_genome_plan.h"
 #include "kv_roll2bit_device.h"
 
 namespace {
@@ -436,6 +437,74 @@ extern "C" int kv_localize_scan(kv_localize *h, const char *text, uint64_t n_byt
         KV_HIP(hipStreamSynchronize(st));
     }
     if (*found > capacity) { h->ovf = true; h->ovf_off = global_offset; h->ovf_len = n_bytes; }
+    return KV_OK;
+}
+
+// kv_localize_scan over the text of a genome that sits in HBM (kv_genome.hip): nothing is uploaded.  All chunks append to the one
+// pair of match buffers and are counted by the one d_ctr[0]; a chunk that begins on a 16-byte boundary is scanned where it lies,
+// any other is copied to the handle's aligned chunk buffer first (k_loc_scan loads the text 16 bytes at a time).
+extern "C" int kv_localize_scan_genome(kv_localize *h, kv_genome *g, uint64_t chunk_bytes, uint32_t *ids_out, uint64_t *pos_out, uint64_t capacity,
+                                       uint64_t *n_found)
+{
+    KV_REQUIRE(h && g && n_found && (capacity == 0 || (ids_out && pos_out)), KV_ERR_ARG, "kv_localize_scan_genome: null argument");
+    KvGenomeView gv;
+    KV_STEP(kv_genome_view(g, &gv));
+    KV_REQUIRE(gv.n < (1ull << 40), KV_ERR_ARG, "kv_localize_scan_genome: text of %llu bytes", (unsigned long long)gv.n);
+    *n_found = 0;
+    // (the uid of a genome, inverted, is no offset a chunk of an uploaded text has)
+    const bool repeat = h->ovf && h->ovf_off == ~gv.uid && h->ovf_len == gv.n;
+    h->ovf = false;
+    if (gv.n < (uint64_t)h->Z || h->n_distinct == 0) return KV_OK;
+    const GnScanPlan plan = gn_scan_plan(gv.n, (uint64_t)h->Z, chunk_bytes);
+    KV_REQUIRE((plan.len + LOC_TILE - 1) / LOC_TILE < 0x7FFFFFFFull, KV_ERR_ARG, "kv_localize_scan_genome: chunk too large");
+    hipStream_t st = kv_stream();
+    hipError_t e = h->ids.need_exact(std::max<uint64_t>(capacity, 1) * 4);
+    if (e == hipSuccess) e = h->pos.need_exact(std::max<uint64_t>(capacity, 1) * 8);
+    if (e == hipSuccess && (plan.step & 15) && plan.n_chunks > 1) e = h->text.need_exact((plan.len + 15) & ~15ull);
+    KV_REQUIRE(e == hipSuccess, KV_ERR_HIP, "scan buffers allocation failed: %s", hipGetErrorString(e));
+    KV_HIP(hipMemsetAsync(h->d_ctr, 0, 8, st));
+    LocScan p;
+    p.Z = h->Z;
+    p.keys = h->d_keys; p.table = h->d_table; p.capmask = h->capmask; p.pf = h->d_pf; p.pfmask = h->pfmask;
+    p.occ = h->d_occ; p.ctr = h->d_ctr; p.out_ids = (uint32_t *)h->ids.p; p.out_pos = (uint64_t *)h->pos.p; p.cap = capacity; p.count = repeat ? 0 : 1;
+    {
+        KvProfScope prof("k_loc_scan");
+        for (uint64_t k = 0; k < plan.n_chunks; ++k) {
+            const uint64_t start = k * plan.step, size = std::min<uint64_t>(plan.len, gv.n - start);
+            if (size < (uint64_t)h->Z) break;
+            if ((start & 15) == 0) {
+                p.text = gv.text + start;
+                p.alloc = std::min<uint64_t>((size + 15) & ~15ull, gv.alloc - start);
+            } else {
+                KV_HIP(hipMemcpyAsync(h->text.p, gv.text + start, size, hipMemcpyDeviceToDevice, st));
+                p.text = (const uint8_t *)h->text.p;
+                p.alloc = h->text.bytes & ~15ull;
+            }
+            p.n = size; p.goff = start;
+            const uint64_t n_tiles = (size - (uint64_t)h->Z + 1 + LOC_TILE - 1) / LOC_TILE;
+            const dim3 grid((unsigned)n_tiles), block(LOC_THREADS);
+            switch (h->W) {
+            case 1: hipLaunchKernelGGL(k_loc_scan<1>, grid, block, 0, st, p); break;
+            case 2: hipLaunchKernelGGL(k_loc_scan<2>, grid, block, 0, st, p); break;
+            case 3: hipLaunchKernelGGL(k_loc_scan<3>, grid, block, 0, st, p); break;
+            default: hipLaunchKernelGGL(k_loc_scan<4>, grid, block, 0, st, p); break;
+            }
+        }
+    }
+    KV_HIP(hipGetLastError());
+    hipError_t re = hipSuccess;
+    KvReadback rb;
+    const unsigned long long *found = rb.add((const unsigned long long *)h->d_ctr, 1, st, &re);
+    KV_HIP(re);
+    KV_HIP(rb.wait(st));
+    *n_found = *found;
+    const uint64_t n_copy = std::min<uint64_t>(*found, capacity);
+    if (n_copy) {
+        KV_HIP(hipMemcpyAsync(ids_out, h->ids.p, n_copy * 4, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipMemcpyAsync(pos_out, h->pos.p, n_copy * 8, hipMemcpyDeviceToHost, st));
+        KV_HIP(hipStreamSynchronize(st));
+    }
+    if (*found > capacity) { h->ovf = true; h->ovf_off = ~gv.uid; h->ovf_len = gv.n; }
     return KV_OK;
 }
 

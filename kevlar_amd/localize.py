@@ -106,6 +106,7 @@ def contigs_2_seeds(partstream, seedstream, seedsize=51):
 class Genome(object):
     """The sequences of a reference as one text: sequence i is text[starts[i] : starts[i] + len(seqs[i])], with one SEPARATOR
     byte between neighbours, so a global position maps back to (sequence, local position) by a search over `starts`."""
+    on_device = False
 
     def __init__(self, records):
         self.ids = [seqid for seqid, seq in records]
@@ -118,7 +119,9 @@ class Genome(object):
 
     @classmethod
     def from_file(cls, refrfile):
-        """seqid = the defline up to the first blank"""
+        """seqid = the defline up to the first blank; `refrfile`: a path, '-' or an open text stream (left open)"""
+        if not (refrfile is None or isinstance(refrfile, str)):
+            return cls(list(kevlar_amd.seqio.parse_seq_dict(refrfile).items()))
         stream = kevlar_amd.open(refrfile, 'r')
         try:
             return cls(list(kevlar_amd.seqio.parse_seq_dict(stream).items()))
@@ -134,6 +137,171 @@ class Genome(object):
         positions = np.asarray(positions, dtype=np.int64)
         which = np.searchsorted(self.starts, positions, side='right') - 1
         return which, positions - self.starts[which]
+
+
+class GenomeDeclined(ValueError):
+    """The device FASTA splitter does not take this file (KV_ERR_TYPE): the host parser reads it."""
+
+
+class _PendingSlice(object):
+    """A slice of a device-resident sequence that has been asked for and not fetched yet: it knows its length, and `value` once
+    DeviceGenome.fetch_many has filled the collector it sits in."""
+
+    def __init__(self, index, start, stop):
+        self.index, self.start, self.stop = index, start, stop
+        self.value = None
+
+    def __len__(self):
+        return self.stop - self.start
+
+    def __str__(self):
+        return self.value
+
+
+class _LazySequence(object):
+    """Sequence i of a DeviceGenome as far as localize needs a string: len() and slicing with Python's clipping.  A slice is
+    fetched from the device at once, or, with a collector, noted there and fetched with all the others."""
+
+    def __init__(self, genome, index, collector=None):
+        self._genome, self._index, self._collector = genome, index, collector
+
+    def __len__(self):
+        return int(self._genome.lengths[self._index])
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice):
+            key = range(len(self))[key]
+            key = slice(key, key + 1)
+        start, stop, step = key.indices(len(self))
+        if step != 1:
+            return str(self)[key]
+        stop = max(stop, start)
+        if self._collector is not None:
+            pending = _PendingSlice(self._index, start, stop)
+            self._collector.append(pending)
+            return pending
+        return self._genome.fetch_many([(self._index, start, stop)])[0]
+
+    def __str__(self):
+        return self._genome.fetch_many([(self._index, 0, len(self))])[0]
+
+
+class DeviceGenome(object):
+    """Genome whose text was parsed on the device (kv_genome_open) and stays there: `ids`, `starts`, `lengths` and `locate` as
+    Genome has them, the sequences as lazy slices (`seqdict`, `fetch_many`), and SeedSet.scan_genome scans the text where it is.
+    Raises GenomeDeclined for a file the device does not take; duplicate ids are the AssertionError of seqio.parse_seq_dict."""
+    on_device = True
+
+    def __init__(self, path, segment_text=0):
+        self._handle = None
+        _lib.require_device()
+        self._lib = _lib.load()
+        handle = ctypes.c_void_p()
+        rc = self._lib.kv_genome_open(str(path).encode(), int(segment_text), ctypes.byref(handle))
+        if rc == _lib.KV_ERR_TYPE:
+            raise GenomeDeclined(_lib.last_error())
+        _lib.check(rc)
+        self._handle = handle
+        nseq, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        stats = np.zeros(4, dtype=np.uint64)
+        ids, id_offs, starts, lengths = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(self._lib.kv_genome_info(handle, ctypes.byref(nseq), ctypes.byref(nbytes), stats.ctypes.data, ctypes.byref(ids),
+                                            ctypes.byref(id_offs), ctypes.byref(starts), ctypes.byref(lengths)))
+        n = int(nseq.value)
+        self.n_text = int(nbytes.value)
+        self.container, self.n_segments = ('plain', 'bgzf', 'gzip')[int(stats[0])], int(stats[1])
+
+        def column(pointer, count):
+            if count == 0:
+                return np.zeros(0, dtype=np.int64)
+            return np.ctypeslib.as_array(ctypes.cast(pointer, ctypes.POINTER(ctypes.c_uint64)), shape=(count,)).astype(np.int64)
+        offs = column(id_offs, n + 1)
+        blob = ctypes.string_at(ids, int(offs[-1])) if n and offs[-1] else b''
+        self.ids = [blob[offs[i]:offs[i + 1]].decode('ascii') for i in range(n)]
+        self.starts, self.lengths = column(starts, n), column(lengths, n)
+        seen = set()
+        for seqid in self.ids:
+            assert seqid not in seen, seqid
+            seen.add(seqid)
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.kv_genome_close(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def seqdict(self, collector=None):
+        """{id: lazy sequence}; with a list as `collector` the slices taken are noted in it and filled by resolve()"""
+        return {seqid: _LazySequence(self, i, collector) for i, seqid in enumerate(self.ids)}
+
+    def locate(self, positions):
+        """(sequence index, local position) of global positions"""
+        positions = np.asarray(positions, dtype=np.int64)
+        which = np.searchsorted(self.starts, positions, side='right') - 1
+        return which, positions - self.starts[which]
+
+    def fetch_text(self, start, length):
+        """bytes [start, start + length) of the genome text, clipped at its end"""
+        starts, lens = np.array([start], dtype=np.uint64), np.array([length], dtype=np.uint64)
+        out = ctypes.create_string_buffer(max(int(length), 1))
+        offs = np.zeros(2, dtype=np.uint64)
+        _lib.check(self._lib.kv_genome_fetch(self._handle, starts.ctypes.data, lens.ctypes.data, 1, out, offs.ctypes.data))
+        return out.raw[:int(offs[1])]
+
+    def fetch_many(self, requests):
+        """[sequence[start:stop] as str for (sequence index, start, stop) in requests], clipped as Python clips slices, all of
+        them in one gather launch"""
+        requests = list(requests)
+        if not requests:
+            return []
+        index = np.array([r[0] for r in requests], dtype=np.int64)
+        length = self.lengths[index]
+        start = np.clip(np.array([r[1] for r in requests], dtype=np.int64), 0, length)
+        stop = np.clip(np.array([r[2] for r in requests], dtype=np.int64), start, length)
+        starts = (self.starts[index] + start).astype(np.uint64)
+        lens = (stop - start).astype(np.uint64)
+        out = ctypes.create_string_buffer(max(int(lens.sum()), 1))
+        offs = np.zeros(len(requests) + 1, dtype=np.uint64)
+        _lib.check(self._lib.kv_genome_fetch(self._handle, starts.ctypes.data, lens.ctypes.data, len(requests), out, offs.ctypes.data))
+        blob = out.raw[:int(offs[-1])].decode('latin-1')
+        offs = offs.astype(np.int64).tolist()
+        return [blob[offs[i]:offs[i + 1]] for i in range(len(requests))]
+
+    def resolve(self, collector):
+        """fetch every slice noted in `collector` (one fetch_many) and fill its value"""
+        for pending, value in zip(collector, self.fetch_many([(p.index, p.start, p.stop) for p in collector])):
+            pending.value = value
+
+
+last_load = {}          # how the last load_genome went: on_device, container, declined (the reason, or None); for tests and tools
+
+
+def load_genome(refrfile, segment_text=0):
+    """The reference for localize: parsed and kept on the device when `refrfile` is a file on disk that the device splitter
+    takes (`on_device` is then true), else today's host Genome -- for '-', an open stream, a file whose name and content disagree
+    about gzip (the host goes by the name), and a file the device declines."""
+    import os
+    last_load.clear()
+    last_load.update(on_device=False, declined=None)
+    if isinstance(refrfile, str) and refrfile != '-' and os.path.isfile(refrfile):
+        with open(refrfile, 'rb') as fh:
+            gzipped = fh.read(2) == b'\x1f\x8b'
+        if gzipped == refrfile.endswith('.gz'):
+            try:
+                genome = DeviceGenome(refrfile, segment_text=segment_text)
+                last_load.update(on_device=True, container=genome.container)
+                return genome
+            except GenomeDeclined as why:
+                last_load.update(declined=str(why))           # (why the device did not take it; nothing is printed)
+    return Genome.from_file(refrfile)
 
 
 class SeedSet(object):
@@ -230,14 +398,32 @@ class SeedSet(object):
             return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
         return np.concatenate(got_ids), np.concatenate(got_pos)
 
+    def scan_genome(self, genome, chunk_bytes=0, capacity=DEFAULT_MATCH_CAPACITY):
+        """scan() over the text of a DeviceGenome where it lies: one call, nothing uploaded.  chunk_bytes: the most text one
+        chunk holds (0: the whole text in one); more matches than `capacity`: the call is repeated with room for all of them."""
+        capacity = max(int(capacity), 1)
+        found = ctypes.c_uint64(0)
+        while True:
+            ids = np.empty(capacity, dtype=np.uint32)
+            pos = np.empty(capacity, dtype=np.uint64)
+            _lib.check(self._lib.kv_localize_scan_genome(self._handle, genome._handle, int(chunk_bytes), ids.ctypes.data, pos.ctypes.data,
+                                                         capacity, ctypes.byref(found)))
+            if found.value <= capacity:
+                return ids[:found.value].copy(), pos[:found.value].copy()
+            capacity = max(int(found.value), 2 * capacity)
+
 
 class SeedMatches(object):
     """Matches of a seed set in a genome, sorted by seed id, in CSR form: seed ids `seeds` (ascending), the matches of
     seeds[r] are rows indptr[r] .. indptr[r + 1] of (`seqidx`, `local`); `row_of` maps a seed id to r (-1: no match kept)."""
 
-    def __init__(self, seedset, genome, max_occ=DEFAULT_MAX_OCC, chunk_bytes=DEFAULT_CHUNK_BYTES,
+    def __init__(self, seedset, genome, max_occ=DEFAULT_MAX_OCC, chunk_bytes=None,
                  capacity=DEFAULT_MATCH_CAPACITY):
-        ids, pos = seedset.scan(genome.text, chunk_bytes=chunk_bytes, capacity=capacity)
+        # chunk_bytes None: DEFAULT_CHUNK_BYTES of an uploaded text at a time; a resident text (no upload buffer to bound) in one
+        if genome.on_device:
+            ids, pos = seedset.scan_genome(genome, chunk_bytes=chunk_bytes or 0, capacity=capacity)
+        else:
+            ids, pos = seedset.scan(genome.text, chunk_bytes=chunk_bytes or DEFAULT_CHUNK_BYTES, capacity=capacity)
         self.counts = seedset.counts()
         if max_occ:
             keep = self.counts[ids] <= max_occ
@@ -278,7 +464,7 @@ class SeedMatches(object):
         return out
 
 
-def get_seed_matches(seedfile, refrfile, seedsize=51, max_occ=DEFAULT_MAX_OCC, chunk_bytes=DEFAULT_CHUNK_BYTES):
+def get_seed_matches(seedfile, refrfile, seedsize=51, max_occ=DEFAULT_MAX_OCC, chunk_bytes=None):
     """{canonical seed: {(seqid, position)}} for the seeds of a FASTA file: the reference's dictionary, computed by the device
     scan.  A seed with more than `max_occ` positions is left out (see the module's docstring)."""
     kevlar_amd.plog('[kevlar::localize] computing seed matches')
@@ -288,7 +474,7 @@ def get_seed_matches(seedfile, refrfile, seedsize=51, max_occ=DEFAULT_MAX_OCC, c
     finally:
         if seedfile not in ('-', None):
             stream.close()
-    genome = Genome.from_file(refrfile)
+    genome = load_genome(refrfile)
     with SeedSet(seqs, seedsize) as seedset:
         matches = SeedMatches(seedset, genome, max_occ=max_occ, chunk_bytes=chunk_bytes)
         seed_index = defaultdict(set)
@@ -318,12 +504,14 @@ def cutout(contigs, refrseqs, seed_matches, seedsize=51, delta=50, maxdiff=None,
 
 
 def localize(partstream, refrfile, seedsize=51, delta=50, maxdiff=None, inclpattern=None, exclpattern=None, debug=False,
-             max_occ=DEFAULT_MAX_OCC, chunk_bytes=DEFAULT_CHUNK_BYTES):
+             max_occ=DEFAULT_MAX_OCC, chunk_bytes=None):
     """(partition id, ReferenceCutout) for every reference target of every partition of (partition id, contigs) pairs.
 
-    maxdiff=None clusters by three times the partition's longest contig; a false maxdiff (0) gives one cutout per sequence.
-    max_occ: a seed with more genome positions than this contributes none (the reference's bwa keeps an irreproducible sample
-    of 5000 of them instead).  chunk_bytes: genome text per scan call."""
+    refrfile: a path (the genome is then parsed and kept on the device where the file allows it: load_genome), '-' or an open
+    text stream (parsed on the host).  maxdiff=None clusters by three times the partition's longest contig; a false maxdiff (0)
+    gives one cutout per sequence.  max_occ: a seed with more genome positions than this contributes none (the reference's bwa
+    keeps an irreproducible sample of 5000 of them instead).  chunk_bytes: genome text per scan chunk (None: 64 MiB of a text
+    that is uploaded, all of a resident one)."""
     partdata = [(partid, list(part)) for partid, part in partstream]
     kevlar_amd.plog('[kevlar::localize]', 'loaded {} read partitions into memory'.format(len(partdata)))
     contigs = [contig for partid, part in partdata for contig in part]
@@ -332,33 +520,50 @@ def localize(partstream, refrfile, seedsize=51, delta=50, maxdiff=None, inclpatt
         # the reference reports the index of the last seed, one less than their number (0 when there is none)
         kevlar_amd.plog('[kevlar::localize]', 'contigs decomposed into {} seeds'.format(max(seedset.n_distinct - 1, 0)))
         kevlar_amd.plog('[kevlar::localize] computing seed matches')
-        genome = Genome.from_file(refrfile)
+        genome = load_genome(refrfile)
         matches = SeedMatches(seedset, genome, max_occ=max_occ, chunk_bytes=chunk_bytes)
     kevlar_amd.plog('[kevlar::localize]', 'found positions for {} seeds'.format(len(matches)))
     if len(matches) == 0:
         kevlar_amd.plog('[kevlar::localize]', 'WARNING: no reference matches')
         return
     kevlar_amd.plog('[kevlar::localize]', 'loading reference sequences into memory')
-    refrseqs = genome.seqdict()          # (the scan read them already)
+    # a resident genome hands out slices that are fetched later, all cutouts of the call in one gather (DeviceGenome.resolve)
+    pending = [] if genome.on_device else None
+    refrseqs = genome.seqdict(pending) if genome.on_device else genome.seqdict()          # (the scan read them already)
     kevlar_amd.plog('[kevlar::localize]', 'computing the reference target sequence for each partition')
     progress = kevlar_amd.ProgressIndicator('[kevlar::localize]     computed targets for {counter} partitions',
                                             interval=100, breaks=[1000, 10000, 100000])
+
+    def targets():
+        contig_at = 0
+        for partid, part in partdata:
+            progress.update()
+            windows = np.arange(seedset.wpre[contig_at], seedset.wpre[contig_at + len(part)])
+            contig_at += len(part)
+            rows = matches.of_windows(windows)
+            localizer = Localizer(seedsize, incl=inclpattern, excl=exclpattern)
+            for which, position in zip(matches.seqidx[rows].tolist(), matches.local[rows].tolist()):
+                localizer.add_seed_match(genome.ids[which], position)
+            clusterdist = maxdiff
+            if clusterdist is None:
+                clusterdist = 3 * max(len(contig.sequence) for contig in part)
+            for gdna in localizer.get_cutouts(refrseqs=refrseqs, delta=delta, clusterdist=clusterdist):
+                yield partid, gdna
+
     ncutouts = 0
-    contig_at = 0
-    for partid, part in partdata:
-        progress.update()
-        windows = np.arange(seedset.wpre[contig_at], seedset.wpre[contig_at + len(part)])
-        contig_at += len(part)
-        rows = matches.of_windows(windows)
-        localizer = Localizer(seedsize, incl=inclpattern, excl=exclpattern)
-        for which, position in zip(matches.seqidx[rows].tolist(), matches.local[rows].tolist()):
-            localizer.add_seed_match(genome.ids[which], position)
-        clusterdist = maxdiff
-        if clusterdist is None:
-            clusterdist = 3 * max(len(contig.sequence) for contig in part)
-        for gdna in localizer.get_cutouts(refrseqs=refrseqs, delta=delta, clusterdist=clusterdist):
-            ncutouts += 1
-            yield partid, gdna
+    if genome.on_device:
+        found = list(targets())
+        genome.resolve(pending)
+        genome.close()
+        for partid, gdna in found:
+            if isinstance(gdna.sequence, _PendingSlice):
+                gdna.sequence = gdna.sequence.value
+        found = iter(found)
+    else:
+        found = targets()
+    for partid, gdna in found:
+        ncutouts += 1
+        yield partid, gdna
     if ncutouts == 0:
         kevlar_amd.plog('[kevlar::localize]', 'WARNING: no reference matches')
 
